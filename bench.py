@@ -11,8 +11,12 @@ SURVEY.md 8(e)); each rank verifies its shard, and the per-rank verdict
 bitmaps are all-gathered over RCCL (the one exchange step) inside the timed
 region, then checked against the construction.
 
-The default run also measures every other BASELINE.json configuration at its
-stated size, each with its own verdict check, roofline and CPU baseline:
+A plain run sets up, warms up, times the K steps, writes the last step's
+verdicts if --dump-outputs DIR is given, and prints the result line.  With
+--full the run also reports per-stage times, the roofline, the host-record
+pass, the small-batch and ingest legs and the CPU baseline of the headline
+chain, and measures every other BASELINE.json configuration at its stated
+size, each with its own verdict check, roofline and CPU baseline:
   rlc            configs[2]: RLC batch verify of the same resident chain
   configs3       configs[3]: 10M-round pedersen-bls-unchained and
                  bls-unchained-on-g1 chains, per-round verify and the
@@ -21,7 +25,8 @@ stated size, each with its own verdict check, roofline and CPU baseline:
   multi_abi      the product multi-GPU boundary (dgpu_verify_multi: one
                  process drives all N GPUs, host records, RCCL gathers), run
                  in a child process while the ranks wait
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rounds R] [--no-legs]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rounds R] [--dump-outputs DIR]
+    python bench.py --full [--gpus N] [--steps K] [--warmup W] [--rounds R] [--no-legs]
     python bench.py --driver abi [--gpus N]   # the value through dgpu_verify_multi
 
 With --gpus N > 1 and no torch.distributed environment, bench.py starts the
@@ -96,7 +101,35 @@ def parse(argv=None):
                     help="only the small-batch latency leg (host records, n = 1 .. 4096) on a 4096-round chain")
     ap.add_argument("--dry-run", action="store_true",
                     help="print the chosen driver, the rank count and each rank's shard, touch no GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, measure everything else: per-stage times and roofline, the "
+                         "host-record pass, RLC, small-batch and ingest legs, CPU baselines, and the configs[3] / "
+                         "configs[4] / multi_abi legs (each can be switched off with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the verdicts; for "
+                         "--mode recover the recovered signatures and ok flags) as DIR/<name>.npy in float32")
     return ap.parse_args(argv)
+
+
+# --dump-outputs writes at most this many float32 values in all (48 MB)
+DUMP_MAX_VALUES = 12_000_000
+
+
+def dump_outputs(d, arrays):
+    """The timed path's outputs as d/<name>.npy (float32).  An array that does
+    not fit its share of DUMP_MAX_VALUES is written as a fixed, seeded sample
+    of its flattened values (the same indices for the same shape)."""
+    os.makedirs(d, exist_ok=True)
+    left = DUMP_MAX_VALUES
+    todo = sorted(arrays.items(), key=lambda kv: np.asarray(kv[1]).size)
+    for k, (name, a) in enumerate(todo):
+        a = np.asarray(a)
+        share = left // (len(todo) - k)
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))
+            a = a.reshape(-1)[idx]
+        left -= a.size
+        np.save(os.path.join(d, name + ".npy"), a.astype(np.float32))
 
 
 def log(*a):
@@ -325,7 +358,7 @@ def cpu_threads():
 
 
 # ---------------------------------------------------------------- configs[4]
-def recover_leg(args, world, rank, local, n_total, steps, warmup, cpu_seconds):
+def recover_leg(args, world, rank, local, n_total, steps, warmup, cpu_seconds, main=False):
     """configs[4]: batch threshold recovery (kyber tbls.Recover as the
     aggregator calls it, chain/beacon/chain.go:158-168): per round t partials
     (one invalid in --bad-rate of the rounds), VerifyPartial, selection +
@@ -369,18 +402,21 @@ def recover_leg(args, world, rank, local, n_total, steps, warmup, cpu_seconds):
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
-    stage_ms = stage_times(lib, ctx, step)
+    stage_ms = stage_times(lib, ctx, step) if args.full else {}
     elapsed, _ = timed(step, steps, world, dev)
+    ok = d_ok.cpu().numpy().astype(bool)
+    out = d_out.cpu().numpy()
+    if main and args.dump_outputs:  # each rank's own shard of the batch
+        dump_outputs(args.dump_outputs, {"ok" if world == 1 else f"ok_rank{rank}": ok,
+                                         "recovered" if world == 1 else f"recovered_rank{rank}": out})
     # per-step wall times (diagnostic: host-side gaps between the kernels)
     step_ms = []
-    for _ in range(2):
+    for _ in range(2 if args.full else 0):
         t0 = time.perf_counter()
         step()
         torch.cuda.synchronize()
         step_ms.append((time.perf_counter() - t0) * 1e3)
 
-    ok = d_ok.cpu().numpy().astype(bool)
-    out = d_out.cpu().numpy()
     mism = int((ok != expect_ok).sum()) + int((out[ok & expect_ok] != expect[ok & expect_ok]).any(axis=1).sum())
     mism_t = torch.tensor([mism], device=coll_device(dev))
     if world > 1:
@@ -404,7 +440,7 @@ def recover_leg(args, world, rank, local, n_total, steps, warmup, cpu_seconds):
             res["roofline"]["items_note"] = ("rounds per pass (the batched check: one pairing and the MSMs per "
                                              "round; rounds on the exact path add engine items)")
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 from oracle import cpu_baseline as cb
                 exp_sigs = [bytes(expect[i]) if expect_ok[i] else None for i in range(n)]
@@ -630,12 +666,16 @@ def verify_leg(args, world, rank, local, scheme, n_total, steps, warmup, mode="p
     log(f"{scheme} warmup done")
     # per-stage kernel timing (HIP events on the launch stream), single lane;
     # the first of the two passes absorbs the single-lane buffer growth
-    stage_ms = stage_times(lib, ctx, step, passes=2 if main else 1)
-    log("stage times", json.dumps(stage_ms))
+    stage_ms = {}
+    if args.full:
+        stage_ms = stage_times(lib, ctx, step, passes=2 if main else 1)
+        log("stage times", json.dumps(stage_ms))
     # the exchange step: every rank's verdict bitmap to every rank (RCCL)
     elapsed, verdicts = timed(step, steps, world, dev,
                               after=lambda: gather_verdict_bits(d_bits, n, n_total, world, rank))
     log(f"{scheme}: {steps} steps in {elapsed:.3f} s")
+    if main and rank == 0 and args.dump_outputs:  # the gathered verdicts of the last step, one per round
+        dump_outputs(args.dump_outputs, {"verdicts": verdicts})
     expect = np.ones(n_total, dtype=bool)
     expect[list(bad.keys())] = False
     res = {"value": n_total * steps / elapsed, "unit": "rounds/s", "steps": steps, "warmup": warmup,
@@ -691,12 +731,12 @@ def verify_leg(args, world, rank, local, scheme, n_total, steps, warmup, mode="p
                                    "bisection (dgpu_verify_beacons_device mode DGPU_MODE_RLC)")}
         log(f"rlc: {res['rlc']['value']:.0f} rounds/s")
 
-    if main and rank == 0 and world == 1 and not args.no_small_batch:
+    if main and args.full and rank == 0 and world == 1 and not args.no_small_batch:
         try:
             res["small_batch"] = small_batch_leg(chain, scheme)
         except Exception as e:  # reported, never fatal
             res["small_batch"] = {"error": repr(e)}
-    if main and rank == 0 and world == 1 and not args.no_ingest:
+    if main and args.full and rank == 0 and world == 1 and not args.no_ingest:
         _EXPECT[id(chain)] = {gi - lo: False for gi in bad if lo <= gi < hi}
         try:
             res["ingest"] = ingest_leg(chain, args.ingest_rounds, scheme)
@@ -780,6 +820,9 @@ def main_abi(args):
             sigs, _ = run()
         el = wall() - t0
         okv = np.array([s is not None for s in sigs])
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"ok": okv, "recovered": np.array(
+                [np.frombuffer(s, dtype=np.uint8) if s is not None else np.zeros(96, np.uint8) for s in sigs])})
         mism = int((okv != expect_ok).sum()) + sum(1 for i, s in enumerate(sigs) if s is not None and expect_ok[i]
                                                   and s != bytes(expect[i]))
         res = {"value": n_total * args.steps / el, "unit": "rounds/s", "ms_per_step": el / args.steps * 1e3,
@@ -802,6 +845,8 @@ def main_abi(args):
         for _ in range(args.steps):
             reason = run()
         el = wall() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"reasons": reason})
         expect = np.ones(n_total, dtype=bool)
         expect[list(bad.keys())] = False
         res = {"value": n_total * args.steps / el, "unit": "rounds/s", "ms_per_step": el / args.steps * 1e3,
@@ -841,10 +886,12 @@ def main_verify(args, world, rank, local):
     import torch.distributed as dist
     n_total = args.rounds or 10_000_000
     main = verify_leg(args, world, rank, local, args.scheme, n_total, args.steps, args.warmup, mode=args.mode,
-                      e2e=not args.no_e2e, rlc=not args.no_rlc, cpu_seconds=args.cpu_seconds, main=True)
+                      e2e=args.full and not args.no_e2e, rlc=args.full and not args.no_rlc,
+                      cpu_seconds=args.cpu_seconds if args.full else None, main=True)
     legs = {}
-    default_run = args.mode == "per-round" and args.scheme == "pedersen-bls-chained" and not args.no_legs
-    if default_run:
+    full_run = (args.full and args.mode == "per-round" and args.scheme == "pedersen-bls-chained"
+                and not args.no_legs)
+    if full_run:
         # configs[3]: the two unchained schemes at their stated size
         legs["configs3"] = {}
         for sch in ("pedersen-bls-unchained", "bls-unchained-on-g1"):
@@ -883,17 +930,14 @@ def main_verify(args, world, rank, local):
                                 if args.mode == "rlc" else f"configs[3]: {args.scheme} chain, per-round verify"),
                    "rounds_total": n_total, "rounds_per_gpu": main["rounds_per_gpu"], "seg_len": args.seg_len,
                    "scheme": args.scheme, "mode": args.mode, "parallelism": f"shard{world}"},
-        "stage_ms": main["stage_ms"],
         "verdict_mismatches": main["verdict_mismatches"],
         "corrupted_rounds_total": main["corrupted_rounds_total"],
         "chain_gen_s": main["chain_gen_s"],
-        "end_to_end": main.get("end_to_end"),
-        "rlc": main.get("rlc"),
-        "ingest": main.get("ingest"),
-        "small_batch": main.get("small_batch"),
-        "roofline": main.get("roofline"),
-        "cpu_baseline": main.get("cpu_baseline"),
     }
+    if args.full:
+        out.update({"stage_ms": main["stage_ms"], "end_to_end": main.get("end_to_end"), "rlc": main.get("rlc"),
+                    "ingest": main.get("ingest"), "small_batch": main.get("small_batch"),
+                    "roofline": main.get("roofline"), "cpu_baseline": main.get("cpu_baseline")})
     out["driver"] = driver_info(world)
     out.update(legs)
     print(json.dumps(out), flush=True)
@@ -917,7 +961,8 @@ def driver_info(world):
 
 
 def main_recover(args, world, rank, local):
-    res = recover_leg(args, world, rank, local, args.rounds or 100_000, args.steps, args.warmup, args.cpu_seconds)
+    res = recover_leg(args, world, rank, local, args.rounds or 100_000, args.steps, args.warmup, args.cpu_seconds,
+                      main=True)
     if rank == 0:
         res["vs_baseline"] = None
         print(json.dumps(res), flush=True)

@@ -24,7 +24,7 @@ def test_bench_two_ranks_share_one_gpu_over_gloo():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rounds", "40000", "--steps", "1",
-           "--warmup", "1", "--no-legs", "--no-e2e", "--no-cpu-baseline", "--no-ingest", "--no-small-batch"]
+           "--warmup", "1", "--full", "--no-legs", "--no-e2e", "--no-cpu-baseline", "--no-ingest", "--no-small-batch"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])

@@ -8,7 +8,7 @@
 # nothing else touches the GPU after a fault.  Output: gpurun_out/$TAG/.
 #   pytest     GPU suite (PYTEST_SEL: test files / -k expression; default tests -m gpu)
 #   smoke      __graft_entry__.smoke()
-#   bench      python bench.py $BENCH_ARGS  -> bench.json (default: every leg)
+#   bench      python bench.py --full $BENCH_ARGS  -> bench.json (default: every leg)
 #   prof       rocprofv3 --kernel-trace --stats of the headline command -> kernel_stats.csv
 #   traffic    FETCH_SIZE / WRITE_SIZE passes of tools/prof_verify.py -> traffic.json
 #              (TRAFFIC_ARGS: prof_verify options, default one 131072-round chunk)
@@ -33,11 +33,11 @@ run_step() {
     timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
     rc=$?; tail -1 $O/smoke.log; return $rc ;;
   bench)
-    timeout -k 10 900 python -u bench.py ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err
+    timeout -k 10 900 python -u bench.py --full ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err
     rc=$?; head -c 400 $O/bench.json; echo; return $rc ;;
   prof)
     timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof -o bench -- \
-      python3 bench.py --no-cpu-baseline --no-e2e --no-legs --steps 2 ${PROF_ARGS} > $O/prof.out 2>&1 || return $?
+      python3 bench.py --full --no-cpu-baseline --no-e2e --no-legs --steps 2 ${PROF_ARGS} > $O/prof.out 2>&1 || return $?
     python3 tools/rocpd_stats.py $(find $O/prof -name "*results.db" | head -1) > $O/kernel_stats.csv || true ;;
   traffic)
     # the third pass runs the engine lines kernel, whose 45,696 B/round of
@@ -59,7 +59,7 @@ run_step() {
       lib=${v%%@*}; kvs=$([ "$lib" != "$v" ] && echo "${v#*@}" | tr '@' ' ')
       name=$(basename $lib .so)$(for kv in $kvs; do echo -n "_${kv//=/_}"; done)
       ( for kv in $kvs; do export "$kv"; done
-        DRAND_GPU_LIB=$PWD/$lib timeout -k 10 600 python bench.py --no-cpu-baseline ${BENCH_ARGS} \
+        DRAND_GPU_LIB=$PWD/$lib timeout -k 10 600 python bench.py --full --no-cpu-baseline ${BENCH_ARGS} \
           > $O/ab/ab_$name.json 2> $O/ab/ab_$name.err ) || return $?
     done
     python3 tools/ab_summary.py $O/ab ;;
