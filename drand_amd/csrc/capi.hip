@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/drand_gpu.h"
+#include "copy_pool.h"
 #include "kernels.cuh"
 #include "pairing_engine.cuh"
 #include "lines_thread.cuh"
@@ -1450,78 +1451,7 @@ int stage_inputs_locked(dgpu_ctx* c, verify_args& a, hipStream_t s) {
 // hipMemcpyAsync copied the whole batch before the first kernel (VERDICT r05
 // item 4).
 
-// Host memcpy on a few pooled threads (pageable -> pinned runs at host
-// memory bandwidth only when several cores copy).
-class copy_pool {
- public:
-  explicit copy_pool(int threads) {
-    for (int i = 0; i < threads; ++i) th_.emplace_back([this] { work(); });
-  }
-  ~copy_pool() {
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      stop_ = true;
-    }
-    cv_.notify_all();
-    for (auto& t : th_) t.join();
-  }
-  // dst <- src (bytes), split across the pool; returns when every part is done
-  void copy(void* dst, const void* src, size_t bytes) {
-    constexpr size_t PART = 1 << 20;
-    const size_t parts = std::min<size_t>(th_.size(), (bytes + PART - 1) / PART);
-    if (parts <= 1) {
-      memcpy(dst, src, bytes);
-      return;
-    }
-    batch b;
-    b.left = parts;
-    const size_t per = (bytes / parts + 63) & ~(size_t)63;
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      for (size_t p = 0; p < parts; ++p) {
-        const size_t off = std::min(bytes, p * per), len = std::min(bytes - off, per);
-        q_.push_back(task{(uint8_t*)dst + off, (const uint8_t*)src + off, len, &b});
-      }
-    }
-    cv_.notify_all();
-    std::unique_lock<std::mutex> lk(b.mu);
-    b.cv.wait(lk, [&] { return b.left == 0; });
-  }
-
- private:
-  struct batch {
-    std::mutex mu;
-    std::condition_variable cv;
-    size_t left = 0;
-  };
-  struct task {
-    uint8_t* d;
-    const uint8_t* s;
-    size_t n;
-    batch* b;
-  };
-  void work() {
-    for (;;) {
-      task t;
-      {
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_.wait(lk, [&] { return stop_ || !q_.empty(); });
-        if (stop_ && q_.empty()) return;
-        t = q_.front();
-        q_.pop_front();
-      }
-      memcpy(t.d, t.s, t.n);
-      std::lock_guard<std::mutex> lk(t.b->mu);
-      if (--t.b->left == 0) t.b->cv.notify_all();
-    }
-  }
-  std::vector<std::thread> th_;
-  std::mutex mu_;
-  std::condition_variable cv_;
-  std::deque<task> q_;
-  bool stop_ = false;
-};
-
+// The pool of host threads that fills the slots: copy_pool.h (host-only).
 copy_pool& host_copy_pool() {
   static copy_pool pool(STAGE_COPY_THREADS);
   return pool;
@@ -1902,7 +1832,8 @@ int dgpu_open(int device, dgpu_ctx** out) {
   const char* tso = getenv("DGPU_TEST_STAGE_ONLY");
   if (tso && !strcmp(tso, "1")) c->test_stage_only = true;
   const char* tac = getenv("DGPU_TEST_ALLOC_CAP");
-  if (tac && atol(tac) >= 0) g_test_alloc_cap = (size_t)atol(tac);
+  // process-global: written at every dgpu_open of this build, so a context opened without the knob resets it
+  g_test_alloc_cap = tac && atol(tac) >= 0 ? (size_t)atol(tac) : 0;
   {  // the fast group-law paths' generic redo on every item (kernels.cuh DG_FORCE_EXC); written at every
      // dgpu_open of this build, so a context opened without the knob resets it
     const char* fev2 = getenv("DGPU_TEST_FORCE_EXC");
@@ -1930,6 +1861,7 @@ int dgpu_open(int device, dgpu_ctx** out) {
     dgpu_close(c);
     return set_err(DGPU_EDEVICE, "%s", msg.c_str());
   }
+  g_last_error.clear();  // a new context starts without an earlier context's message on this thread
   *out = c;
   return DGPU_OK;
 }

@@ -20,7 +20,8 @@
  *  - Plain pointers and sizes only; all host buffers are caller-owned and are
  *    not retained after a call returns (cgo-safe).
  *  - Return codes: DGPU_OK (0) or a negative DGPU_E* value; the message is in
- *    dgpu_last_error() (thread-local).
+ *    dgpu_last_error() (thread-local: the calling thread's last failure; a
+ *    successful dgpu_open clears it).
  *  - A context is bound to one GPU and serializes its own calls internally;
  *    any thread may call.  Calls on one context are also ordered on the
  *    device: each call's work starts after the previous call's, whatever

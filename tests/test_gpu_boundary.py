@@ -459,6 +459,7 @@ def test_host_records_staged_through_the_ring(n, scheme, gpu_ctx):
     from drand_amd.synth import corrupt, make_chain
     code = getattr(_lib, scheme)
     c = make_chain(73, n, code, seg_len=64)
+    pristine = {k: getattr(c, k).copy() for k in ("sigs", "sig_len", "prev", "prev_len")}
     bad = corrupt(c, 73, rate=1e-3)
     pk = np.frombuffer(c.pk, dtype=np.uint8).copy()
     lib, h = gpu_ctx.lib, gpu_ctx.handle
@@ -489,10 +490,16 @@ def test_host_records_staged_through_the_ring(n, scheme, gpu_ctx):
     expect = np.ones(n, dtype=bool)
     expect[list(bad.keys())] = False
     assert np.array_equal(got == 0, expect)
-    # the caller reuses its buffers: every signature moved to the next round
-    # (only an "other round's signature" corruption can turn valid again)
+    # the caller reuses its buffers: every signature moved to the next round.
+    # BLS signatures are deterministic and unique, so a record is valid if and
+    # only if its signature, sig_len, prev and prev_len are the uncorrupted
+    # chain's: the rounds behind an "other round's signature" corruption (the
+    # next round's signature there, now moved on to its own round)
     keep = c.sigs.copy()
     c.sigs[:] = np.roll(keep, 1, axis=0)
+    w = int(pristine["sig_len"][0])
+    valid = ((c.sigs[:, :w] == pristine["sigs"][:, :w]).all(axis=1) & (c.sig_len == pristine["sig_len"]) &
+             (c.prev == pristine["prev"]).all(axis=1) & (c.prev_len == pristine["prev_len"]))
     try:
         again = host_call()
         dev["sigs"].copy_(torch.from_numpy(c.sigs))
@@ -504,7 +511,8 @@ def test_host_records_staged_through_the_ring(n, scheme, gpu_ctx):
     finally:
         c.sigs[:] = keep
     assert dreason.cpu().numpy().tolist() == again.tolist()
-    assert (again != 0).sum() >= n - len(bad)
+    assert valid.any()
+    assert np.array_equal(again == 0, valid)
     if code == _lib.SCHEME_CHAINED:
         # a record longer than its stride, in the first and in the last slice:
         # the staging thread finds it and the call fails with DGPU_EINVAL; the
@@ -519,6 +527,158 @@ def test_host_records_staged_through_the_ring(n, scheme, gpu_ctx):
             finally:
                 c.prev_len[i] = old
         assert host_call().tolist() == got.tolist()
+
+
+@pytest.mark.parametrize("n,scheme", [(10913, "SCHEME_CHAINED"), (43332, "SCHEME_CHAINED"), (76135, "SCHEME_CHAINED"),
+                                      (10913, "SCHEME_UNCHAINED_G1")])
+def test_raw_messages_tail_bytes_reach_the_device(n, scheme, gpu_ctx):
+    """The last bytes of a staged array reach the device.  n messages of 97
+    bytes are 1,058,561 / 4,203,204 / 7,385,095 bytes, copied into one ring
+    slot by 2 / 5 / 8 pool threads: sizes at which a split of
+    round_up_64(floor(bytes / parts)) per thread left the last 1 / 4 / 7
+    bytes of the slot as the previous copy had them (copy_pool.h;
+    tests/test_copy_pool.py is the host check).  Those bytes are the end of
+    the last message: its verdict must follow them.  The signatures come from
+    dgpu_sign, which stages with plain hipMemcpyAsync and never uses the ring."""
+    from drand_amd import _lib
+    from drand_amd.synth import derive_secret
+    code = getattr(_lib, scheme)
+    lib, h = gpu_ctx.lib, gpu_ctx.handle
+    width = 48 if code == _lib.SCHEME_UNCHAINED_G1 else 96
+    stride = 97
+    msgs = np.random.default_rng(9700 + n).integers(0, 256, size=(n, stride), dtype=np.uint8)
+    msg_len = np.full(n, stride, dtype=np.uint32)
+    skb = np.frombuffer(derive_secret(97).to_bytes(32, "big"), dtype=np.uint8).copy()
+    pk = np.zeros(144 - width, dtype=np.uint8)
+    _lib.check(lib.dgpu_derive_pubkey(h, code, _lib.ptr(skb), _lib.ptr(pk), pk.size))
+    sigs = np.zeros((n, width), dtype=np.uint8)
+    sig_len = np.full(n, width, dtype=np.uint32)
+    _lib.check(lib.dgpu_sign(h, code, _lib.ptr(skb), n, _lib.ptr(msgs), stride, _lib.ptr(msg_len), _lib.ptr(sigs)))
+
+    def verify():
+        bits = np.zeros((n + 7) // 8, dtype=np.uint8)
+        reason = np.full(n, 0xEE, dtype=np.uint8)
+        _lib.check(lib.dgpu_verify_recovered(h, code, _lib.ptr(pk), pk.size, n, _lib.ptr(msgs), stride,
+                                             _lib.ptr(msg_len), _lib.ptr(sigs), width, _lib.ptr(sig_len),
+                                             _lib.MODE_PER_ROUND, 0, _lib.ptr(bits), _lib.ptr(reason)))
+        assert np.array_equal(np.unpackbits(bits, bitorder="little")[:n].astype(bool), reason == 0)
+        return reason
+
+    expect = np.zeros(n, dtype=np.uint8)
+    assert np.array_equal(verify(), expect)
+    # the last 8 bytes of the last message change, its signature stays
+    msgs[n - 1, -8:] ^= 0xFF
+    expect[n - 1] = _lib.REASON_PAIRING
+    assert np.array_equal(verify(), expect)
+    # ... and it is signed again
+    _lib.check(lib.dgpu_sign(h, code, _lib.ptr(skb), 1, _lib.ptr(msgs[n - 1:]), stride, _lib.ptr(msg_len[n - 1:]),
+                             _lib.ptr(sigs[n - 1:])))
+    expect[n - 1] = 0
+    assert np.array_equal(verify(), expect)
+
+
+def test_length_array_tail_reaches_the_device(gpu_ctx):
+    """1,048,641 rounds is the smallest batch whose 4-byte length arrays
+    (4,194,564 bytes, 5 pool threads) lost their tail under the split of
+    round_up_64(floor(bytes / parts)): the last sig_len word stayed what the
+    ring slot held before.  An on-G1 call is one slice, so sig_len is one ring
+    piece, and the stale word is known:
+
+      stage_slice copies rounds (n * 8 bytes, one 16 MiB piece), then sigs
+      (n * 96 = 100,669,536 bytes: six full pieces and one of 6,240 bytes),
+      then sig_len, and the pieces alternate between the two slots: sig_len
+      lands in the slot that last held the sixth sigs piece.  The 4 lost
+      bytes are slot offsets 4,194,560..63, i.e. flat sigs bytes
+      5 * 16 MiB + 4,194,560 = 88,080,640..43 = row 917,506, bytes 64..67: the
+      padding behind a 48-byte G1 signature in its 96-byte row, which no
+      kernel reads.
+
+    Two passes, each wrong in its last verdict if that word is lost, neither
+    with a length above its stride.  (a) The chain as generated (padding 0)
+    and a valid last record: a stale 0 would truncate it (reason 1 for 0).
+    (b) The last record truncated (sig_len = 0) and every row's padding filled
+    with the little-endian word 48: a stale 48 would make it valid (reason 0
+    for 1).  Reasons equal the device-resident entry point's on the same
+    records, and the construction."""
+    import torch
+    from drand_amd import _lib
+    from drand_amd.synth import corrupt, make_chain
+    n = 1048641
+    code = _lib.SCHEME_UNCHAINED_G1
+    lib, h = gpu_ctx.lib, gpu_ctx.handle
+    c = make_chain(1048641, n, code, seg_len=256)
+    bad = corrupt(c, 1048641, rate=1e-4)
+    assert n - 1 not in bad and c.sig_len[n - 1] == 48
+    assert c.sigs.shape[1] == 96 and not c.sigs[:, 48:].any()
+    pk = np.frombuffer(c.pk, dtype=np.uint8).copy()
+    dev = {k: torch.from_numpy(np.ascontiguousarray(getattr(c, k))).cuda()
+           for k in ("rounds", "sigs", "sig_len", "prev", "prev_len")}
+    dbits = torch.zeros((n + 7) // 8, dtype=torch.uint8, device="cuda")
+    dreason = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    expect = np.ones(n, dtype=bool)
+    expect[list(bad.keys())] = False
+
+    def check(last_reason):
+        bits = np.zeros((n + 7) // 8, dtype=np.uint8)
+        got = np.full(n, 0xEE, dtype=np.uint8)
+        _lib.check(lib.dgpu_verify_beacons(h, code, _lib.ptr(pk), pk.size, n, _lib.ptr(c.rounds), _lib.ptr(c.sigs),
+                                           c.sigs.shape[1], _lib.ptr(c.sig_len), _lib.ptr(c.prev), c.prev.shape[1],
+                                           _lib.ptr(c.prev_len), _lib.MODE_PER_ROUND, 0, _lib.ptr(bits),
+                                           _lib.ptr(got)))
+        dev["sigs"].copy_(torch.from_numpy(c.sigs))
+        dev["sig_len"].copy_(torch.from_numpy(c.sig_len))
+        _lib.check(lib.dgpu_verify_beacons_device(h, code, _lib.ptr(pk), pk.size, n, _lib.ptr(dev["rounds"]),
+                                                  _lib.ptr(dev["sigs"]), c.sigs.shape[1], _lib.ptr(dev["sig_len"]),
+                                                  _lib.ptr(dev["prev"]), c.prev.shape[1], _lib.ptr(dev["prev_len"]),
+                                                  _lib.MODE_PER_ROUND, 0, _lib.ptr(dbits), _lib.ptr(dreason), None))
+        torch.cuda.synchronize()
+        assert got[n - 1] == last_reason
+        assert np.array_equal(dreason.cpu().numpy(), got)
+        assert np.array_equal(np.unpackbits(bits, bitorder="little")[:n].astype(bool), got == 0)
+        assert np.array_equal(got == 0, expect)
+
+    check(_lib.REASON_OK)
+    c.sigs[:, 48:] = np.tile(np.frombuffer(np.uint32(48).astype("<u4").tobytes(), dtype=np.uint8), 12)
+    c.sig_len[n - 1] = 0
+    expect[n - 1] = False
+    check(_lib.REASON_DECODE)
+
+
+def test_alloc_cap_is_reset_by_the_next_open():
+    """The A/B build's DGPU_TEST_ALLOC_CAP is process-global and written at
+    every dgpu_open of that build: a context opened without the knob clears
+    the cap a closed context left, so a test's result does not depend on the
+    tests before it.  The cap is a host-side check in front of hipMalloc:
+    nothing on the device fails."""
+    from drand_amd import _lib
+    from drand_amd.synth import make_chain
+    n = 64
+    c = make_chain(74, n, _lib.SCHEME_CHAINED, seg_len=64)
+    pk = np.frombuffer(c.pk, dtype=np.uint8).copy()
+
+    def verify(ctx):
+        bits = np.zeros((n + 7) // 8, dtype=np.uint8)
+        reason = np.full(n, 0xEE, dtype=np.uint8)
+        rc = ctx.lib.dgpu_verify_beacons(ctx.handle, _lib.SCHEME_CHAINED, _lib.ptr(pk), pk.size, n, _lib.ptr(c.rounds),
+                                         _lib.ptr(c.sigs), c.sigs.shape[1], _lib.ptr(c.sig_len), _lib.ptr(c.prev),
+                                         c.prev.shape[1], _lib.ptr(c.prev_len), _lib.MODE_PER_ROUND, 0, _lib.ptr(bits),
+                                         _lib.ptr(reason))
+        return rc, reason
+
+    # 64 KiB: the context's constants fit (dgpu_open succeeds), the engine's buffers for 64 rounds do not
+    ctx = open_ctx({"DGPU_TEST_ALLOC_CAP": "65536"})
+    try:
+        rc, _ = verify(ctx)
+        assert rc == _lib.DGPU_ENOMEM and b"test cap 65536" in ctx.lib.dgpu_last_error()
+    finally:
+        ctx.close()
+    ctx = open_ctx({"DGPU_DEC_OVERLAP": "0"})  # another A/B knob: the same build, no cap
+    try:
+        rc, reason = verify(ctx)
+        assert rc == _lib.DGPU_OK and ctx.lib.dgpu_last_error() == b""
+        assert not reason.any()
+    finally:
+        ctx.close()
 
 
 def test_empty_batches_are_no_ops(gpu_ctx):

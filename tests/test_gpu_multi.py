@@ -1,5 +1,5 @@
 """The multi-GPU product entry points (dgpu_verify_multi, dgpu_recover_multi;
-include/drand_gpu.h) with D = 2 and 3 contexts on one GPU
+include/drand_gpu.h) with D = 2, 3 and 8 contexts on one GPU
 (DGPU_MULTI_ALLOW_SAME_DEVICE=1: the all-gathers become in-library device
 copies, every other line is the production D >= 2 path -- per-device RLC
 seeds, the root all-gather + sum + single check on the first context, the
@@ -23,9 +23,18 @@ def _sch(name="pedersen-bls-chained"):
 def chain5003():
     from drand_amd import _lib
     from drand_amd.chain import Verifier
-    from drand_amd.synth import corrupt, make_chain
+    from drand_amd.synth import CORRUPT_Y_SIGN, corrupt, make_chain
     c = make_chain(61, 5003, _lib.SCHEME_CHAINED, seg_len=64)
     bad = corrupt(c, 61, rate=2e-3)
+    # corrupt(seed 61) leaves rounds 0..931 clean: one more bad round (-sigma)
+    # in the first shard, so that at every D a bad round lies in the first
+    # and in the last shard (D = 8: rounds 0..631 and 4424..5002)
+    c.sigs[5, 0] ^= 0x20
+    bad[5] = CORRUPT_Y_SIGN
+    for ndev in (2, 3, 8):
+        for k in (0, ndev - 1):
+            lo, hi = _lib.shard_range(len(c), ndev, k)
+            assert any(lo <= i < hi for i in bad), (ndev, k)
     beacons = [c.beacon(i) for i in range(len(c))]
     single = Verifier(_sch()).verify_reasons(beacons, c.pk)
     expect = np.ones(len(c), dtype=bool)
@@ -34,7 +43,7 @@ def chain5003():
     return c, bad, beacons, single
 
 
-@pytest.mark.parametrize("ndev", [2, 3])
+@pytest.mark.parametrize("ndev", [2, 3, 8])
 def test_verify_multi_same_device_equals_single(ndev, chain5003, monkeypatch):
     from drand_amd import _lib
     from drand_amd.multi import MultiVerifier
@@ -51,6 +60,7 @@ def test_verify_multi_same_device_equals_single(ndev, chain5003, monkeypatch):
             clean = [b for i, b in enumerate(beacons[:1500]) if i not in bad]
             assert not mv.verify_reasons(clean, c.pk, mode).any()
             # an empty last shard: 8 (D - 1) rounds -> shards of 8, the last one empty
+            # (D = 8: ceil(56 / 8) = 7 rounds rounded up to 8 per shard, seven shards)
             n_e = 8 * (ndev - 1)
             assert _lib.shard_range(n_e, ndev, ndev - 1) == (n_e, n_e)
             assert mv.verify_reasons(beacons[:n_e], c.pk, mode).tolist() == single[:n_e].tolist()
@@ -85,7 +95,7 @@ def test_verify_multi_same_device_unchained_and_on_g1(monkeypatch):
             mv.close()
 
 
-@pytest.mark.parametrize("ndev", [2, 3])
+@pytest.mark.parametrize("ndev", [2, 3, 8])
 def test_recover_multi_same_device_equals_single(ndev, monkeypatch):
     from conftest import load_golden
     from drand_amd.multi import MultiThresholdGroup
@@ -93,7 +103,8 @@ def test_recover_multi_same_device_equals_single(ndev, monkeypatch):
     monkeypatch.setenv("DGPU_MULTI_ALLOW_SAME_DEVICE", "1")
     g = load_golden("recover_t17_n32.json")
     commits = [bytes.fromhex(x) for x in g["commits"]]
-    msgs = [bytes.fromhex(c["msg"]) for c in g["cases"]] * 5   # 30 rounds: D=2 shards 16 + 14, D=3 16 + 14 + empty
+    # 30 rounds: D=2 shards 16 + 14, D=3 16 + 14 + empty, D=8 8 + 8 + 8 + 6 + four empty
+    msgs = [bytes.fromhex(c["msg"]) for c in g["cases"]] * 5
     parts = [[bytes.fromhex(p) for p in c["partials"]] for c in g["cases"]] * 5
     single = ThresholdGroup(commits, g["n"]).recover_batch(msgs, parts)
     mg = MultiThresholdGroup(commits, g["n"], [0] * ndev)
