@@ -65,8 +65,11 @@ SYMBOLS = [
     ("dgpu_derive_pubkey", _c.c_int, [_P, _c.c_int, _P, _P, _c.c_size_t]),
     ("dgpu_make_chain", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t, _c.c_size_t, _P, _P, _P, _P]),
     ("dgpu_set_group", _c.c_int, [_P, _c.c_int, _c.c_int, _P]),
+    ("dgpu_set_group_scheme", _c.c_int, [_P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_size_t]),
     ("dgpu_recover_batch_device", _c.c_int, [_P, _c.c_size_t, _P, _c.c_size_t, _P, _c.c_size_t, _P, _P, _P, _P, _P]),
     ("dgpu_make_partials", _c.c_int, [_P, _c.c_size_t, _P, _c.c_size_t, _P, _P, _P, _c.c_size_t, _P]),
+    ("dgpu_make_partials_scheme", _c.c_int, [_P, _c.c_int, _c.c_size_t, _P, _c.c_size_t, _P, _P, _P, _c.c_size_t,
+                                             _P]),
     ("dgpu_recover_batch", _c.c_int, [_P, _c.c_size_t, _P, _c.c_size_t, _P, _c.c_size_t, _P, _P, _P, _P]),
     ("dgpu_shard_range", None, [_c.c_size_t, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t), _c.POINTER(_c.c_size_t)]),
     ("dgpu_verify_beacons", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t, _c.c_size_t, _P, _P, _c.c_size_t, _P, _P,
@@ -90,6 +93,7 @@ SYMBOLS = [
     ("dgpu_verify_multi", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t, _c.c_size_t, _P, _P, _c.c_size_t, _P, _P,
                                      _c.c_size_t, _P, _c.c_int, _c.c_uint64, _P, _P]),
     ("dgpu_multi_set_group", _c.c_int, [_P, _c.c_int, _c.c_int, _P]),
+    ("dgpu_multi_set_group_scheme", _c.c_int, [_P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_size_t]),
     ("dgpu_recover_multi", _c.c_int, [_P, _c.c_size_t, _P, _c.c_size_t, _P, _c.c_size_t, _P, _P, _P, _P]),
 ]
 

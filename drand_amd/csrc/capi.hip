@@ -29,6 +29,7 @@
 #include "recover.cuh"
 #include "g1sig.cuh"
 #include "rlc_msm.cuh"
+#include "recover_g1.cuh"
 
 using namespace dgpu;
 
@@ -235,6 +236,14 @@ struct dgpu_ctx {
   bool decode_subgroup = false;  // DGPU_SUBGROUP=decode: G2 membership in the decoder, not the lines kernel (A/B)
   // threshold group (dgpu_set_group): commitments, PubPoly.Eval table; recovery scratch
   int grp_t = 0, grp_n = 0;
+  // the installed group's scheme (dgpu_set_group_scheme); a G1-signature
+  // group (G2 commitments) owns C_0 as a decoded G2 key with its fixed-Q line
+  // table, outside the caller's key cache, and the 96-byte round slots its
+  // recovered signatures are packed from
+  int grp_scheme = DGPU_SCHEME_CHAINED;
+  bool grp_g1 = false;
+  key_entry grp_key;
+  DevBuf grp_stage, rec_slots;
   DevBuf grp_commits, grp_table, rec_msgs, rec_parts, rec_plen, rec_hidx, rec_pk, rec_idx, rec_lam, rec_out, rec_ok,
       rec_pts, rec_vpk, rec_sel, rec_part, rec_st;
   // batched recovery check: the group's window table of the share keys, round
@@ -485,7 +494,7 @@ int get_key_locked(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t len, key_e
 int eng_pairing_locked(dgpu_ctx* c, const uint32_t* consts, size_t n, const uint32_t* h, const uint32_t* sg,
                        uint8_t* st, hipStream_t s, size_t h_stride = 0, const uint32_t* h_idx = nullptr,
                        const uint32_t* pk_items = nullptr, const uint32_t* fixed_table = nullptr,
-                       const lane_bufs* L = nullptr, bool sig_subgroup = false);
+                       const lane_bufs* L = nullptr, bool sig_subgroup = false, const uint32_t* g1form_keys = nullptr);
 
 // ---------------------------------------------------------------- RLC
 // The segment trees of one RLC batch (level l: P[l], S[l], sz[l] nodes).
@@ -995,7 +1004,8 @@ int eng_fe_kb_locked(dgpu_ctx* c, const uint32_t* consts, size_t cnt, size_t cap
 // final exponentiation.  Decode verdicts in `st` stay final.
 int eng_pairing_locked(dgpu_ctx* c, const uint32_t* consts, size_t n, const uint32_t* h, const uint32_t* sg,
                        uint8_t* st, hipStream_t s, size_t h_stride, const uint32_t* h_idx, const uint32_t* pk_items,
-                       const uint32_t* fixed_table, const lane_bufs* L, bool sig_subgroup) {
+                       const uint32_t* fixed_table, const lane_bufs* L, bool sig_subgroup,
+                       const uint32_t* g1form_keys) {
   if (!h_stride) h_stride = n;
   DevBuf* b_lines = L ? L->lines : &c->eng_lines;
   DevBuf* b_f = L ? L->f : &c->eng_f;
@@ -1052,7 +1062,11 @@ int eng_pairing_locked(dgpu_ctx* c, const uint32_t* consts, size_t n, const uint
                          fixed_table, f, n1);
       HIP_TRY(hipGetLastError());
     } else {
-      if (fixed_table) {  // on-G1: h and sg are affine G1 points, the G2 arguments fixed
+      if (g1form_keys) {  // G1-signature recovery: h and sg affine G1 points, pair 0's G2 point per item
+        mark(c, s, "eng_lines");
+        hipLaunchKernelGGL(k_lines_thr_g1, dim3(grid_for(2 * cnt, 256)), dim3(256), 0, s, n, r0, cnt, h, h_stride, h_idx,
+                           sg, g1form_keys, lines);
+      } else if (fixed_table) {  // on-G1: h and sg are affine G1 points, the G2 arguments fixed
         mark(c, s, "eng_lines_fixed");
         hipLaunchKernelGGL(k_eng_lines_fixed, dim3(blocks, ENG_LINE_STEPS), dim3(ENG_BLOCK), 0, s, n, r0, cnt, h, sg,
                            fixed_table, lines);
@@ -1890,7 +1904,10 @@ void dgpu_close(dgpu_ctx* c) {
     k.consts.release();
     k.table.release();
   }
-  for (DevBuf* b : {&c->grp_commits, &c->grp_table, &c->rec_msgs, &c->rec_parts, &c->rec_plen, &c->rec_hidx,
+  c->grp_key.consts.release();
+  c->grp_key.table.release();
+  for (DevBuf* b : {&c->grp_stage, &c->rec_slots,
+                    &c->grp_commits, &c->grp_table, &c->rec_msgs, &c->rec_parts, &c->rec_plen, &c->rec_hidx,
                     &c->rec_pk, &c->rec_idx, &c->rec_lam, &c->rec_out, &c->rec_ok, &c->rec_pts, &c->rec_vpk,
                     &c->rec_st, &c->rec_sel, &c->rec_part, &c->grp_wtab, &c->rec_cls, &c->rec_x_list,
                     &c->rec_x_msgs, &c->rec_x_parts, &c->rec_x_plen, &c->rec_x_out, &c->rec_x_ok, &c->rec_x_st,
@@ -2473,10 +2490,105 @@ int dgpu_set_group(dgpu_ctx* c, int t, int n, const uint8_t* commits48) {
   HIP_TRY(hipStreamSynchronize(s));
   c->grp_t = t;
   c->grp_n = n;
+  c->grp_scheme = DGPU_SCHEME_CHAINED;
+  c->grp_g1 = false;
   return DGPU_OK;
 }
 
+// A G1-signature group: t compressed G2 commitments.  Everything is decoded
+// and checked in staging buffers first, so a rejected call leaves the
+// installed group (of either kind) as it was.
+static int set_group_g1_locked(dgpu_ctx* c, int scheme, int t, int n, const uint8_t* commits96) {
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  stream_order ord(c, s);
+  // the group's tables may still be read by an earlier asynchronous recovery
+  HIP_TRY(hipEventSynchronize(c->done));
+  int rc;
+  const size_t cw = (size_t)t * G2A_WORDS * 4;
+  if ((rc = c->misc.ensure(t * 96 + t * 4)) || (rc = c->grp_stage.ensure(cw))) return rc;
+  uint8_t* d_in = (uint8_t*)c->misc.p;
+  int* d_rc = (int*)(d_in + t * 96);
+  HIP_TRY(hipMemcpyAsync(d_in, commits96, (size_t)t * 96, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_decode_commits_g2, dim3(grid_for(t, 64)), dim3(64), 0, s, t, d_in, (uint32_t*)c->grp_stage.p,
+                     d_rc);
+  HIP_TRY(hipGetLastError());
+  std::vector<int> hrc(t);
+  HIP_TRY(hipMemcpyAsync(hrc.data(), d_rc, t * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int j = 0; j < t; ++j)
+    if (hrc[j] != DEC_OK) return set_err(DGPU_EINVAL, "group commitment %d rejected (decode code %d)", j, hrc[j]);
+  // VerifyRecovered's key C_0: decoded with its fixed-Q line table as
+  // dgpu_set_pubkey does, into the group's own entry (the key cache keeps its 8)
+  key_entry fresh;
+  if ((rc = decode_g2_key_locked(c, &fresh, commits96))) {
+    fresh.consts.release();
+    fresh.table.release();
+    return rc;
+  }
+  c->grp_t = 0;
+  c->grp_key.consts.release();
+  c->grp_key.table.release();
+  c->grp_key.consts = fresh.consts;
+  c->grp_key.table = fresh.table;
+  c->grp_key.used = true;
+  c->grp_key.g2key = true;
+  if ((rc = c->grp_commits.ensure(cw)) || (rc = c->grp_table.ensure((size_t)n * G2A_WORDS * 4)) ||
+      (rc = c->grp_wtab.ensure((size_t)n * 8 * G2A_WORDS * 4)))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(c->grp_commits.p, c->grp_stage.p, cw, hipMemcpyDeviceToDevice, s));
+  hipLaunchKernelGGL(k_pubpoly_table_g2, dim3(grid_for(n, 64)), dim3(64), 0, s, n, t,
+                     (const uint32_t*)c->grp_commits.p, (uint32_t*)c->grp_table.p);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_pubpoly_wtable_g2, dim3(grid_for(8 * (size_t)n, 64)), dim3(64), 0, s, n,
+                     (const uint32_t*)c->grp_table.p, (uint32_t*)c->grp_wtab.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s));
+  c->grp_t = t;
+  c->grp_n = n;
+  c->grp_scheme = scheme;
+  c->grp_g1 = true;
+  return DGPU_OK;
+}
+
+int dgpu_set_group_scheme(dgpu_ctx* c, int scheme, int t, int n, const uint8_t* commits, size_t commit_len) {
+  if (!c || !commits) return set_err(DGPU_EINVAL, "null argument");
+  if (!scheme_known(scheme)) return set_err(DGPU_EINVAL, "bad scheme %d", scheme);
+  const size_t want = sig_on_g1(scheme) ? 96 : 48;
+  if (commit_len != want)
+    return set_err(DGPU_EINVAL, "commitments of scheme %d are %zu bytes (compressed %s), got %zu", scheme, want,
+                   sig_on_g1(scheme) ? "G2" : "G1", commit_len);
+  if (!sig_on_g1(scheme)) return dgpu_set_group(c, t, n, commits);
+  if (t < 1 || t > RECOVER_MAX_T) return set_err(DGPU_EINVAL, "threshold t=%d outside [1, %d]", t, RECOVER_MAX_T);
+  if (n < t || n > 65536) return set_err(DGPU_EINVAL, "group size n=%d invalid for t=%d", n, t);
+  std::lock_guard<std::mutex> lk(c->mu);
+  return set_group_g1_locked(c, scheme, t, n, commits);
+}
+
 }  // extern "C"
+
+// The G1 recovery MSM's launches (recover_g1.cuh): shared affine window tables
+// [1..8] sig_j, then `slices` threads per round of mixed-addition windows.
+static int recover_msm_g1_locked(dgpu_ctx* c, size_t n_rounds, int t, const uint8_t* d_ok, const uint32_t* sel,
+                                 const uint64_t* dig, const uint32_t* sg, size_t items, uint32_t* part, int slices,
+                                 hipStream_t s) {
+  const size_t ne = n_rounds * (size_t)t * 8;
+  int rc;
+  if ((rc = c->rec_tab.ensure(ne * 2 * FP_WORDS * 4)) || (rc = c->rec_tabz.ensure(ne * FP_WORDS * 4)) ||
+      (rc = c->rec_tabpre.ensure(ne * FP_WORDS * 4)))
+    return rc;
+  uint32_t* tab = (uint32_t*)c->rec_tab.p;
+  hipLaunchKernelGGL(k_recover_tables_g1, dim3(grid_for(n_rounds * (size_t)t, 256)), dim3(256), 0, s, n_rounds, t, d_ok,
+                     sel, sg, items, tab, (uint32_t*)c->rec_tabz.p);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_g1_batch_affine, dim3(grid_for((ne + 15) / 16, 256)), dim3(256), 0, s, ne, tab,
+                     (const uint32_t*)c->rec_tabz.p, (uint32_t*)c->rec_tabpre.p);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_recover_msm_g1, dim3(grid_for((size_t)slices * n_rounds, 256)), dim3(256), 0, s, n_rounds, t,
+                     d_ok, dig, (const uint32_t*)tab, part, slices);
+  HIP_TRY(hipGetLastError());
+  return DGPU_OK;
+}
 
 // Exact per-partial recovery over device buffers: VerifyPartial of every
 // partial, selection, Lagrange + MSM, VerifyRecovered -- the reference's
@@ -2491,7 +2603,9 @@ static int recover_exact_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_m
   const uint32_t* consts = (const uint32_t*)c->eng_consts.p;
   int rc;
   if ((rc = c->rec_hidx.ensure(items * 4))) return rc;
-  if ((rc = c->rec_pk.ensure(items * 2 * FP_LIMBS * 4))) return rc;
+  const bool g1 = c->grp_g1;  // G1 signatures: per-item G2 share keys (recover_g1.cuh)
+  const int g1dst = c->grp_scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0;
+  if ((rc = c->rec_pk.ensure(items * (g1 ? (size_t)G2A_WORDS : 2 * FP_LIMBS) * 4))) return rc;
   if ((rc = c->rec_idx.ensure(items * 4))) return rc;
   if ((rc = c->rec_lam.ensure(n_rounds * RECOVER_MAX_T * RECOVER_SLOTS * 8))) return rc;
   if ((rc = c->rec_pts.ensure(n_rounds * G2A_WORDS * 4))) return rc;
@@ -2505,17 +2619,27 @@ static int recover_exact_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_m
   uint8_t* st = (uint8_t*)c->status.p;
   uint32_t* hidx = (uint32_t*)c->rec_hidx.p;
   mark(c, s, "recover_hash");
-  hipLaunchKernelGGL(k_hash_to_g2_msgs_pts, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds, d_msgs, h);
+  if (g1)
+    hipLaunchKernelGGL(k_hash_to_g1_msgs_pts, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds, d_msgs, g1dst, h);
+  else
+    hipLaunchKernelGGL(k_hash_to_g2_msgs_pts, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds, d_msgs, h);
   HIP_TRY(hipGetLastError());
   mark(c, s, "recover_decode");
   hipLaunchKernelGGL(k_round_of_item, dim3(grid_for(items, 256)), dim3(256), 0, s, items, m, hidx);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_decode_partials, dim3(grid_for(items, 256)), dim3(256), 0, s, items, d_parts, stride, d_plen,
-                     c->grp_n, c->grp_t, (const uint32_t*)c->grp_table.p, (const uint32_t*)c->grp_commits.p, sg,
-                     (uint32_t*)c->rec_pk.p, (uint32_t*)c->rec_idx.p, st);
+  if (g1)
+    hipLaunchKernelGGL(k_decode_partials_g1, dim3(grid_for(items, 256)), dim3(256), 0, s, items, d_parts, stride,
+                       d_plen, c->grp_n, c->grp_t, (const uint32_t*)c->grp_table.p, (const uint32_t*)c->grp_commits.p,
+                       sg, (uint32_t*)c->rec_pk.p, (uint32_t*)c->rec_idx.p, st);
+  else
+    hipLaunchKernelGGL(k_decode_partials, dim3(grid_for(items, 256)), dim3(256), 0, s, items, d_parts, stride, d_plen,
+                       c->grp_n, c->grp_t, (const uint32_t*)c->grp_table.p, (const uint32_t*)c->grp_commits.p, sg,
+                       (uint32_t*)c->rec_pk.p, (uint32_t*)c->rec_idx.p, st);
   HIP_TRY(hipGetLastError());
-  // VerifyPartial of every partial: e(Eval(i), H(msg)) e(-g1, sig) == 1 on the engine
-  if ((rc = eng_pairing_locked(c, consts, items, h, sg, st, s, n_rounds, hidx, (const uint32_t*)c->rec_pk.p)))
+  // VerifyPartial of every partial on the engine: e(Eval(i), H(msg)) e(-g1, sig) == 1,
+  // G1 signatures: e(H(msg), Eval(i)) e(-sig, g2) == 1
+  if ((rc = eng_pairing_locked(c, consts, items, h, sg, st, s, n_rounds, hidx, g1 ? nullptr : (const uint32_t*)c->rec_pk.p,
+                               nullptr, nullptr, false, g1 ? (const uint32_t*)c->rec_pk.p : nullptr)))
     return rc;
   uint32_t* rpts = (uint32_t*)c->rec_pts.p;
   uint32_t* rpk = (uint32_t*)c->rec_vpk.p;
@@ -2538,6 +2662,24 @@ static int recover_exact_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_m
                      (const uint8_t*)d_ok, (const uint32_t*)xs, dig, (uint64_t)0);
   HIP_TRY(hipGetLastError());
   mark(c, s, "recover_msm");
+  if (g1) {
+    // (k_recover_select's per-round copy of C_0 in rec_vpk is not used on this
+    // side: VerifyRecovered takes the group's fixed-Q line table)
+    if ((rc = recover_msm_g1_locked(c, n_rounds, t, d_ok, sel, dig, sg, items, part, 4, s))) return rc;
+    hipLaunchKernelGGL(k_recover_finish_g1, dim3(grid_for(n_rounds, 64)), dim3(64), 0, s, n_rounds,
+                       (const uint8_t*)d_ok, (const uint32_t*)part, d_out, rpts, rst, 4);
+    HIP_TRY(hipGetLastError());
+    // VerifyRecovered: e(H(msg), C_0) e(-sig, g2) == 1 over C_0's fixed-Q line table
+    if ((rc = eng_pairing_locked(c, (const uint32_t*)c->grp_key.consts.p, n_rounds, h, rpts, rst, s, 0, nullptr, nullptr,
+                                 (const uint32_t*)c->grp_key.table.p)))
+      return rc;
+    mark(c, s, "recover_verdict");
+    hipLaunchKernelGGL(k_recover_verdict, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds, rst, d_out, d_ok);
+    HIP_TRY(hipGetLastError());
+    if (d_status) HIP_TRY(hipMemcpyAsync(d_status, st, items, hipMemcpyDeviceToDevice, s));
+    mark(c, s);
+    return DGPU_OK;
+  }
 #if defined(DG_RECOVER_MSM_BITS)
   hipLaunchKernelGGL(k_recover_msm, dim3(grid_for(4 * n_rounds, 256)), dim3(256), 0, s, n_rounds, t,
                      (const uint8_t*)d_ok, (const uint32_t*)sel, (const uint64_t*)dig, (const uint32_t*)sg, items, part);
@@ -2567,9 +2709,9 @@ static int recover_exact_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_m
 // Recovery over device buffers (the body of every recover entry point):
 // the batched check (recover.cuh) for every round it decides, the exact
 // per-partial path for the rest (compacted, then scattered back).
-static int recover_device_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_msgs, size_t m,
-                                 const uint8_t* d_parts, size_t stride, const uint32_t* d_plen, uint8_t* d_out,
-                                 uint8_t* d_ok, uint8_t* d_status, hipStream_t s) {
+static int recover_slots_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_msgs, size_t m,
+                                const uint8_t* d_parts, size_t stride, const uint32_t* d_plen, uint8_t* d_out,
+                                uint8_t* d_ok, uint8_t* d_status, hipStream_t s) {
   if (!c->grp_t) return set_err(DGPU_ENOKEY, "no threshold group installed (dgpu_set_group)");
   c->n_ev = 0;
   c->ev_overflow = false;
@@ -2581,9 +2723,13 @@ static int recover_device_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_
   const uint32_t* consts = (const uint32_t*)c->eng_consts.p;
   const int t = c->grp_t;
   int rc;
-  if ((rc = c->rec_hidx.ensure(items * 4)) || (rc = c->rec_pk.ensure(items * 2 * FP_LIMBS * 4)) ||
+  const bool g1 = c->grp_g1;  // G1 signatures: the check's combination of share keys is a G2 point per round
+  const int g1dst = c->grp_scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0;
+  if ((rc = c->rec_hidx.ensure(items * 4)) ||
+      (rc = c->rec_pk.ensure(items * (g1 ? (size_t)G2A_WORDS : 2 * FP_LIMBS) * 4)) ||
       (rc = c->rec_idx.ensure(items * 4)) || (rc = c->rec_lam.ensure(n_rounds * RECOVER_MAX_T * RECOVER_SLOTS * 8)) ||
-      (rc = c->rec_pts.ensure(n_rounds * G2A_WORDS * 4)) || (rc = c->rec_vpk.ensure(n_rounds * 2 * FP_LIMBS * 4)) ||
+      (rc = c->rec_pts.ensure(n_rounds * G2A_WORDS * 4)) ||
+      (rc = c->rec_vpk.ensure(n_rounds * (g1 ? (size_t)G2A_WORDS : 2 * FP_LIMBS) * 4)) ||
       (rc = c->rec_st.ensure(n_rounds)) || (rc = c->rec_cls.ensure(n_rounds)) ||
       (rc = c->h_pts.ensure(n_rounds * G2A_WORDS * 4)) || (rc = c->sig_pts.ensure(items * G2A_WORDS * 4)) ||
       (rc = c->status.ensure(items)) || (rc = c->rec_sel.ensure(n_rounds * RECOVER_MAX_T * 2 * 4)) ||
@@ -2605,12 +2751,20 @@ static int recover_device_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_
   uint64_t seed = ((uint64_t)rd() << 32) ^ rd();
   if (!seed) seed = 1;
   mark(c, s, "recover_hash");
-  hipLaunchKernelGGL(k_hash_to_g2_msgs_pts, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds, d_msgs, h);
+  if (g1)
+    hipLaunchKernelGGL(k_hash_to_g1_msgs_pts, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds, d_msgs, g1dst, h);
+  else
+    hipLaunchKernelGGL(k_hash_to_g2_msgs_pts, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds, d_msgs, h);
   HIP_TRY(hipGetLastError());
   mark(c, s, "recover_decode");
-  hipLaunchKernelGGL(k_decode_partials, dim3(grid_for(items, 256)), dim3(256), 0, s, items, d_parts, stride, d_plen,
-                     c->grp_n, c->grp_t, (const uint32_t*)c->grp_table.p, (const uint32_t*)c->grp_commits.p, sg,
-                     (uint32_t*)c->rec_pk.p, (uint32_t*)c->rec_idx.p, st);
+  if (g1)
+    hipLaunchKernelGGL(k_decode_partials_g1, dim3(grid_for(items, 256)), dim3(256), 0, s, items, d_parts, stride,
+                       d_plen, c->grp_n, c->grp_t, (const uint32_t*)c->grp_table.p, (const uint32_t*)c->grp_commits.p,
+                       sg, (uint32_t*)c->rec_pk.p, (uint32_t*)c->rec_idx.p, st);
+  else
+    hipLaunchKernelGGL(k_decode_partials, dim3(grid_for(items, 256)), dim3(256), 0, s, items, d_parts, stride, d_plen,
+                       c->grp_n, c->grp_t, (const uint32_t*)c->grp_table.p, (const uint32_t*)c->grp_commits.p, sg,
+                       (uint32_t*)c->rec_pk.p, (uint32_t*)c->rec_idx.p, st);
   HIP_TRY(hipGetLastError());
   mark(c, s, "recover_select");
   hipLaunchKernelGGL(k_recover_cand, dim3(grid_for(n_rounds, 64)), dim3(64), 0, s, n_rounds, m, t, d_status ? 1 : 0,
@@ -2621,7 +2775,9 @@ static int recover_device_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_
                      (const uint8_t*)d_ok, (const uint32_t*)xs, dig, seed);
   HIP_TRY(hipGetLastError());
   mark(c, s, "recover_msm");
-  {
+  if (g1) {
+    if ((rc = recover_msm_g1_locked(c, n_rounds, t, d_ok, sel, dig, sg, items, part, 5, s))) return rc;
+  } else {
     // shared affine window tables [1..8] sig_j, then 5 slices of mixed-addition windows
     const size_t ne = n_rounds * (size_t)t * 8;
     if ((rc = c->rec_tab.ensure(ne * G2A_WORDS * 4)) || (rc = c->rec_tabz.ensure(ne * 2 * FP_WORDS * 4)) ||
@@ -2648,16 +2804,29 @@ static int recover_device_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_
     }
     HIP_TRY(hipGetLastError());
   }
-  hipLaunchKernelGGL(k_recover_finish, dim3(grid_for(n_rounds, 64)), dim3(64), 0, s, n_rounds, (const uint8_t*)d_ok,
-                     (const uint32_t*)part, d_out, rpts, rst, 5);
+  if (g1)
+    hipLaunchKernelGGL(k_recover_finish_g1, dim3(grid_for(n_rounds, 64)), dim3(64), 0, s, n_rounds,
+                       (const uint8_t*)d_ok, (const uint32_t*)part, d_out, rpts, rst, 5);
+  else
+    hipLaunchKernelGGL(k_recover_finish, dim3(grid_for(n_rounds, 64)), dim3(64), 0, s, n_rounds, (const uint8_t*)d_ok,
+                       (const uint32_t*)part, d_out, rpts, rst, 5);
   HIP_TRY(hipGetLastError());
-  mark(c, s, "recover_rlc_g1");
-  hipLaunchKernelGGL(k_recover_rlc_g1, dim3(grid_for(n_rounds, 64)), dim3(64), 0, s, n_rounds, t, c->grp_n,
-                     (const uint32_t*)sel, (const uint32_t*)c->rec_idx.p, (const uint64_t*)dig,
-                     (const uint32_t*)c->grp_wtab.p, (const uint32_t*)c->grp_commits.p, cls, d_ok, rpk, rst);
+  if (g1) {
+    mark(c, s, "recover_rlc_g2");
+    hipLaunchKernelGGL(k_recover_rlc_g2, dim3(grid_for(n_rounds, 64)), dim3(64), 0, s, n_rounds, t, c->grp_n,
+                       (const uint32_t*)sel, (const uint32_t*)c->rec_idx.p, (const uint64_t*)dig,
+                       (const uint32_t*)c->grp_wtab.p, (const uint32_t*)c->grp_commits.p, cls, d_ok, rpk, rst);
+  } else {
+    mark(c, s, "recover_rlc_g1");
+    hipLaunchKernelGGL(k_recover_rlc_g1, dim3(grid_for(n_rounds, 64)), dim3(64), 0, s, n_rounds, t, c->grp_n,
+                       (const uint32_t*)sel, (const uint32_t*)c->rec_idx.p, (const uint64_t*)dig,
+                       (const uint32_t*)c->grp_wtab.p, (const uint32_t*)c->grp_commits.p, cls, d_ok, rpk, rst);
+  }
   HIP_TRY(hipGetLastError());
-  // one pairing per round: e(A, H) e(-g1, B) == 1
-  if ((rc = eng_pairing_locked(c, consts, n_rounds, h, rpts, rst, s, n_rounds, nullptr, rpk))) return rc;
+  // one pairing per round: e(A, H) e(-g1, B) == 1; G1 signatures: e(H, A) e(-B, g2) == 1
+  if ((rc = eng_pairing_locked(c, consts, n_rounds, h, rpts, rst, s, n_rounds, nullptr, g1 ? nullptr : rpk, nullptr,
+                               nullptr, false, g1 ? rpk : nullptr)))
+    return rc;
   mark(c, s, "recover_verdict");
   hipLaunchKernelGGL(k_recover_rlc_verdict, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds,
                      d_status ? 1 : 0, (const uint8_t*)rst, cls, d_ok, d_out);
@@ -2694,31 +2863,54 @@ static int recover_device_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_
   return DGPU_OK;
 }
 
+// Bytes of one recovered signature / of a full partial under the installed group.
+static size_t group_sig_bytes(const dgpu_ctx* c) { return c->grp_g1 ? 48 : 96; }
+static size_t group_partial_bytes(const dgpu_ctx* c) { return 2 + group_sig_bytes(c); }
+
+// recover_slots_locked works on 96-byte round slots (its selection, verdict
+// and scatter kernels zero and copy whole slots); a G1-signature group's
+// 48-byte signatures are packed from the context's slots to d_out + 48 r.
+static int recover_device_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_msgs, size_t m,
+                                 const uint8_t* d_parts, size_t stride, const uint32_t* d_plen, uint8_t* d_out,
+                                 uint8_t* d_ok, uint8_t* d_status, hipStream_t s) {
+  if (!c->grp_g1) return recover_slots_locked(c, n_rounds, d_msgs, m, d_parts, stride, d_plen, d_out, d_ok, d_status, s);
+  int rc;
+  if ((rc = c->rec_slots.ensure(n_rounds * 96))) return rc;
+  uint8_t* slots = (uint8_t*)c->rec_slots.p;
+  if ((rc = recover_slots_locked(c, n_rounds, d_msgs, m, d_parts, stride, d_plen, slots, d_ok, d_status, s))) return rc;
+  hipLaunchKernelGGL(k_recover_pack48, dim3(grid_for(n_rounds * 48, 256)), dim3(256), 0, s, n_rounds,
+                     (const uint8_t*)slots, (const uint8_t*)d_ok, d_out);
+  HIP_TRY(hipGetLastError());
+  return DGPU_OK;
+}
+
 extern "C" {
 
 int dgpu_recover_batch_device(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_msgs32, size_t m,
                               const uint8_t* d_partials, size_t partial_stride, const uint32_t* d_partial_len,
-                              uint8_t* d_out_sigs96, uint8_t* d_ok, uint8_t* d_status, void* stream) {
+                              uint8_t* d_out_sigs, uint8_t* d_ok, uint8_t* d_status, void* stream) {
   if (!c) return set_err(DGPU_EINVAL, "null ctx");
   if (n_rounds == 0) return DGPU_OK;  // an empty batch: no-op, NULL buffers accepted (as the verify entry points)
-  if (!d_msgs32 || !d_partials || !d_partial_len || !d_out_sigs96 || !d_ok) return set_err(DGPU_EINVAL, "null argument");
-  if (m == 0 || partial_stride < 98) return set_err(DGPU_EINVAL, "need m >= 1 partial slots and stride >= 98");
+  if (!d_msgs32 || !d_partials || !d_partial_len || !d_out_sigs || !d_ok) return set_err(DGPU_EINVAL, "null argument");
   std::lock_guard<std::mutex> lk(c->mu);
+  if (m == 0 || partial_stride < group_partial_bytes(c))
+    return set_err(DGPU_EINVAL, "need m >= 1 partial slots and stride >= %zu", group_partial_bytes(c));
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = caller_stream(stream);
   stream_order ord(c, s);
-  return recover_device_locked(c, n_rounds, d_msgs32, m, d_partials, partial_stride, d_partial_len, d_out_sigs96,
+  return recover_device_locked(c, n_rounds, d_msgs32, m, d_partials, partial_stride, d_partial_len, d_out_sigs,
                                d_ok, d_status, s);
 }
 
 int dgpu_recover_batch(dgpu_ctx* c, size_t n_rounds, const uint8_t* msgs32, size_t m, const uint8_t* partials,
-                       size_t partial_stride, const uint32_t* partial_len, uint8_t* out_sigs96, uint8_t* ok_bits,
+                       size_t partial_stride, const uint32_t* partial_len, uint8_t* out_sigs, uint8_t* ok_bits,
                        uint8_t* partial_valid) {
   if (!c) return set_err(DGPU_EINVAL, "null ctx");
   if (n_rounds == 0) return DGPU_OK;  // an empty batch: no-op, NULL buffers accepted (as the verify entry points)
-  if (!msgs32 || !partials || !partial_len || !out_sigs96 || !ok_bits) return set_err(DGPU_EINVAL, "null argument");
-  if (m == 0 || partial_stride < 98) return set_err(DGPU_EINVAL, "need m >= 1 partial slots and stride >= 98");
+  if (!msgs32 || !partials || !partial_len || !out_sigs || !ok_bits) return set_err(DGPU_EINVAL, "null argument");
   std::lock_guard<std::mutex> lk(c->mu);
+  if (m == 0 || partial_stride < group_partial_bytes(c))
+    return set_err(DGPU_EINVAL, "need m >= 1 partial slots and stride >= %zu", group_partial_bytes(c));
   if (!c->grp_t) return set_err(DGPU_ENOKEY, "no threshold group installed (dgpu_set_group)");
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = c->stream;
@@ -2741,7 +2933,7 @@ int dgpu_recover_batch(dgpu_ctx* c, size_t n_rounds, const uint8_t* msgs32, size
                                   (uint8_t*)c->rec_ok.p, partial_valid ? (uint8_t*)c->out_reason.p : nullptr, s)))
     return rc;
   std::vector<uint8_t> okv(n_rounds), stv(partial_valid ? items : 0);
-  HIP_TRY(hipMemcpyAsync(out_sigs96, c->rec_out.p, n_rounds * 96, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(out_sigs, c->rec_out.p, n_rounds * group_sig_bytes(c), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(okv.data(), c->rec_ok.p, n_rounds, hipMemcpyDeviceToHost, s));
   if (partial_valid) HIP_TRY(hipMemcpyAsync(stv.data(), c->out_reason.p, items, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -2755,7 +2947,17 @@ int dgpu_recover_batch(dgpu_ctx* c, size_t n_rounds, const uint8_t* msgs32, size
 
 int dgpu_make_partials(dgpu_ctx* c, size_t n_rounds, const uint8_t* msgs32, size_t m, const uint32_t* sign_idx,
                        const uint32_t* label, const uint8_t* shares_be32, size_t n_shares, uint8_t* out98) {
+  return dgpu_make_partials_scheme(c, DGPU_SCHEME_CHAINED, n_rounds, msgs32, m, sign_idx, label, shares_be32, n_shares,
+                                   out98);
+}
+
+int dgpu_make_partials_scheme(dgpu_ctx* c, int scheme, size_t n_rounds, const uint8_t* msgs32, size_t m,
+                              const uint32_t* sign_idx, const uint32_t* label, const uint8_t* shares_be32,
+                              size_t n_shares, uint8_t* out98) {
   if (!c) return set_err(DGPU_EINVAL, "null ctx");
+  if (!scheme_known(scheme)) return set_err(DGPU_EINVAL, "bad scheme %d", scheme);
+  const bool g1 = sig_on_g1(scheme);
+  const size_t pb = g1 ? 50 : 98;  // bytes per partial
   if (n_rounds == 0 || m == 0) return DGPU_OK;
   if (!msgs32 || !sign_idx || !label || !shares_be32 || !out98) return set_err(DGPU_EINVAL, "null argument");
   const size_t items = n_rounds * m;
@@ -2780,7 +2982,7 @@ int dgpu_make_partials(dgpu_ctx* c, size_t n_rounds, const uint8_t* msgs32, size
   };
   if ((rc = d_msgs.ensure(n_rounds * 32)) || (rc = d_h.ensure(n_rounds * G2A_WORDS * 4)) ||
       (rc = d_si.ensure(items * 4)) || (rc = d_lb.ensure(items * 4)) || (rc = d_sh.ensure(n_shares * sizeof(scalar256))) ||
-      (rc = d_out.ensure(items * 98))) {
+      (rc = d_out.ensure(items * pb))) {
     cleanup();
     return rc;
   }
@@ -2789,17 +2991,26 @@ int dgpu_make_partials(dgpu_ctx* c, size_t n_rounds, const uint8_t* msgs32, size
   if (e == hipSuccess) e = hipMemcpyAsync(d_lb.p, label, items * 4, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(d_sh.p, sh.data(), n_shares * sizeof(scalar256), hipMemcpyHostToDevice, s);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_hash_to_g2_msgs_pts, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds,
-                       (const uint8_t*)d_msgs.p, (uint32_t*)d_h.p);
+    if (g1)
+      hipLaunchKernelGGL(k_hash_to_g1_msgs_pts, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds,
+                         (const uint8_t*)d_msgs.p, scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, (uint32_t*)d_h.p);
+    else
+      hipLaunchKernelGGL(k_hash_to_g2_msgs_pts, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds,
+                         (const uint8_t*)d_msgs.p, (uint32_t*)d_h.p);
     e = hipGetLastError();
   }
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_sign_partials, dim3(grid_for(items, 64)), dim3(64), 0, s, items, m, n_rounds,
-                       (const uint32_t*)d_h.p, (const uint32_t*)d_si.p, (const uint32_t*)d_lb.p,
-                       (const scalar256*)d_sh.p, (uint8_t*)d_out.p);
+    if (g1)
+      hipLaunchKernelGGL(k_sign_partials_g1, dim3(grid_for(items, 64)), dim3(64), 0, s, items, m, n_rounds,
+                         (const uint32_t*)d_h.p, (const uint32_t*)d_si.p, (const uint32_t*)d_lb.p,
+                         (const scalar256*)d_sh.p, (uint8_t*)d_out.p);
+    else
+      hipLaunchKernelGGL(k_sign_partials, dim3(grid_for(items, 64)), dim3(64), 0, s, items, m, n_rounds,
+                         (const uint32_t*)d_h.p, (const uint32_t*)d_si.p, (const uint32_t*)d_lb.p,
+                         (const scalar256*)d_sh.p, (uint8_t*)d_out.p);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(out98, d_out.p, items * 98, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(out98, d_out.p, items * pb, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   cleanup();
   if (e != hipSuccess) return set_err(DGPU_EDEVICE, "make_partials: %s", hipGetErrorString(e));

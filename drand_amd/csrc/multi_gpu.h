@@ -383,6 +383,16 @@ int dgpu_verify_multi(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_le
 
 extern "C" {
 
+int dgpu_multi_set_group_scheme(dgpu_multi* m, int scheme, int t, int n, const uint8_t* commits, size_t commit_len) {
+  if (!m) return set_err(DGPU_EINVAL, "null handle");
+  std::lock_guard<std::mutex> mlk(m->mu);
+  for (int k = 0; k < m->ndev; ++k) {
+    int rc = dgpu_set_group_scheme(m->ctx[k], scheme, t, n, commits, commit_len);
+    if (rc) return set_err(rc, "device %d: %s", m->devs[k], std::string(g_last_error).c_str());
+  }
+  return DGPU_OK;
+}
+
 int dgpu_multi_set_group(dgpu_multi* m, int t, int n, const uint8_t* commits48) {
   if (!m) return set_err(DGPU_EINVAL, "null handle");
   std::lock_guard<std::mutex> mlk(m->mu);
@@ -400,12 +410,12 @@ int dgpu_multi_set_group(dgpu_multi* m, int t, int n, const uint8_t* commits48) 
 // and the recovered signatures and per-partial statuses -- data, not
 // verdicts -- go to the host straight from the device that made them.
 int dgpu_recover_multi(dgpu_multi* m, size_t n_rounds, const uint8_t* msgs32, size_t m_slots, const uint8_t* partials,
-                       size_t partial_stride, const uint32_t* partial_len, uint8_t* out_sigs96, uint8_t* ok_bits,
+                       size_t partial_stride, const uint32_t* partial_len, uint8_t* out_sigs, uint8_t* ok_bits,
                        uint8_t* partial_valid) {
   if (!m) return set_err(DGPU_EINVAL, "null multi handle");
   if (n_rounds == 0) return DGPU_OK;  // an empty batch: no-op, NULL buffers accepted
-  if (!msgs32 || !partials || !partial_len || !out_sigs96 || !ok_bits) return set_err(DGPU_EINVAL, "null argument");
-  if (m_slots == 0 || partial_stride < 98) return set_err(DGPU_EINVAL, "need m >= 1 partial slots and stride >= 98");
+  if (!msgs32 || !partials || !partial_len || !out_sigs || !ok_bits) return set_err(DGPU_EINVAL, "null argument");
+  if (m_slots == 0) return set_err(DGPU_EINVAL, "need m >= 1 partial slots");
   const size_t items = n_rounds * m_slots;
   for (size_t i = 0; i < items; ++i)
     if (partial_len[i] > partial_stride) return set_err(DGPU_EINVAL, "partial_len[%zu] > stride", i);
@@ -420,6 +430,8 @@ int dgpu_recover_multi(dgpu_multi* m, size_t n_rounds, const uint8_t* msgs32, si
     dgpu_ctx* c = m->ctx[k];
     if (!c->grp_t) return set_err(DGPU_ENOKEY, "device %d: no threshold group installed (dgpu_multi_set_group)",
                                   m->devs[k]);
+    if (partial_stride < group_partial_bytes(c))
+      return set_err(DGPU_EINVAL, "need stride >= %zu", group_partial_bytes(c));
     dgpu_shard_range(n_rounds, D, k, &lo[k], &hi[k]);
     HIP_TRY(hipSetDevice(c->device));
     multi_bufs& b = m->buf[k];
@@ -452,7 +464,8 @@ int dgpu_recover_multi(dgpu_multi* m, size_t n_rounds, const uint8_t* msgs32, si
     hipLaunchKernelGGL(k_pack_ok, dim3(grid_for((nr + 7) / 8, 256)), dim3(256), 0, s, nr, (const uint8_t*)c->rec_ok.p,
                        (uint8_t*)m->buf[k].bits.p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out_sigs96 + lo[k] * 96, c->rec_out.p, nr * 96, hipMemcpyDeviceToHost, s));
+    const size_t sb = group_sig_bytes(c);  // 48 for a G1-signature group
+    HIP_TRY(hipMemcpyAsync(out_sigs + lo[k] * sb, c->rec_out.p, nr * sb, hipMemcpyDeviceToHost, s));
     if (partial_valid) {
       stv[k].resize(it);
       HIP_TRY(hipMemcpyAsync(stv[k].data(), c->out_reason.p, it, hipMemcpyDeviceToHost, s));

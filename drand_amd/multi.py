@@ -12,7 +12,7 @@ import numpy as np
 from . import _lib
 from .chain import pack_beacons, rlc_seed_for
 from .scheme import Scheme, scheme_code
-from .threshold import pack_partials, unpack_recovered
+from .threshold import group_scheme_code, pack_partials, sig_bytes, unpack_recovered
 
 
 class MultiVerifier:
@@ -54,12 +54,20 @@ class MultiThresholdGroup:
     """ThresholdGroup's batch recovery over several GPUs (dgpu_multi_set_group
     + dgpu_recover_multi): rounds shard contiguously across the devices."""
 
-    def __init__(self, commits, n, devices=None, mctx=None):
+    def __init__(self, commits, n, devices=None, mctx=None, scheme=None):
+        """scheme as ThresholdGroup's: None for 48-byte G1 commitments, a
+        G1-signature scheme (name, Scheme or code) for 96-byte G2 ones."""
         self.commits = [bytes(c) for c in commits]
+        self.scheme_code = group_scheme_code(self.commits, scheme)
+        self.sig_len = sig_bytes(self.scheme_code)
         self.t, self.n = len(self.commits), n
         self.mctx = mctx if mctx is not None else _lib.MultiContext(devices)
         buf = np.frombuffer(b"".join(self.commits), dtype=np.uint8).copy()
-        _lib.check(self.mctx.lib.dgpu_multi_set_group(self.mctx.handle, self.t, n, _lib.ptr(buf)))
+        if self.sig_len == 96:
+            _lib.check(self.mctx.lib.dgpu_multi_set_group(self.mctx.handle, self.t, n, _lib.ptr(buf)))
+        else:
+            _lib.check(self.mctx.lib.dgpu_multi_set_group_scheme(self.mctx.handle, self.scheme_code, self.t, n,
+                                                                 _lib.ptr(buf), len(self.commits[0])))
 
     def close(self):
         self.mctx.close()
@@ -69,16 +77,16 @@ class MultiThresholdGroup:
         nr = len(msgs)
         if nr == 0:
             return [], []
-        mb, buf, plen, m, stride = pack_partials(msgs, partials)
+        mb, buf, plen, m, stride = pack_partials(msgs, partials, self.scheme_code)
         return self.recover_records(mb, buf, plen, partials, statuses)
 
     def recover_records(self, mb, buf, plen, partials=None, statuses=False):
         nr, m, stride = buf.shape
-        out = np.zeros(nr * 96, dtype=np.uint8)
+        out = np.zeros(nr * self.sig_len, dtype=np.uint8)
         ok = np.zeros((nr + 7) // 8, dtype=np.uint8)
         pv = np.zeros(nr * m, dtype=np.uint8) if statuses else None
         _lib.check(self.mctx.lib.dgpu_recover_multi(self.mctx.handle, nr, _lib.ptr(mb), m, _lib.ptr(buf), stride,
                                                     _lib.ptr(plen), _lib.ptr(out), _lib.ptr(ok), _lib.ptr(pv)))
         if partials is None:
             partials = [[b"x"] * m for _ in range(nr)]
-        return unpack_recovered(out, ok, pv, partials, m)
+        return unpack_recovered(out, ok, pv, partials, m, self.sig_len)

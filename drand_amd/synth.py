@@ -209,10 +209,12 @@ def corrupt_global(shard, seed, n_total, lo, rate=1e-3, kinds=ALL_CORRUPTIONS):
 class Group:
     """A t-of-n threshold group: polynomial coefficients a_0..a_{t-1} over Fr
     (a_0 = derive_secret(seed), the group secret), the public commitments
-    C_j = a_j * g1 (48-byte compressed) and the shares s_i = f(i + 1)."""
+    C_j = a_j * g1 (48-byte compressed; a_j * g2, 96 bytes, under a
+    G1-signature scheme) and the shares s_i = f(i + 1)."""
 
-    def __init__(self, seed, t, n, coeffs, commits):
+    def __init__(self, seed, t, n, coeffs, commits, scheme=_lib.SCHEME_CHAINED):
         self.seed, self.t, self.n = seed, t, n
+        self.scheme_code = scheme
         self.coeffs = coeffs
         self.commits = commits
         self.shares = [poly_eval(coeffs, i + 1) for i in range(n)]
@@ -235,57 +237,68 @@ def poly_eval(coeffs, x):
     return acc
 
 
-def make_group(seed, t, n, device=0):
-    """Commitments derived on the GPU (dgpu_derive_pubkey per coefficient)."""
+def _sig_len(scheme):
+    return 48 if scheme in (_lib.SCHEME_UNCHAINED_G1, _lib.SCHEME_G1_RFC9380) else 96
+
+
+def make_group(seed, t, n, device=0, scheme=_lib.SCHEME_CHAINED):
+    """Commitments derived on the GPU (dgpu_derive_pubkey per coefficient):
+    on G1, or on G2 for a G1-signature scheme code."""
     ctx = get_context(device)
     coeffs = share_coeffs(seed, t)
     commits = []
+    klen = 144 - _sig_len(scheme)  # the key group is the other one
     for a in coeffs:
-        pk = np.zeros(48, dtype=np.uint8)
+        pk = np.zeros(klen, dtype=np.uint8)
         skb = np.frombuffer(a.to_bytes(32, "big"), dtype=np.uint8).copy()
-        _lib.check(ctx.lib.dgpu_derive_pubkey(ctx.handle, _lib.SCHEME_CHAINED, _lib.ptr(skb), _lib.ptr(pk), 48))
+        _lib.check(ctx.lib.dgpu_derive_pubkey(ctx.handle, scheme, _lib.ptr(skb), _lib.ptr(pk), klen))
         commits.append(bytes(pk))
-    return Group(seed, t, n, coeffs, commits)
+    return Group(seed, t, n, coeffs, commits, scheme)
 
 
-def sign_partials(group, msgs, sign_idx, labels=None, device=0):
+def sign_partials(group, msgs, sign_idx, labels=None, device=0, scheme=None):
     """tbls.Sign of every (round, slot): msgs (n_rounds, 32) uint8, sign_idx
     (n_rounds, m) share indices; labels (default = sign_idx) the BE16 index
     written in front (a label that differs from the signer makes an invalid
-    partial).  Returns (n_rounds, m, 98) uint8.  Runs on the GPU
-    (dgpu_make_partials)."""
+    partial).  Returns (n_rounds, m, 98) uint8 -- (n_rounds, m, 50) under a
+    G1-signature scheme code (default: the group's).  Runs on the GPU
+    (dgpu_make_partials_scheme)."""
+    scheme = group.scheme_code if scheme is None else scheme
     ctx = get_context(device)
     msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
     sign_idx = np.ascontiguousarray(sign_idx, dtype=np.uint32)
     labels = sign_idx if labels is None else np.ascontiguousarray(labels, dtype=np.uint32)
     nr, m = sign_idx.shape
     shares = np.frombuffer(b"".join(s.to_bytes(32, "big") for s in group.shares), dtype=np.uint8).copy()
-    out = np.zeros((nr, m, 98), dtype=np.uint8)
-    _lib.check(ctx.lib.dgpu_make_partials(ctx.handle, nr, _lib.ptr(msgs), m, _lib.ptr(sign_idx), _lib.ptr(labels),
-                                          _lib.ptr(shares), len(group.shares), _lib.ptr(out)))
+    out = np.zeros((nr, m, 2 + _sig_len(scheme)), dtype=np.uint8)
+    _lib.check(ctx.lib.dgpu_make_partials_scheme(ctx.handle, scheme, nr, _lib.ptr(msgs), m, _lib.ptr(sign_idx),
+                                                 _lib.ptr(labels), _lib.ptr(shares), len(group.shares),
+                                                 _lib.ptr(out)))
     return out
 
 
-def group_signatures(group, msgs, device=0):
+def group_signatures(group, msgs, device=0, scheme=None):
     """sk * H(msg) for every message (the expected recovered signatures),
-    through dgpu_make_partials with the group secret as the only share."""
+    through dgpu_make_partials_scheme with the group secret as the only share."""
+    scheme = group.scheme_code if scheme is None else scheme
     ctx = get_context(device)
     msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
     nr = msgs.shape[0]
     zeros = np.zeros(nr, dtype=np.uint32)
     sk = np.frombuffer(group.coeffs[0].to_bytes(32, "big"), dtype=np.uint8).copy()
-    out = np.zeros((nr, 98), dtype=np.uint8)
-    _lib.check(ctx.lib.dgpu_make_partials(ctx.handle, nr, _lib.ptr(msgs), 1, _lib.ptr(zeros), _lib.ptr(zeros),
-                                          _lib.ptr(sk), 1, _lib.ptr(out)))
+    out = np.zeros((nr, 2 + _sig_len(scheme)), dtype=np.uint8)
+    _lib.check(ctx.lib.dgpu_make_partials_scheme(ctx.handle, scheme, nr, _lib.ptr(msgs), 1, _lib.ptr(zeros),
+                                                 _lib.ptr(zeros), _lib.ptr(sk), 1, _lib.ptr(out)))
     return out[:, 2:].copy()
 
 
-def make_recovery_batch(group, n_rounds, seed, bad_rate=0.1, first_round=1, device=0):
+def make_recovery_batch(group, n_rounds, seed, bad_rate=0.1, first_round=1, device=0, scheme=None):
     """configs[4] workload: per round the DigestMessage of an unchained round
     (SHA-256(BE64 round)) and t partials from distinct random signers; in a
     `bad_rate` fraction of rounds one partial carries a wrong index (fails
     VerifyPartial), so that round cannot be recovered (t - 1 good).
-    Returns (msgs (n, 32), partials (n, t, 98), expect_ok (n,) bool)."""
+    Returns (msgs (n, 32), partials (n, t, 98), expect_ok (n,) bool);
+    partials (n, t, 50) under a G1-signature scheme code (default: the group's)."""
     rng = np.random.default_rng(seed)
     msgs = np.zeros((n_rounds, 32), dtype=np.uint8)
     for r in range(n_rounds):
@@ -297,5 +310,5 @@ def make_recovery_batch(group, n_rounds, seed, bad_rate=0.1, first_round=1, devi
     rows = np.nonzero(bad)[0]
     cols = rng.integers(0, t, size=len(rows))
     labels[rows, cols] = (labels[rows, cols] + 1 + rng.integers(0, n - 1, size=len(rows))) % n
-    parts = sign_partials(group, msgs, sign_idx, labels, device=device)
+    parts = sign_partials(group, msgs, sign_idx, labels, device=device, scheme=scheme)
     return msgs, parts, ~bad

@@ -6,9 +6,12 @@ Mirrors (names, argument meaning, error behaviour):
 and the batch form an aggregator or a catch-up recomputation needs:
   ThresholdGroup.recover_batch(msgs, partials)   one GPU call for many rounds
 
-A share.PubPoly is represented by its t compressed G1 commitments (48 bytes
-each, key/keys.go DistPublic.Coefficients).  No CPU fallback: the work runs
-in libdrand_gpu.so (dgpu_set_group / dgpu_recover_batch).
+A share.PubPoly is represented by its t compressed commitments (key/keys.go
+DistPublic.Coefficients): 48-byte G1 points for the G2-signature schemes,
+96-byte G2 points for the G1-signature schemes (bls-unchained-on-g1,
+bls-unchained-g1-rfc9380), whose partials are BE16(index) || 48-byte G1
+signature and whose recovered signatures are 48 bytes.  No CPU fallback: the
+work runs in libdrand_gpu.so (dgpu_set_group_scheme / dgpu_recover_batch).
 """
 import struct
 import threading
@@ -17,6 +20,39 @@ import numpy as np
 
 from . import _lib
 from .chain import get_context
+from .scheme import Scheme, get_scheme_by_id_with_default, scheme_code
+
+_G1_SIG_CODES = (_lib.SCHEME_UNCHAINED_G1, _lib.SCHEME_G1_RFC9380)
+
+
+def group_scheme_code(commits, scheme=None):
+    """The scheme code a group of these commitments installs under: `scheme`
+    is a scheme name, a Scheme or a code; None means the default G2-signature
+    group and needs 48-byte commitments.  ValueError if the commitments'
+    length does not fit the scheme's key group (96 bytes for the G1-signature
+    schemes, 48 otherwise)."""
+    if scheme is None:
+        code = _lib.SCHEME_CHAINED
+    elif isinstance(scheme, Scheme):
+        code = scheme_code(scheme)
+    elif isinstance(scheme, str):
+        code = scheme_code(get_scheme_by_id_with_default(scheme))
+    else:
+        code = int(scheme)
+        if code not in (_lib.SCHEME_CHAINED, _lib.SCHEME_UNCHAINED) + _G1_SIG_CODES:
+            raise ValueError(f"scheme code {code} is not valid")
+    want = 96 if code in _G1_SIG_CODES else 48
+    lens = {len(c) for c in commits}
+    if lens != {want}:
+        if scheme is None and lens == {96}:
+            raise ValueError("96-byte (G2) commitments need a G1-signature scheme")
+        raise ValueError(f"commitments of lengths {sorted(lens)} do not fit the scheme ({want} bytes each)")
+    return code
+
+
+def sig_bytes(code):
+    """Signature length of a scheme code: 48 on G1, 96 on G2."""
+    return 48 if code in _G1_SIG_CODES else 96
 
 
 class RecoverError(Exception):
@@ -31,12 +67,13 @@ def index_of(partial):
     return struct.unpack(">H", partial[:2])[0]
 
 
-def pack_partials(msgs, partials):
+def pack_partials(msgs, partials, scheme=_lib.SCHEME_CHAINED):
     """Fixed-stride partial records of the C-ABI: (msgs (nr*32,), partials
-    (nr, m, stride), partial_len (nr, m), m, stride); empty slots have length 0."""
+    (nr, m, stride), partial_len (nr, m), m, stride); empty slots have length 0.
+    The stride is at least the scheme's partial length (2 + signature bytes)."""
     nr = len(msgs)
     m = max(1, max(len(p) for p in partials))
-    stride = max([98] + [len(s) for p in partials for s in p])
+    stride = max([2 + sig_bytes(scheme)] + [len(s) for p in partials for s in p])
     buf = np.zeros((nr, m, stride), dtype=np.uint8)
     plen = np.zeros((nr, m), dtype=np.uint32)
     for r, plist in enumerate(partials):
@@ -50,10 +87,10 @@ def pack_partials(msgs, partials):
     return mb, buf, plen, m, stride
 
 
-def unpack_recovered(out, ok, pv, partials, m):
+def unpack_recovered(out, ok, pv, partials, m, sig_len=96):
     nr = len(partials)
     okb = np.unpackbits(ok, bitorder="little")[:nr]
-    sigs = [bytes(out[96 * r:96 * (r + 1)]) if okb[r] else None for r in range(nr)]
+    sigs = [bytes(out[sig_len * r:sig_len * (r + 1)]) if okb[r] else None for r in range(nr)]
     if pv is None:
         return sigs, None
     valid = [[bool(pv[r * m + j]) for j in range(len(partials[r]))] for r in range(nr)]
@@ -65,46 +102,62 @@ class ThresholdGroup:
 
     _lock = threading.Lock()
 
-    def __init__(self, commits, n, device=0):
+    def __init__(self, commits, n, device=0, scheme=None):
+        """scheme: None (48-byte G1 commitments, G2 signatures, as always), or
+        a scheme name / Scheme / code; 96-byte G2 commitments require one of
+        the G1-signature schemes.  A mismatch raises ValueError before any
+        library call."""
         self.commits = [bytes(c) for c in commits]
+        self.scheme_code = group_scheme_code(self.commits, scheme)
+        self.sig_len = sig_bytes(self.scheme_code)
         self.t = len(self.commits)
         self.n = n
         self.ctx = get_context(device)
-        buf = np.frombuffer(b"".join(self.commits), dtype=np.uint8).copy()
         with ThresholdGroup._lock:
-            _lib.check(self.ctx.lib.dgpu_set_group(self.ctx.handle, self.t, n, _lib.ptr(buf)))
-            ThresholdGroup._active = (id(self.ctx), tuple(self.commits), n)
+            ThresholdGroup._active = None
+            self._set_group()
+            ThresholdGroup._active = self._key()
+
+    def _key(self):
+        return (id(self.ctx), self.scheme_code, tuple(self.commits), self.n)
+
+    def _set_group(self):
+        buf = np.frombuffer(b"".join(self.commits), dtype=np.uint8).copy()
+        if self.sig_len == 96:
+            _lib.check(self.ctx.lib.dgpu_set_group(self.ctx.handle, self.t, self.n, _lib.ptr(buf)))
+        else:
+            _lib.check(self.ctx.lib.dgpu_set_group_scheme(self.ctx.handle, self.scheme_code, self.t, self.n,
+                                                          _lib.ptr(buf), len(self.commits[0])))
 
     def _install(self):
-        key = (id(self.ctx), tuple(self.commits), self.n)
-        if getattr(ThresholdGroup, "_active", None) != key:
-            buf = np.frombuffer(b"".join(self.commits), dtype=np.uint8).copy()
-            _lib.check(self.ctx.lib.dgpu_set_group(self.ctx.handle, self.t, self.n, _lib.ptr(buf)))
-            ThresholdGroup._active = key
+        if getattr(ThresholdGroup, "_active", None) != self._key():
+            self._set_group()
+            ThresholdGroup._active = self._key()
 
     def recover_batch(self, msgs, partials, statuses=True):
         """msgs: list of 32-byte messages (DigestMessage of each round);
         partials: list (per round) of lists of partial signatures (bytes).
-        Returns (sigs, valid): sigs[r] = 96-byte recovered signature or None
+        Returns (sigs, valid): sigs[r] = recovered signature (96 bytes; 48
+        for a G1-signature group) or None
         (the reference's error), valid[r][j] = partial j verified.  With
         statuses=False valid is None and the library verifies each round's
         candidates with one batched pairing (recover.cuh)."""
         nr = len(msgs)
         if nr == 0:
             return [], []
-        mb, buf, plen, m, stride = pack_partials(msgs, partials)
-        out = np.zeros(nr * 96, dtype=np.uint8)
+        mb, buf, plen, m, stride = pack_partials(msgs, partials, self.scheme_code)
+        out = np.zeros(nr * self.sig_len, dtype=np.uint8)
         ok = np.zeros((nr + 7) // 8, dtype=np.uint8)
         pv = np.zeros(nr * m, dtype=np.uint8) if statuses else None
         with ThresholdGroup._lock:
             self._install()
             _lib.check(self.ctx.lib.dgpu_recover_batch(self.ctx.handle, nr, _lib.ptr(mb), m, _lib.ptr(buf), stride,
                                                        _lib.ptr(plen), _lib.ptr(out), _lib.ptr(ok), _lib.ptr(pv)))
-        return unpack_recovered(out, ok, pv, partials, m)
+        return unpack_recovered(out, ok, pv, partials, m, self.sig_len)
 
     def recover(self, msg, sigs):
-        """key.Scheme.Recover(pub, msg, sigs, t, n): the recovered 96-byte
-        signature, or RecoverError."""
+        """key.Scheme.Recover(pub, msg, sigs, t, n): the recovered signature
+        (96 bytes, 48 for a G1-signature group), or RecoverError."""
         out, _ = self.recover_batch([msg], [list(sigs)], statuses=False)
         if out[0] is None:
             raise RecoverError("share: not enough good public shares to reconstruct secret commitment")

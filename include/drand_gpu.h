@@ -55,7 +55,12 @@ extern "C" {
  * legacy default (null) stream, no longer the context's own stream;
  * dgpu_synchronize added; dgpu_stage_times returns the count of stages the
  * call recorded (may exceed max_stages); RLC mode accepted for the G1-signature
- * schemes; DGPU_MAX_STAGES 32. */
+ * schemes; DGPU_MAX_STAGES 32.
+ * Added to ABI 3 without a version change (additive only): threshold
+ * recovery for the G1-signature schemes -- dgpu_set_group_scheme,
+ * dgpu_multi_set_group_scheme, dgpu_make_partials_scheme; the recover entry
+ * points follow the installed group's scheme (their out_sigs96 parameters
+ * are now out_sigs, stride 96 or 48 bytes per round). */
 #define DGPU_ABI_VERSION 3
 
 /* scheme IDs (common/scheme/scheme.go:9,12; bls-unchained-on-g1 added by this build) */
@@ -234,8 +239,9 @@ int dgpu_verify_batch_device(dgpu_ctx *ctx, int scheme, size_t n, const uint64_t
  * first under DGPU_G1_LINES=buffer), ...; RLC mode: rlc_hash_to_g2_raw /
  * rlc_hash_to_g1_raw, decode_g2 / decode_g1, rlc_affine, rlc_root_msm,
  * rlc_prep, the engine stages of the node checks, rlc_leaves_tree,
- * rlc_bisection; recovery: recover_hash, recover_decode, engine stages,
- * recover_msm, recover_verdict), at most max_stages of them, and returns the
+ * rlc_bisection; recovery: recover_hash, recover_decode, recover_select,
+ * recover_lagrange, engine stages, recover_msm, recover_rlc_g1 (a
+ * G1-signature group: recover_rlc_g2), recover_verdict), at most max_stages of them, and returns the
  * number of distinct stages the call recorded (like snprintf: a value above
  * max_stages means the output was truncated).  DGPU_MAX_STAGES bounds every
  * pipeline's count.  A call that recorded more stage events than the
@@ -321,8 +327,24 @@ int dgpu_derive_pubkey(dgpu_ctx *ctx, int scheme, const uint8_t *sk_be32, uint8_
  * key.Scheme.VerifyPartial): t compressed G1 commitments C_0..C_{t-1}
  * (48 bytes each), group size n (share indices 0..n-1 get a precomputed
  * PubPoly.Eval table; larger indices are evaluated on the fly).
- * 1 <= t <= 32, t <= n <= 65536.  Rejects undecodable commitments. */
+ * 1 <= t <= 32, t <= n <= 65536.  Rejects undecodable commitments.
+ * Installs a G2-signature group (the two pedersen-bls schemes). */
 int dgpu_set_group(dgpu_ctx *ctx, int t, int n, const uint8_t *commits48);
+
+/* dgpu_set_group for any scheme.  DGPU_SCHEME_CHAINED / _UNCHAINED:
+ * commit_len must be 48 and the call is exactly dgpu_set_group.
+ * DGPU_SCHEME_UNCHAINED_G1 / _G1_RFC9380 (signatures on G1, keys on G2, the
+ * same key.Scheme.Recover / VerifyPartial call sites): commit_len must be 96,
+ * the commitments are compressed G2 points C_j = a_j g2, decoded with kilic's
+ * rules and the subgroup check; the PubPoly.Eval table is built in G2 and C_0
+ * is installed as VerifyRecovered's key (its fixed Miller-loop lines, as
+ * dgpu_set_pubkey computes them, outside the 8-entry key cache).  The group
+ * remembers its scheme: it selects the hash DST and the partial format of the
+ * recover entry points.  Same limits on t and n.  DGPU_EINVAL for a wrong
+ * commit_len, an unknown scheme, or an undecodable or out-of-subgroup
+ * commitment; a rejected G1-signature call leaves the installed group as it
+ * was. */
+int dgpu_set_group_scheme(dgpu_ctx *ctx, int scheme, int t, int n, const uint8_t *commits, size_t commit_len);
 
 /* Batch form of key.Scheme.Recover (kyber tbls.Recover + share.RecoverCommit
  * (R)) as the aggregator calls it (chain/beacon/chain.go:158-168), n_rounds
@@ -334,22 +356,30 @@ int dgpu_set_group(dgpu_ctx *ctx, int t, int n, const uint8_t *commits48);
  * VerifyPartial (decode + subgroup + pairing against PubPoly.Eval(index))
  * are kept until t are kept; duplicates of an index count once; fewer than t
  * distinct -> the reference's error (bit 0 in ok_bits, zero signature);
- * otherwise out_sigs96 + 96 r = the Lagrange-interpolated signature, kept
+ * otherwise out_sigs + 96 r = the Lagrange-interpolated signature, kept
  * only if it passes VerifyRecovered under C_0 (chain.go:165), as the
  * aggregator does before appending the beacon.
- * partial_valid (optional, n_rounds*m bytes): 1 iff the partial verified. */
+ * partial_valid (optional, n_rounds*m bytes): 1 iff the partial verified.
+ * The call follows the installed group's scheme.  Under a G1-signature group
+ * (dgpu_set_group_scheme) a partial is BE16(share index) || 48-byte G1
+ * signature, 50 bytes -- any other length, 98 included, is a decode error --,
+ * messages are hashed to G1 under the scheme's DST, partial_stride >= 50, and
+ * the recovered signature of round r is 48 bytes at out_sigs + 48 r (zero on
+ * failure); everything else as above.  out_sigs: n_rounds * 96 bytes for a
+ * G2-signature group, n_rounds * 48 for a G1-signature group. */
 int dgpu_recover_batch(dgpu_ctx *ctx, size_t n_rounds, const uint8_t *msgs32, size_t m, const uint8_t *partials,
-                       size_t partial_stride, const uint32_t *partial_len, uint8_t *out_sigs96, uint8_t *ok_bits,
+                       size_t partial_stride, const uint32_t *partial_len, uint8_t *out_sigs, uint8_t *ok_bits,
                        uint8_t *partial_valid);
 
 /* dgpu_recover_batch over device buffers already resident in HBM, enqueued on
  * `stream` (hipStream_t; NULL = the legacy default stream) without host
  * synchronisation.  d_ok: n_rounds bytes (1 = recovered); d_status
  * (optional): n_rounds*m bytes, DGPU_REASON_* of every partial (0 = verified).
- * A partial_len above partial_stride reads as an invalid partial. */
+ * A partial_len above partial_stride reads as an invalid partial.
+ * d_out_sigs: 96 bytes per round, 48 under a G1-signature group. */
 int dgpu_recover_batch_device(dgpu_ctx *ctx, size_t n_rounds, const uint8_t *d_msgs32, size_t m,
                               const uint8_t *d_partials, size_t partial_stride, const uint32_t *d_partial_len,
-                              uint8_t *d_out_sigs96, uint8_t *d_ok, uint8_t *d_status, void *stream);
+                              uint8_t *d_out_sigs, uint8_t *d_ok, uint8_t *d_status, void *stream);
 
 /* Synthetic threshold partials (test/bench data tool; tbls.Sign (R),
  * chain/beacon/node_test.go:56-106 builds the same shape): for item i of
@@ -359,6 +389,13 @@ int dgpu_recover_batch_device(dgpu_ctx *ctx, size_t n_rounds, const uint8_t *d_m
  * yields an invalid partial. */
 int dgpu_make_partials(dgpu_ctx *ctx, size_t n_rounds, const uint8_t *msgs32, size_t m, const uint32_t *sign_idx,
                        const uint32_t *label, const uint8_t *shares_be32, size_t n_shares, uint8_t *out98);
+
+/* dgpu_make_partials for any scheme: the G1-signature schemes write 2 + 48
+ * bytes per item, BE16(label[i]) || compress(share * H_G1(msg)) under the
+ * scheme's DST, at out + 50 i; the other schemes 98 bytes as above. */
+int dgpu_make_partials_scheme(dgpu_ctx *ctx, int scheme, size_t n_rounds, const uint8_t *msgs32, size_t m,
+                              const uint32_t *sign_idx, const uint32_t *label, const uint8_t *shares_be32,
+                              size_t n_shares, uint8_t *out);
 
 /* Synthetic chain generator (test/bench data tool; mirrors the reference's
  * fixture generator client/test/result/mock/result.go:86-130).  Builds
@@ -397,14 +434,17 @@ int dgpu_verify_multi(dgpu_multi *m, int scheme, const uint8_t *pk, size_t pk_le
 /* dgpu_set_group on every device of the handle (the aggregator's group,
  * chain/beacon/chain.go:158-168 -> key.Scheme.Recover). */
 int dgpu_multi_set_group(dgpu_multi *m, int t, int n, const uint8_t *commits48);
+/* dgpu_set_group_scheme on every device of the handle. */
+int dgpu_multi_set_group_scheme(dgpu_multi *m, int scheme, int t, int n, const uint8_t *commits, size_t commit_len);
 
 /* dgpu_recover_batch over the node: rounds shard contiguously across the
  * devices (dgpu_shard_range over n_rounds), each device recovers its shard,
  * RCCL all-gathers the per-device recovery bitmaps; recovered signatures and
  * per-partial validity go to the host from the device that computed them.
- * Arguments and results exactly as dgpu_recover_batch. */
+ * Arguments and results exactly as dgpu_recover_batch (out_sigs: 96 bytes per
+ * round, 48 under a G1-signature group). */
 int dgpu_recover_multi(dgpu_multi *m, size_t n_rounds, const uint8_t *msgs32, size_t m_slots, const uint8_t *partials,
-                       size_t partial_stride, const uint32_t *partial_len, uint8_t *out_sigs96, uint8_t *ok_bits,
+                       size_t partial_stride, const uint32_t *partial_len, uint8_t *out_sigs, uint8_t *ok_bits,
                        uint8_t *partial_valid);
 
 /* Test mode (environment, read by dgpu_multi_open): DGPU_MULTI_ALLOW_SAME_DEVICE=1
