@@ -54,9 +54,11 @@ int set_err(int code, const char* fmt, ...) {
     if (_e != hipSuccess) return set_err(DGPU_EDEVICE, "%s: %s", #expr, hipGetErrorString(_e)); \
   } while (0)
 
-// Grow-only device scratch buffer.  Growth frees the old allocation only
-// after the device is idle: a kernel enqueued earlier (this call or an
-// earlier asynchronous one) may still read it.
+// Grow-only device scratch buffer, owner of its allocation.  Growth frees the
+// old allocation only after the device is idle: a kernel enqueued earlier
+// (this call or an earlier asynchronous one) may still read it.  The
+// destructor and release() free at once: the owner has drained the streams
+// that used the buffer (dgpu_close, stream_scratch, the callers of release()).
 #ifdef DG_AB_KNOBS
 // test hook of the A/B build (DGPU_TEST_ALLOC_CAP=<bytes>): larger requests
 // fail as an out-of-memory hipMalloc would (the engine chunk's retry path)
@@ -65,6 +67,19 @@ size_t g_test_alloc_cap = 0;
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p, cap = o.cap;
+      o.p = nullptr, o.cap = 0;
+    }
+    return *this;
+  }
+  ~DevBuf() { release(); }
   int ensure(size_t bytes) {
     if (bytes <= cap) return DGPU_OK;
 #ifdef DG_AB_KNOBS
@@ -307,6 +322,17 @@ struct stream_order {
   ~stream_order() { hipEventRecord(c->done, s); }
 };
 
+// N temporary device buffers of a data tool.  However the tool returns, the
+// stream that used them is synchronised first (the destructor's body) and the
+// buffers, being members, are freed after it.
+template <int N>
+struct stream_scratch {
+  hipStream_t s;
+  DevBuf b[N];
+  explicit stream_scratch(hipStream_t s_) : s(s_) {}
+  ~stream_scratch() { (void)hipStreamSynchronize(s); }
+};
+
 // A fork to a side stream (the decode beside the hash, the cofactor's U):
 // however the function returns, the main stream ends up waiting for all the
 // side stream's work, so the call's `done` event (recorded on the main
@@ -415,7 +441,7 @@ int decode_g2_key_locked(dgpu_ctx* c, key_entry* e, const uint8_t* pk) {
   const size_t tbl_words = (size_t)ENG_LINE_STEPS * FP_LIMBS * ENG_WAVE_WORDS;
   if ((rc = e->table.ensure(tbl_words * 4)) || (rc = c->misc.ensure(4096))) return rc;
   if ((rc = upload_eng_consts(&e->consts, nullptr))) return rc;
-  DevBuf unit;
+  DevBuf unit;  // read by k_eng_lines below, which every return path after its launch waits for
   if ((rc = upload_eng_consts(&unit, nullptr, true))) return rc;
   uint8_t* aux = (uint8_t*)c->misc.p;
   uint32_t* d_pk = (uint32_t*)aux;           // affine G2, stride 1 (224 B)
@@ -438,21 +464,14 @@ int decode_g2_key_locked(dgpu_ctx* c, key_entry* e, const uint8_t* pk) {
   int drc = -1;
   if (err == hipSuccess) err = hipMemcpyAsync(&drc, d_rc, sizeof drc, hipMemcpyDeviceToHost, s);
   if (err == hipSuccess) err = hipStreamSynchronize(s);
-  if (err != hipSuccess) {
-    unit.release();
-    return set_err(DGPU_EDEVICE, "set_pubkey: %s", hipGetErrorString(err));
-  }
-  if (drc != DEC_OK) {
-    unit.release();
-    return set_err(DGPU_EINVAL, "public key rejected (decode code %d)", drc);
-  }
+  if (err != hipSuccess) return set_err(DGPU_EDEVICE, "set_pubkey: %s", hipGetErrorString(err));
+  if (drc != DEC_OK) return set_err(DGPU_EINVAL, "public key rejected (decode code %d)", drc);
   hipLaunchKernelGGL(k_eng_lines, dim3(1), dim3(ENG_BLOCK), 0, s, (size_t)1, (size_t)0, (size_t)1,
                      (const uint32_t*)d_pk, (size_t)1, (const uint32_t*)nullptr, (const uint32_t*)d_g2,
                      (const uint32_t*)nullptr, (const uint32_t*)unit.p, (uint32_t*)e->table.p, (uint8_t*)nullptr,
                      (uint32_t*)nullptr);
   err = hipGetLastError();
   if (err == hipSuccess) err = hipStreamSynchronize(s);
-  unit.release();
   if (err != hipSuccess) return set_err(DGPU_EDEVICE, "set_pubkey lines: %s", hipGetErrorString(err));
   return DGPU_OK;
 }
@@ -491,10 +510,213 @@ int get_key_locked(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t len, key_e
   return DGPU_OK;
 }
 
-int eng_pairing_locked(dgpu_ctx* c, const uint32_t* consts, size_t n, const uint32_t* h, const uint32_t* sg,
-                       uint8_t* st, hipStream_t s, size_t h_stride = 0, const uint32_t* h_idx = nullptr,
-                       const uint32_t* pk_items = nullptr, const uint32_t* fixed_table = nullptr,
-                       const lane_bufs* L = nullptr, bool sig_subgroup = false, const uint32_t* g1form_keys = nullptr);
+// Karabina final exponentiation of one chunk (pairing_engine.cuh, DESIGN.md
+// 2b): segment 0 (easy part), then per exponentiation by |x| the compressed
+// chain, its six stored values' norms, the batched inversion of their
+// products (divsteps, fp.cuh fp_inv), the decompression, and the next 12-lane
+// segment (the split at the inversion -- parts formed at the chain's snaps,
+// one thread per round inverting and decompressing -- measured slower, r04j,
+// and removed in round 6); last, the Granger-Scott kernel for the listed
+// blocks with a flagged item.  capb: the chunk capacity
+// rounded up to whole blocks of 5 rounds (>= cnt); kb: ENG_KB_BYTES_PER_ROUND
+// x capb bytes.
+int eng_fe_kb_locked(dgpu_ctx* c, const uint32_t* consts, size_t cnt, size_t capb, size_t r0, uint32_t* f,
+                     const uint32_t* n1inv, uint8_t* kb, uint8_t* st, hipStream_t s) {
+  if (capb % ENG_ROUNDS_PER_BLOCK || cnt > capb) return set_err(DGPU_EINVAL, "karabina FE: bad chunk capacity");
+  uint32_t* xbuf = (uint32_t*)kb;  // [capb / 5 blocks][ENG_KB_PLANES][limb][60]
+  uint32_t* pbuf = xbuf + ENG_KB_XWORDS * capb;
+  uint32_t* pre = pbuf + (size_t)FP_LIMBS * capb;
+  uint32_t* ebuf = pre + (size_t)FP_LIMBS * capb;
+  uint32_t* fb = ebuf + (size_t)ENG_KB_NSNAP * FP_LIMBS * capb;
+  uint8_t* flags = (uint8_t*)(fb + capb);
+  const unsigned blocks = grid_for(cnt, ENG_ROUNDS_PER_BLOCK);
+  const size_t inv_threads = std::max<size_t>(1, (cnt + c->kb_inv_chain - 1) / c->kb_inv_chain);
+  constexpr int nseg = (int)(sizeof(ENG_PROG_FEK_OFF) / sizeof(ENG_PROG_FEK_OFF[0])) - 1;
+  static_assert(nseg == 6, "segment 0 + one per exponentiation by |x|");
+  for (int seg = 0; seg < nseg; ++seg) {
+    if (seg > 0) {
+      mark(c, s, "eng_fe_chain");
+      const bool kb_thread = c->kb_thread && cnt >= c->thr_min;
+      const bool norm_pre = kb_thread && c->kb_norm_chain;
+      if (norm_pre && c->kb_pair)  // two lanes per round
+        hipLaunchKernelGGL(k_kb_chain_pair<true>, dim3(grid_for(2 * cnt, 256)), dim3(256), 0, s, cnt, xbuf, ebuf);
+      else if (norm_pre)
+        hipLaunchKernelGGL(k_kb_chain_thr<true>, dim3(grid_for(cnt, 256)), dim3(256), 0, s, cnt, xbuf, ebuf);
+      else if (kb_thread)
+        hipLaunchKernelGGL(k_kb_chain_thr<false>, dim3(grid_for(cnt, 256)), dim3(256), 0, s, cnt, xbuf, nullptr);
+      else
+        hipLaunchKernelGGL(k_eng_kb_chain, dim3(grid_for(cnt, 8)), dim3(64), 0, s, cnt, xbuf);
+      HIP_TRY(hipGetLastError());
+      mark(c, s, "eng_fe_kbinv");
+      if (norm_pre)
+        hipLaunchKernelGGL(k_eng_kb_norm<true>, dim3(grid_for(cnt, 256)), dim3(256), 0, s, cnt, r0,
+                           (const uint32_t*)xbuf, pbuf, ebuf, flags, (const uint8_t*)st, c->kb_test_flag);
+      else
+        hipLaunchKernelGGL(k_eng_kb_norm<false>, dim3(grid_for(cnt, 256)), dim3(256), 0, s, cnt, r0,
+                           (const uint32_t*)xbuf, pbuf, ebuf, flags, (const uint8_t*)st, c->kb_test_flag);
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(k_eng_inv, dim3(grid_for(inv_threads, 256)), dim3(256), 0, s, cnt, r0, pbuf, pre, st);
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(k_eng_kb_dec, dim3(grid_for((size_t)ENG_KB_NSNAP * cnt, 256)), dim3(256), 0, s, cnt, xbuf,
+                         (const uint32_t*)pbuf, (const uint32_t*)ebuf, (const uint8_t*)flags);
+      HIP_TRY(hipGetLastError());
+    }
+    mark(c, s, "eng_fe");
+    const int so = ENG_PROG_FEK_OFF[seg], sl = ENG_PROG_FEK_OFF[seg + 1] - ENG_PROG_FEK_OFF[seg];
+#ifdef DG_AB_KNOBS
+    if ((c->eng_xw & 2) && seg > 0 && seg < nseg - 1)  // measured slower too (r06d)
+      hipLaunchKernelGGL(k_eng_fe_seg_xw<ENG_FEK_MID_SLOTS>, dim3(grid_for(cnt, ENG_XW_ITEMS)), dim3(ENG_XW_BLOCK), 0, s,
+                         so, sl, false, false, cnt, r0, consts, (const uint32_t*)f, n1inv, xbuf, flags, fb, st);
+    else if (c->eng_xw & 2)
+      hipLaunchKernelGGL(k_eng_fe_seg_xw<ENG_SLOTS_FE>, dim3(grid_for(cnt, ENG_XW_ITEMS)), dim3(ENG_XW_BLOCK), 0, s,
+                         so, sl, seg == 0, seg == nseg - 1, cnt, r0, consts, (const uint32_t*)f, n1inv, xbuf, flags, fb,
+                         st);
+    else
+#endif
+      hipLaunchKernelGGL(k_eng_fe_seg, dim3(blocks), dim3(ENG_BLOCK), 0, s, so, sl, seg == 0, seg == nseg - 1, cnt, r0,
+                         consts, (const uint32_t*)f, n1inv, xbuf, flags, fb, st);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_eng_fe_fb, dim3(ENG_FB_GRID), dim3(ENG_BLOCK), 0, s, cnt, r0, consts, f, n1inv, st,
+                     (const uint8_t*)flags, (const uint32_t*)fb);
+  HIP_TRY(hipGetLastError());
+  return DGPU_OK;
+}
+
+// One batch of pairing checks for eng_pairing_locked: item i passes when
+// e(P_i, h_i) e(-g1, sg_i) == 1 with P_i the key in `consts` or item i's in
+// pk_items (G2 signatures), or e(h_i, Q) e(-sg_i, g2) == 1 with Q fixed
+// (fixed_table: its line table) or item i's in g1form_keys (G1 signatures).
+struct pairing_job {
+  const uint32_t* consts = nullptr;  // engine block constants (a key's, or the context's without one)
+  size_t n = 0;                      // items
+  const uint32_t* h = nullptr;       // hash points, SoA over h_stride items ...
+  const uint32_t* sg = nullptr;      // signature points, SoA over n items
+  uint8_t* st = nullptr;             // ST_* per item: decode verdicts in, pairing verdicts out
+  size_t h_stride = 0;               // ... 0: n
+  const uint32_t* h_idx = nullptr;   // item i's hash point index (null: i)
+  const uint32_t* pk_items = nullptr;     // a G1 key per item (recovery)
+  const uint32_t* fixed_table = nullptr;  // G1 signatures: the key's fixed-Q line table
+  const lane_bufs* lanes = nullptr;       // the lane's engine scratch (null: the context's first)
+  bool sig_subgroup = false;              // the lines kernel checks the signatures' G2 membership
+  const uint32_t* g1form_keys = nullptr;  // G1 signatures: a G2 key per item (recovery)
+};
+
+// Per-round pairing checks on the lane-cooperative engine, chunk by chunk
+// (pairing_engine.cuh): lines -> Miller product + norm -> batch inversion ->
+// final exponentiation.  Decode verdicts in `st` stay final.
+int eng_pairing_locked(dgpu_ctx* c, const pairing_job& job, hipStream_t s) {
+  const uint32_t* const consts = job.consts;
+  const size_t n = job.n;
+  const uint32_t *const h = job.h, *const sg = job.sg;
+  uint8_t* const st = job.st;
+  const size_t h_stride = job.h_stride ? job.h_stride : n;
+  const uint32_t *const h_idx = job.h_idx, *const pk_items = job.pk_items, *const fixed_table = job.fixed_table;
+  const lane_bufs* const L = job.lanes;
+  const bool sig_subgroup = job.sig_subgroup;
+  const uint32_t* const g1form_keys = job.g1form_keys;
+  DevBuf* b_lines = L ? L->lines : &c->eng_lines;
+  DevBuf* b_f = L ? L->f : &c->eng_f;
+  DevBuf* b_n1 = L ? L->n1 : &c->eng_n1;
+  DevBuf* b_kb = L ? L->kb : &c->eng_kb;
+  const bool need_lines = !(fixed_table && c->fused_fixed);
+  // small calls: the Granger-Scott FE (one launch; the Karabina side's five
+  // chain / norm / batched-inversion / decompression rounds are latency there)
+  const bool fe_gs = c->fe_gs || n <= c->fe_gs_max;
+  int rc;
+  size_t cap = 0, cap_blk = 0;
+  bool retried = false;
+  for (;;) {
+    // equal chunks of at most eng_chunk items (whole 5-item blocks): no short tail launch
+    const size_t nchunks = (n + c->eng_chunk - 1) / c->eng_chunk;
+    cap = (n + nchunks - 1) / nchunks;
+    cap = std::min(n, (cap + ENG_ROUNDS_PER_BLOCK - 1) / ENG_ROUNDS_PER_BLOCK * ENG_ROUNDS_PER_BLOCK);
+    cap_blk = (cap + ENG_ROUNDS_PER_BLOCK - 1) / ENG_ROUNDS_PER_BLOCK;  // blocked layouts
+    // the Karabina planes are wave-blocked: whole blocks of 5 rounds (cap may be n, not a multiple of 5)
+    rc = fe_gs ? DGPU_OK : b_kb->ensure(cap_blk * ENG_ROUNDS_PER_BLOCK * ENG_KB_BYTES_PER_ROUND);
+    if (!rc && need_lines) rc = b_lines->ensure(cap_blk * (size_t)ENG_LINE_STEPS * FP_LIMBS * ENG_WAVE_WORDS * 4);
+    if (!rc) rc = b_f->ensure(cap_blk * 2 * FP_LIMBS * ENG_WAVE_WORDS * 4);
+    if (!rc) rc = b_n1->ensure(cap * FP_LIMBS * 4);
+    if (rc != DGPU_ENOMEM || c->eng_chunk <= ENG_CHUNK_MIN || cap <= ENG_CHUNK_MIN) break;
+    // HBM is shared (other contexts, torch): the chunk was sized from the free
+    // memory at dgpu_open; halve it for this context and retry (ADVICE r04).
+    // The buffers may still be read by this context's earlier work (its two
+    // streams and the call's stream); nothing else has to wait (ADVICE r05).
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream2));
+    for (DevBuf* b : {b_kb, b_lines, b_f, b_n1}) b->release();
+    c->eng_chunk = std::max(ENG_CHUNK_MIN, c->eng_chunk / 2);
+    ++c->chunk_retries;
+    retried = true;
+  }
+  if (rc) return rc;
+  if (retried) g_last_error.clear();  // the failed attempt's message is stale
+  // k_eng_inv's prefix products reuse the line buffer (or f, on the fused path)
+  uint32_t* lines = need_lines ? (uint32_t*)b_lines->p : nullptr;
+  uint32_t* f = (uint32_t*)b_f->p;
+  uint32_t* n1 = (uint32_t*)b_n1->p;
+  uint32_t* pre = need_lines ? lines : nullptr;
+  if (!pre) {
+    if ((rc = c->eng_lines.ensure(cap * FP_LIMBS * 4))) return rc;
+    pre = (uint32_t*)c->eng_lines.p;
+  }
+  for (size_t r0 = 0; r0 < n; r0 += cap) {
+    const size_t cnt = std::min(cap, n - r0);
+    const unsigned blocks = grid_for(cnt, ENG_ROUNDS_PER_BLOCK);
+    if (!need_lines) {  // on-G1, lines formed inside the Miller kernel
+      mark(c, s, "eng_miller");
+      hipLaunchKernelGGL(k_eng_miller_fixed, dim3(blocks), dim3(ENG_BLOCK), 0, s, n, r0, cnt, consts, h, sg,
+                         fixed_table, f, n1);
+      HIP_TRY(hipGetLastError());
+    } else {
+      if (g1form_keys) {  // G1-signature recovery: h and sg affine G1 points, pair 0's G2 point per item
+        mark(c, s, "eng_lines");
+        hipLaunchKernelGGL(k_lines_thr_g1, dim3(grid_for(2 * cnt, 256)), dim3(256), 0, s, n, r0, cnt, h, h_stride, h_idx,
+                           sg, g1form_keys, lines);
+      } else if (fixed_table) {  // on-G1: h and sg are affine G1 points, the G2 arguments fixed
+        mark(c, s, "eng_lines_fixed");
+        hipLaunchKernelGGL(k_eng_lines_fixed, dim3(blocks, ENG_LINE_STEPS), dim3(ENG_BLOCK), 0, s, n, r0, cnt, h, sg,
+                           fixed_table, lines);
+      } else {
+        mark(c, s, "eng_lines");
+        if (c->lines_thread && cnt >= c->thr_min && !pk_items && c->lines_wave)  // pair per wave: P in SGPRs
+          hipLaunchKernelGGL(k_lines_thr<true>, dim3(grid_for(2 * ((cnt + 63) / 64 * 64), 256)), dim3(256), 0, s, n, r0,
+                             cnt, h, h_stride, h_idx, sg, pk_items, consts, lines,
+                             sig_subgroup ? st : (uint8_t*)nullptr);
+        else if (c->lines_thread && cnt >= c->thr_min)
+          hipLaunchKernelGGL(k_lines_thr<false>, dim3(grid_for(2 * cnt, 256)), dim3(256), 0, s, n, r0, cnt, h, h_stride,
+                             h_idx, sg, pk_items, consts, lines, sig_subgroup ? st : (uint8_t*)nullptr);
+        else
+          hipLaunchKernelGGL(k_eng_lines, dim3(blocks), dim3(ENG_BLOCK), 0, s, n, r0, cnt, h, h_stride, h_idx, sg,
+                           pk_items, consts, lines, sig_subgroup ? st : (uint8_t*)nullptr, (uint32_t*)nullptr);
+      }
+      HIP_TRY(hipGetLastError());
+      mark(c, s, "eng_miller");
+#ifdef DG_AB_KNOBS
+      if (c->eng_xw & 1)  // no idle lanes, barrier-ordered: measured 8% slower (profiles/r06/r06d_engine_xw_ab.txt)
+        hipLaunchKernelGGL(k_eng_miller_xw, dim3(grid_for(cnt, ENG_XW_ITEMS)), dim3(ENG_XW_BLOCK), 0, s, cnt, consts,
+                           lines, f, n1);
+      else
+#endif
+        hipLaunchKernelGGL(k_eng_miller, dim3(blocks), dim3(ENG_BLOCK), 0, s, cnt, consts, lines, f, n1);
+      HIP_TRY(hipGetLastError());
+    }
+    const size_t inv_threads = std::max<size_t>(1, (cnt + 63) / 64);
+    mark(c, s, "eng_inv");
+    hipLaunchKernelGGL(k_eng_inv, dim3(grid_for(inv_threads, 256)), dim3(256), 0, s, cnt, r0, n1, pre, st);
+    HIP_TRY(hipGetLastError());
+    if (fe_gs) {
+      mark(c, s, "eng_fe");
+      hipLaunchKernelGGL(k_eng_fe, dim3(blocks), dim3(ENG_BLOCK), 0, s, cnt, r0, consts, f, n1, st);
+      HIP_TRY(hipGetLastError());
+    } else if ((rc = eng_fe_kb_locked(c, consts, cnt, cap_blk * ENG_ROUNDS_PER_BLOCK, r0, f, n1, (uint8_t*)b_kb->p,
+                                      st, s))) {
+      return rc;
+    }
+  }
+  return DGPU_OK;
+}
 
 // ---------------------------------------------------------------- RLC
 // The segment trees of one RLC batch (level l: P[l], S[l], sz[l] nodes).
@@ -511,35 +733,11 @@ struct rlc_geom {
 };
 inline rlc_geom rlc_geom_of(bool g1) { return g1 ? rlc_geom{true, G1A_WORDS, G1J_WORDS} : rlc_geom{false, G2A_WORDS, G2J_WORDS}; }
 
-// RLC phase 1: R_i = pre-cofactor H(m_i) (affine, in rlc_tree's tail),
-// sig_i decoded (+ subgroup, required before any combination: soundness --
-// both groups' cofactors have small prime factors, so a small-order component
-// would survive a random 64-bit combination with noticeable probability).
-// Asynchronous on s.
 // The SSWU stage of the G2 hash over 2n field elements u -> Jacobian points
-// in q: the fused k_h2c_sswu.  A/B build -DDG_SSWU_STAGED: five launches with
-// the two exponentiations on their own 90-VGPR kernel (kernels.cuh k_sswu_a;
-// `aux` = six free planes of FP_WORDS x n words) -- measured slower (r06i:
-// hash 151.0 vs 148.0 ms per 2M, RLC raw hash 62.7 vs 60.0), not shipped.
-hipError_t launch_sswu(size_t n, const uint32_t* u, uint32_t* q, const sswu_planes& aux, hipStream_t s) {
-  const unsigned B = 256, g = grid_for(2 * n, B);
-#ifndef DG_SSWU_STAGED
-  (void)aux;
-  hipLaunchKernelGGL(k_h2c_sswu, dim3(g), dim3(B), 0, s, n, u, q);
+// in q: the fused k_h2c_sswu.
+hipError_t launch_sswu(size_t n, const uint32_t* u, uint32_t* q, hipStream_t s) {
+  hipLaunchKernelGGL(k_h2c_sswu, dim3(grid_for(2 * n, 256)), dim3(256), 0, s, n, u, q);
   return hipGetLastError();
-#else
-  hipLaunchKernelGGL(k_sswu_a, dim3(g), dim3(B), 0, s, n, u, q, aux);
-  hipLaunchKernelGGL(k_fp_pow_planes<0>, dim3(g), dim3(B), 0, s, n, aux, 0);
-  hipLaunchKernelGGL(k_sswu_b, dim3(g), dim3(B), 0, s, n, u, q, aux);
-  hipLaunchKernelGGL(k_fp_pow_planes<1>, dim3(g), dim3(B), 0, s, n, aux, 2);
-  hipLaunchKernelGGL(k_sswu_c, dim3(g), dim3(B), 0, s, n, u, q, aux);
-  return hipGetLastError();
-#endif
-}
-sswu_planes planes_of(uint32_t* base, size_t n) {  // six consecutive FP planes
-  sswu_planes a;
-  for (int k = 0; k < 6; ++k) a.p[k] = base + (size_t)k * FP_WORDS * n;
-  return a;
 }
 
 size_t rlc_tree_points(size_t n) {
@@ -556,6 +754,11 @@ uint32_t* rlc_rpts(dgpu_ctx* c, size_t n, int jw) {
   return (uint32_t*)c->rlc_tree.p + 2 * rlc_tree_points(n) * jw;
 }
 
+// RLC phase 1: R_i = pre-cofactor H(m_i) (affine, in rlc_tree's tail),
+// sig_i decoded (+ subgroup, required before any combination: soundness --
+// both groups' cofactors have small prime factors, so a small-order component
+// would survive a random 64-bit combination with noticeable probability).
+// Asynchronous on s.
 int rlc_points_locked(dgpu_ctx* c, const verify_args& a, hipStream_t s) {
   const unsigned B = 256;
   const size_t n = a.n;
@@ -589,7 +792,7 @@ int rlc_points_locked(dgpu_ctx* c, const verify_args& a, hipStream_t s) {
     uint32_t* q = u + 4 * FP_WORDS * n;
     hipLaunchKernelGGL(k_h2c_field, dim3(grid_for(n, B)), dim3(B), 0, s, n, a.m, u);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(launch_sswu(n, u, q, planes_of(rpts, n), s));  // rpts is free until k_h2c_sum
+    HIP_TRY(launch_sswu(n, u, q, s));
     hipLaunchKernelGGL(k_h2c_sum, dim3(grid_for(n, B)), dim3(B), 0, s, n, (const uint32_t*)q, rpts);
     HIP_TRY(hipGetLastError());
   }
@@ -763,8 +966,14 @@ int rlc_check_locked(dgpu_ctx* c, const key_entry* key, const std::vector<uint32
     hipLaunchKernelGGL(k_rlc_prep<G2Ops>, dim3(grid_for(m, 64)), dim3(64), 0, s, m, d_idx, n_level, P_lvl, S_lvl, ch,
                        cs, cst);
   HIP_TRY(hipGetLastError());
-  if ((rc = eng_pairing_locked(c, (const uint32_t*)key->consts.p, m, ch, cs, cst, s, 0, nullptr, nullptr,
-                               G.g1 ? (const uint32_t*)key->table.p : nullptr)))
+  if ((rc = eng_pairing_locked(c,
+                               {.consts = (const uint32_t*)key->consts.p,
+                                .n = m,
+                                .h = ch,
+                                .sg = cs,
+                                .st = cst,
+                                .fixed_table = G.g1 ? (const uint32_t*)key->table.p : nullptr},
+                               s)))
     return rc;
   mark(c, s, "rlc_bisection");
   hipLaunchKernelGGL(k_rlc_fail, dim3(grid_for(m, B)), dim3(B), 0, s, m, cst, d_fail);
@@ -926,190 +1135,6 @@ int rlc_resolve_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a, 
   return rlc_descend_locked(c, key, T, s, true);
 }
 
-// Karabina final exponentiation of one chunk (pairing_engine.cuh, DESIGN.md
-// 2b): segment 0 (easy part), then per exponentiation by |x| the compressed
-// chain, its six stored values' norms, the batched inversion of their
-// products (divsteps, fp.cuh fp_inv), the decompression, and the next 12-lane
-// segment (the split at the inversion -- parts formed at the chain's snaps,
-// one thread per round inverting and decompressing -- measured slower, r04j,
-// and removed in round 6); last, the Granger-Scott kernel for the listed
-// blocks with a flagged item.  capb: the chunk capacity
-// rounded up to whole blocks of 5 rounds (>= cnt); kb: ENG_KB_BYTES_PER_ROUND
-// x capb bytes.
-int eng_fe_kb_locked(dgpu_ctx* c, const uint32_t* consts, size_t cnt, size_t capb, size_t r0, uint32_t* f,
-                     const uint32_t* n1inv, uint8_t* kb, uint8_t* st, hipStream_t s) {
-  if (capb % ENG_ROUNDS_PER_BLOCK || cnt > capb) return set_err(DGPU_EINVAL, "karabina FE: bad chunk capacity");
-  uint32_t* xbuf = (uint32_t*)kb;  // [capb / 5 blocks][ENG_KB_PLANES][limb][60]
-  uint32_t* pbuf = xbuf + ENG_KB_XWORDS * capb;
-  uint32_t* pre = pbuf + (size_t)FP_LIMBS * capb;
-  uint32_t* ebuf = pre + (size_t)FP_LIMBS * capb;
-  uint32_t* fb = ebuf + (size_t)ENG_KB_NSNAP * FP_LIMBS * capb;
-  uint8_t* flags = (uint8_t*)(fb + capb);
-  const unsigned blocks = grid_for(cnt, ENG_ROUNDS_PER_BLOCK);
-  const size_t inv_threads = std::max<size_t>(1, (cnt + c->kb_inv_chain - 1) / c->kb_inv_chain);
-  constexpr int nseg = (int)(sizeof(ENG_PROG_FEK_OFF) / sizeof(ENG_PROG_FEK_OFF[0])) - 1;
-  static_assert(nseg == 6, "segment 0 + one per exponentiation by |x|");
-  for (int seg = 0; seg < nseg; ++seg) {
-    if (seg > 0) {
-      mark(c, s, "eng_fe_chain");
-      const bool kb_thread = c->kb_thread && cnt >= c->thr_min;
-      const bool norm_pre = kb_thread && c->kb_norm_chain;
-      if (norm_pre && c->kb_pair)  // two lanes per round
-        hipLaunchKernelGGL(k_kb_chain_pair<true>, dim3(grid_for(2 * cnt, 256)), dim3(256), 0, s, cnt, xbuf, ebuf);
-      else if (norm_pre)
-        hipLaunchKernelGGL(k_kb_chain_thr<true>, dim3(grid_for(cnt, 256)), dim3(256), 0, s, cnt, xbuf, ebuf);
-      else if (kb_thread)
-        hipLaunchKernelGGL(k_kb_chain_thr<false>, dim3(grid_for(cnt, 256)), dim3(256), 0, s, cnt, xbuf, nullptr);
-      else
-        hipLaunchKernelGGL(k_eng_kb_chain, dim3(grid_for(cnt, 8)), dim3(64), 0, s, cnt, xbuf);
-      HIP_TRY(hipGetLastError());
-      mark(c, s, "eng_fe_kbinv");
-      if (norm_pre)
-        hipLaunchKernelGGL(k_eng_kb_norm<true>, dim3(grid_for(cnt, 256)), dim3(256), 0, s, cnt, r0,
-                           (const uint32_t*)xbuf, pbuf, ebuf, flags, (const uint8_t*)st, c->kb_test_flag);
-      else
-        hipLaunchKernelGGL(k_eng_kb_norm<false>, dim3(grid_for(cnt, 256)), dim3(256), 0, s, cnt, r0,
-                           (const uint32_t*)xbuf, pbuf, ebuf, flags, (const uint8_t*)st, c->kb_test_flag);
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(k_eng_inv, dim3(grid_for(inv_threads, 256)), dim3(256), 0, s, cnt, r0, pbuf, pre, st);
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(k_eng_kb_dec, dim3(grid_for((size_t)ENG_KB_NSNAP * cnt, 256)), dim3(256), 0, s, cnt, xbuf,
-                         (const uint32_t*)pbuf, (const uint32_t*)ebuf, (const uint8_t*)flags);
-      HIP_TRY(hipGetLastError());
-    }
-    mark(c, s, "eng_fe");
-    const int so = ENG_PROG_FEK_OFF[seg], sl = ENG_PROG_FEK_OFF[seg + 1] - ENG_PROG_FEK_OFF[seg];
-#ifdef DG_AB_KNOBS
-    if ((c->eng_xw & 2) && seg > 0 && seg < nseg - 1)  // measured slower too (r06d)
-      hipLaunchKernelGGL(k_eng_fe_seg_xw<ENG_FEK_MID_SLOTS>, dim3(grid_for(cnt, ENG_XW_ITEMS)), dim3(ENG_XW_BLOCK), 0, s,
-                         so, sl, false, false, cnt, r0, consts, (const uint32_t*)f, n1inv, xbuf, flags, fb, st);
-    else if (c->eng_xw & 2)
-      hipLaunchKernelGGL(k_eng_fe_seg_xw<ENG_SLOTS_FE>, dim3(grid_for(cnt, ENG_XW_ITEMS)), dim3(ENG_XW_BLOCK), 0, s,
-                         so, sl, seg == 0, seg == nseg - 1, cnt, r0, consts, (const uint32_t*)f, n1inv, xbuf, flags, fb,
-                         st);
-    else
-#endif
-      hipLaunchKernelGGL(k_eng_fe_seg, dim3(blocks), dim3(ENG_BLOCK), 0, s, so, sl, seg == 0, seg == nseg - 1, cnt, r0,
-                         consts, (const uint32_t*)f, n1inv, xbuf, flags, fb, st);
-    HIP_TRY(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_eng_fe_fb, dim3(ENG_FB_GRID), dim3(ENG_BLOCK), 0, s, cnt, r0, consts, f, n1inv, st,
-                     (const uint8_t*)flags, (const uint32_t*)fb);
-  HIP_TRY(hipGetLastError());
-  return DGPU_OK;
-}
-
-// Per-round pairing checks on the lane-cooperative engine, chunk by chunk
-// (pairing_engine.cuh): lines -> Miller product + norm -> batch inversion ->
-// final exponentiation.  Decode verdicts in `st` stay final.
-int eng_pairing_locked(dgpu_ctx* c, const uint32_t* consts, size_t n, const uint32_t* h, const uint32_t* sg,
-                       uint8_t* st, hipStream_t s, size_t h_stride, const uint32_t* h_idx, const uint32_t* pk_items,
-                       const uint32_t* fixed_table, const lane_bufs* L, bool sig_subgroup,
-                       const uint32_t* g1form_keys) {
-  if (!h_stride) h_stride = n;
-  DevBuf* b_lines = L ? L->lines : &c->eng_lines;
-  DevBuf* b_f = L ? L->f : &c->eng_f;
-  DevBuf* b_n1 = L ? L->n1 : &c->eng_n1;
-  DevBuf* b_kb = L ? L->kb : &c->eng_kb;
-  const bool need_lines = !(fixed_table && c->fused_fixed);
-  // small calls: the Granger-Scott FE (one launch; the Karabina side's five
-  // chain / norm / batched-inversion / decompression rounds are latency there)
-  const bool fe_gs = c->fe_gs || n <= c->fe_gs_max;
-  int rc;
-  size_t cap = 0, cap_blk = 0;
-  bool retried = false;
-  for (;;) {
-    // equal chunks of at most eng_chunk items (whole 5-item blocks): no short tail launch
-    const size_t nchunks = (n + c->eng_chunk - 1) / c->eng_chunk;
-    cap = (n + nchunks - 1) / nchunks;
-    cap = std::min(n, (cap + ENG_ROUNDS_PER_BLOCK - 1) / ENG_ROUNDS_PER_BLOCK * ENG_ROUNDS_PER_BLOCK);
-    cap_blk = (cap + ENG_ROUNDS_PER_BLOCK - 1) / ENG_ROUNDS_PER_BLOCK;  // blocked layouts
-    // the Karabina planes are wave-blocked: whole blocks of 5 rounds (cap may be n, not a multiple of 5)
-    rc = fe_gs ? DGPU_OK : b_kb->ensure(cap_blk * ENG_ROUNDS_PER_BLOCK * ENG_KB_BYTES_PER_ROUND);
-    if (!rc && need_lines) rc = b_lines->ensure(cap_blk * (size_t)ENG_LINE_STEPS * FP_LIMBS * ENG_WAVE_WORDS * 4);
-    if (!rc) rc = b_f->ensure(cap_blk * 2 * FP_LIMBS * ENG_WAVE_WORDS * 4);
-    if (!rc) rc = b_n1->ensure(cap * FP_LIMBS * 4);
-    if (rc != DGPU_ENOMEM || c->eng_chunk <= ENG_CHUNK_MIN || cap <= ENG_CHUNK_MIN) break;
-    // HBM is shared (other contexts, torch): the chunk was sized from the free
-    // memory at dgpu_open; halve it for this context and retry (ADVICE r04).
-    // The buffers may still be read by this context's earlier work (its two
-    // streams and the call's stream); nothing else has to wait (ADVICE r05).
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream2));
-    for (DevBuf* b : {b_kb, b_lines, b_f, b_n1}) b->release();
-    c->eng_chunk = std::max(ENG_CHUNK_MIN, c->eng_chunk / 2);
-    ++c->chunk_retries;
-    retried = true;
-  }
-  if (rc) return rc;
-  if (retried) g_last_error.clear();  // the failed attempt's message is stale
-  // k_eng_inv's prefix products reuse the line buffer (or f, on the fused path)
-  uint32_t* lines = need_lines ? (uint32_t*)b_lines->p : nullptr;
-  uint32_t* f = (uint32_t*)b_f->p;
-  uint32_t* n1 = (uint32_t*)b_n1->p;
-  uint32_t* pre = need_lines ? lines : nullptr;
-  if (!pre) {
-    if ((rc = c->eng_lines.ensure(cap * FP_LIMBS * 4))) return rc;
-    pre = (uint32_t*)c->eng_lines.p;
-  }
-  for (size_t r0 = 0; r0 < n; r0 += cap) {
-    const size_t cnt = std::min(cap, n - r0);
-    const unsigned blocks = grid_for(cnt, ENG_ROUNDS_PER_BLOCK);
-    if (!need_lines) {  // on-G1, lines formed inside the Miller kernel
-      mark(c, s, "eng_miller");
-      hipLaunchKernelGGL(k_eng_miller_fixed, dim3(blocks), dim3(ENG_BLOCK), 0, s, n, r0, cnt, consts, h, sg,
-                         fixed_table, f, n1);
-      HIP_TRY(hipGetLastError());
-    } else {
-      if (g1form_keys) {  // G1-signature recovery: h and sg affine G1 points, pair 0's G2 point per item
-        mark(c, s, "eng_lines");
-        hipLaunchKernelGGL(k_lines_thr_g1, dim3(grid_for(2 * cnt, 256)), dim3(256), 0, s, n, r0, cnt, h, h_stride, h_idx,
-                           sg, g1form_keys, lines);
-      } else if (fixed_table) {  // on-G1: h and sg are affine G1 points, the G2 arguments fixed
-        mark(c, s, "eng_lines_fixed");
-        hipLaunchKernelGGL(k_eng_lines_fixed, dim3(blocks, ENG_LINE_STEPS), dim3(ENG_BLOCK), 0, s, n, r0, cnt, h, sg,
-                           fixed_table, lines);
-      } else {
-        mark(c, s, "eng_lines");
-        if (c->lines_thread && cnt >= c->thr_min && !pk_items && c->lines_wave)  // pair per wave: P in SGPRs
-          hipLaunchKernelGGL(k_lines_thr<true>, dim3(grid_for(2 * ((cnt + 63) / 64 * 64), 256)), dim3(256), 0, s, n, r0,
-                             cnt, h, h_stride, h_idx, sg, pk_items, consts, lines,
-                             sig_subgroup ? st : (uint8_t*)nullptr);
-        else if (c->lines_thread && cnt >= c->thr_min)
-          hipLaunchKernelGGL(k_lines_thr<false>, dim3(grid_for(2 * cnt, 256)), dim3(256), 0, s, n, r0, cnt, h, h_stride,
-                             h_idx, sg, pk_items, consts, lines, sig_subgroup ? st : (uint8_t*)nullptr);
-        else
-          hipLaunchKernelGGL(k_eng_lines, dim3(blocks), dim3(ENG_BLOCK), 0, s, n, r0, cnt, h, h_stride, h_idx, sg,
-                           pk_items, consts, lines, sig_subgroup ? st : (uint8_t*)nullptr, (uint32_t*)nullptr);
-      }
-      HIP_TRY(hipGetLastError());
-      mark(c, s, "eng_miller");
-#ifdef DG_AB_KNOBS
-      if (c->eng_xw & 1)  // no idle lanes, barrier-ordered: measured 8% slower (profiles/r06/r06d_engine_xw_ab.txt)
-        hipLaunchKernelGGL(k_eng_miller_xw, dim3(grid_for(cnt, ENG_XW_ITEMS)), dim3(ENG_XW_BLOCK), 0, s, cnt, consts,
-                           lines, f, n1);
-      else
-#endif
-        hipLaunchKernelGGL(k_eng_miller, dim3(blocks), dim3(ENG_BLOCK), 0, s, cnt, consts, lines, f, n1);
-      HIP_TRY(hipGetLastError());
-    }
-    const size_t inv_threads = std::max<size_t>(1, (cnt + 63) / 64);
-    mark(c, s, "eng_inv");
-    hipLaunchKernelGGL(k_eng_inv, dim3(grid_for(inv_threads, 256)), dim3(256), 0, s, cnt, r0, n1, pre, st);
-    HIP_TRY(hipGetLastError());
-    if (fe_gs) {
-      mark(c, s, "eng_fe");
-      hipLaunchKernelGGL(k_eng_fe, dim3(blocks), dim3(ENG_BLOCK), 0, s, cnt, r0, consts, f, n1, st);
-      HIP_TRY(hipGetLastError());
-    } else if ((rc = eng_fe_kb_locked(c, consts, cnt, cap_blk * ENG_ROUNDS_PER_BLOCK, r0, f, n1, (uint8_t*)b_kb->p,
-                                      st, s))) {
-      return rc;
-    }
-  }
-  return DGPU_OK;
-}
-
 // Signatures on G1: H(m) in G1 (+ batch affine), G1 signature decode, then
 // the engine's Miller (fixed-Q lines) / inversion / final-exponentiation kernels.
 int verify_g1_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a, uint8_t* st, hipStream_t s) {
@@ -1149,8 +1174,14 @@ int verify_g1_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a, ui
                        sg, st);
     HIP_TRY(hipGetLastError());
   }
-  return eng_pairing_locked(c, (const uint32_t*)key->consts.p, n, h, sg, st, s, 0, nullptr, nullptr,
-                            (const uint32_t*)key->table.p);
+  return eng_pairing_locked(c,
+                            {.consts = (const uint32_t*)key->consts.p,
+                             .n = n,
+                             .h = h,
+                             .sg = sg,
+                             .st = st,
+                             .fixed_table = (const uint32_t*)key->table.p},
+                            s);
 }
 
 // host-record staging (verify_status_host_locked): the kernels of a slice
@@ -1208,12 +1239,7 @@ int g2_lane_hash_locked(dgpu_ctx* c, const lane_bufs& L, size_t n, const msg_src
   mark(c, s, "hash_to_g2");
   hipLaunchKernelGGL(k_h2c_field, dim3(grid_for(n, B)), dim3(B), 0, s, n, m, u);
   HIP_TRY(hipGetLastError());
-  {  // the SSWU's planes: h_pts and h_z, free until the cofactor step writes them
-    sswu_planes aux;
-    for (int k = 0; k < 4; ++k) aux.p[k] = h + (size_t)k * FP_WORDS * n;
-    for (int k = 0; k < 2; ++k) aux.p[4 + k] = (uint32_t*)L.h_z->p + (size_t)k * FP_WORDS * n;
-    HIP_TRY(launch_sswu(n, u, q, aux, s));
-  }
+  HIP_TRY(launch_sswu(n, u, q, s));
   if (cof_engine) {
     const unsigned blocks = cof_blocks;
     uint32_t* w = (uint32_t*)c->cof_tmp.p;
@@ -1367,15 +1393,21 @@ int verify_status_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a
       (rc = g2_lane_hash_locked(c, L0, n0, a.m, a.sigs, a.sig_stride, a.sig_len, st, s, s_dec, consts, stg, 0)))
     return rc;
   const bool sub = !c->decode_subgroup;
-  if (!two)
-    return eng_pairing_locked(c, consts, n, (const uint32_t*)c->h_pts.p, (const uint32_t*)c->sig_pts.p, st, s, 0,
-                              nullptr, nullptr, nullptr, &L0, sub);
+  // one slice of the batch on one lane's buffers
+  auto slice_job = [&](const lane_bufs& L, size_t cnt, uint8_t* sst) {
+    return pairing_job{.consts = consts,
+                       .n = cnt,
+                       .h = (const uint32_t*)L.h_pts->p,
+                       .sg = (const uint32_t*)L.sig_pts->p,
+                       .st = sst,
+                       .lanes = &L,
+                       .sig_subgroup = sub};
+  };
+  if (!two) return eng_pairing_locked(c, slice_job(L0, n, st), s);
   hipStream_t s2 = c->stream2;
   HIP_TRY(hipEventRecord(c->lane_ev[0], s));
   HIP_TRY(hipStreamWaitEvent(s2, c->lane_ev[0], 0));
-  if ((rc = eng_pairing_locked(c, consts, n0, (const uint32_t*)L0.h_pts->p, (const uint32_t*)L0.sig_pts->p, st, s, 0,
-                               nullptr, nullptr, nullptr, &L0, sub)))
-    return rc;
+  if ((rc = eng_pairing_locked(c, slice_job(L0, n0, st), s))) return rc;
   // the remaining slices alternate between the lanes (stream order keeps each
   // lane's buffers in use by one slice at a time), so a slice's hash runs
   // beside the other lane's engine chunks (DGPU_LANE_SLICES, default 2)
@@ -1389,10 +1421,7 @@ int verify_status_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a
         (rc = g2_lane_hash_locked(c, *LL[ln], nk, src_slice(a.m, off), a.sigs + off * a.sig_stride, a.sig_stride,
                                   a.sig_len + off, st + off, ss[ln], nullptr, nullptr, stg, k)))
       return rc;
-    if ((rc = eng_pairing_locked(c, consts, nk, (const uint32_t*)LL[ln]->h_pts->p,
-                                 (const uint32_t*)LL[ln]->sig_pts->p, st + off, ss[ln], 0, nullptr, nullptr, nullptr,
-                                 LL[ln], sub)))
-      return rc;
+    if ((rc = eng_pairing_locked(c, slice_job(*LL[ln], nk, st + off), ss[ln]))) return rc;
   }
   HIP_TRY(hipEventRecord(c->lane_ev[1], s2));
   HIP_TRY(hipStreamWaitEvent(s, c->lane_ev[1], 0));
@@ -1900,30 +1929,9 @@ void dgpu_close(dgpu_ctx* c) {
     if (c->ring_ev[k]) hipEventDestroy(c->ring_ev[k]);
     if (c->ring[k]) hipHostFree(c->ring[k]);
   }
-  for (key_entry& k : c->keys) {
-    k.consts.release();
-    k.table.release();
-  }
-  c->grp_key.consts.release();
-  c->grp_key.table.release();
-  for (DevBuf* b : {&c->grp_stage, &c->rec_slots,
-                    &c->grp_commits, &c->grp_table, &c->rec_msgs, &c->rec_parts, &c->rec_plen, &c->rec_hidx,
-                    &c->rec_pk, &c->rec_idx, &c->rec_lam, &c->rec_out, &c->rec_ok, &c->rec_pts, &c->rec_vpk,
-                    &c->rec_st, &c->rec_sel, &c->rec_part, &c->grp_wtab, &c->rec_cls, &c->rec_x_list,
-                    &c->rec_x_msgs, &c->rec_x_parts, &c->rec_x_plen, &c->rec_x_out, &c->rec_x_ok, &c->rec_x_st,
-                    &c->rec_tab, &c->rec_tabz, &c->rec_tabpre, &c->rec_tab_rows,
-                    &c->eng_consts, &c->eng_lines, &c->eng_f, &c->eng_n1, &c->eng_kb, &c->l2_kb,
-                    &c->rlc_tree, &c->rlc_idx, &c->rlc_fail, &c->rlc_h, &c->rlc_s, &c->rlc_st, &c->rlc_root,
-                    &c->msm_aos, &c->msm_flags, &c->msm_counts, &c->msm_list, &c->msm_buckets, &c->msm_runs, &c->msm_part, &c->cof_tmp,
-                    &c->msm_root,
-                    &c->h_pts, &c->sig_pts, &c->status, &c->h_z, &c->h_pre, &c->h_tmp, &c->in_rounds, &c->in_sigs,
-                    &c->in_sig_len, &c->in_prev, &c->in_prev_len, &c->in_msgs, &c->in_msg_len, &c->out_bits,
-                    &c->out_reason, &c->misc, &c->l2_h_pts, &c->l2_sig_pts, &c->l2_h_z, &c->l2_h_pre, &c->l2_h_tmp,
-                    &c->l2_lines, &c->l2_f, &c->l2_n1})
-    b->release();
   if (c->stream2) hipStreamDestroy(c->stream2);
   if (c->stream) hipStreamDestroy(c->stream);
-  delete c;
+  delete c;  // the device buffers go with the context: every stream that used them has been drained
 }
 
 int dgpu_set_pubkey(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t len) {
@@ -2409,19 +2417,11 @@ int dgpu_make_chain(dgpu_ctx* c, int scheme, const uint8_t* sk_be32, size_t n_se
   hipStream_t s = c->stream;
   stream_order ord(c, s);
   int rc;
-  DevBuf d_first, d_prev, d_plen, d_sigs;
-  auto cleanup = [&]() {
-    hipStreamSynchronize(s);
-    d_first.release();
-    d_prev.release();
-    d_plen.release();
-    d_sigs.release();
-  };
+  stream_scratch<4> tmp(s);
+  DevBuf &d_first = tmp.b[0], &d_prev = tmp.b[1], &d_plen = tmp.b[2], &d_sigs = tmp.b[3];
   if ((rc = d_first.ensure(n_seg * 8)) || (rc = d_prev.ensure(n_seg * 96)) || (rc = d_plen.ensure(n_seg * 4)) ||
-      (rc = d_sigs.ensure(n_seg * seg_len * 96))) {
-    cleanup();
+      (rc = d_sigs.ensure(n_seg * seg_len * 96)))
     return rc;
-  }
   std::vector<uint8_t> pv(n_seg * 96, 0);
   std::vector<uint32_t> pl(n_seg, 0);
   if (chained) {
@@ -2430,7 +2430,6 @@ int dgpu_make_chain(dgpu_ctx* c, int scheme, const uint8_t* sk_be32, size_t n_se
       memcpy(&pv[i * 96], seed_prev + i * 96, pl[i]);
     }
   }
-  int ret = DGPU_OK;
   hipError_t e = hipMemcpyAsync(d_first.p, first_round, n_seg * 8, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(d_prev.p, pv.data(), n_seg * 96, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(d_plen.p, pl.data(), n_seg * 4, hipMemcpyHostToDevice, s);
@@ -2450,573 +2449,11 @@ int dgpu_make_chain(dgpu_ctx* c, int scheme, const uint8_t* sk_be32, size_t n_se
   }
   if (e == hipSuccess) e = hipMemcpyAsync(sigs_out, d_sigs.p, n_seg * seg_len * 96, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) ret = set_err(DGPU_EDEVICE, "make_chain: %s", hipGetErrorString(e));
-  cleanup();
-  return ret;
-}
-
-int dgpu_set_group(dgpu_ctx* c, int t, int n, const uint8_t* commits48) {
-  if (!c || !commits48) return set_err(DGPU_EINVAL, "null argument");
-  if (t < 1 || t > RECOVER_MAX_T) return set_err(DGPU_EINVAL, "threshold t=%d outside [1, %d]", t, RECOVER_MAX_T);
-  if (n < t || n > 65536) return set_err(DGPU_EINVAL, "group size n=%d invalid for t=%d", n, t);
-  std::lock_guard<std::mutex> lk(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  stream_order ord(c, s);
-  // the group's tables may still be read by an earlier asynchronous recovery
-  HIP_TRY(hipEventSynchronize(c->done));
-  int rc;
-  if ((rc = c->misc.ensure(t * 48 + t * 4))) return rc;
-  if ((rc = c->grp_commits.ensure((size_t)t * 2 * FP_LIMBS * 4))) return rc;
-  if ((rc = c->grp_table.ensure((size_t)n * 2 * FP_LIMBS * 4))) return rc;
-  uint8_t* d_in = (uint8_t*)c->misc.p;
-  int* d_rc = (int*)(d_in + t * 48);
-  HIP_TRY(hipMemcpyAsync(d_in, commits48, (size_t)t * 48, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_decode_commits, dim3(grid_for(t, 64)), dim3(64), 0, s, t, d_in, (uint32_t*)c->grp_commits.p, d_rc);
-  HIP_TRY(hipGetLastError());
-  std::vector<int> hrc(t);
-  HIP_TRY(hipMemcpyAsync(hrc.data(), d_rc, t * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  c->grp_t = 0;
-  for (int j = 0; j < t; ++j)
-    if (hrc[j] != DEC_OK) return set_err(DGPU_EINVAL, "group commitment %d rejected (decode code %d)", j, hrc[j]);
-  hipLaunchKernelGGL(k_pubpoly_table, dim3(grid_for(n, 64)), dim3(64), 0, s, n, t, (const uint32_t*)c->grp_commits.p,
-                     (uint32_t*)c->grp_table.p);
-  HIP_TRY(hipGetLastError());
-  if ((rc = c->grp_wtab.ensure((size_t)n * 8 * REC_WTAB_WORDS * 4))) return rc;
-  hipLaunchKernelGGL(k_pubpoly_wtable, dim3(grid_for(8 * (size_t)n, 64)), dim3(64), 0, s, n,
-                     (const uint32_t*)c->grp_table.p, (uint32_t*)c->grp_wtab.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(s));
-  c->grp_t = t;
-  c->grp_n = n;
-  c->grp_scheme = DGPU_SCHEME_CHAINED;
-  c->grp_g1 = false;
-  return DGPU_OK;
-}
-
-// A G1-signature group: t compressed G2 commitments.  Everything is decoded
-// and checked in staging buffers first, so a rejected call leaves the
-// installed group (of either kind) as it was.
-static int set_group_g1_locked(dgpu_ctx* c, int scheme, int t, int n, const uint8_t* commits96) {
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  stream_order ord(c, s);
-  // the group's tables may still be read by an earlier asynchronous recovery
-  HIP_TRY(hipEventSynchronize(c->done));
-  int rc;
-  const size_t cw = (size_t)t * G2A_WORDS * 4;
-  if ((rc = c->misc.ensure(t * 96 + t * 4)) || (rc = c->grp_stage.ensure(cw))) return rc;
-  uint8_t* d_in = (uint8_t*)c->misc.p;
-  int* d_rc = (int*)(d_in + t * 96);
-  HIP_TRY(hipMemcpyAsync(d_in, commits96, (size_t)t * 96, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_decode_commits_g2, dim3(grid_for(t, 64)), dim3(64), 0, s, t, d_in, (uint32_t*)c->grp_stage.p,
-                     d_rc);
-  HIP_TRY(hipGetLastError());
-  std::vector<int> hrc(t);
-  HIP_TRY(hipMemcpyAsync(hrc.data(), d_rc, t * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  for (int j = 0; j < t; ++j)
-    if (hrc[j] != DEC_OK) return set_err(DGPU_EINVAL, "group commitment %d rejected (decode code %d)", j, hrc[j]);
-  // VerifyRecovered's key C_0: decoded with its fixed-Q line table as
-  // dgpu_set_pubkey does, into the group's own entry (the key cache keeps its 8)
-  key_entry fresh;
-  if ((rc = decode_g2_key_locked(c, &fresh, commits96))) {
-    fresh.consts.release();
-    fresh.table.release();
-    return rc;
-  }
-  c->grp_t = 0;
-  c->grp_key.consts.release();
-  c->grp_key.table.release();
-  c->grp_key.consts = fresh.consts;
-  c->grp_key.table = fresh.table;
-  c->grp_key.used = true;
-  c->grp_key.g2key = true;
-  if ((rc = c->grp_commits.ensure(cw)) || (rc = c->grp_table.ensure((size_t)n * G2A_WORDS * 4)) ||
-      (rc = c->grp_wtab.ensure((size_t)n * 8 * G2A_WORDS * 4)))
-    return rc;
-  HIP_TRY(hipMemcpyAsync(c->grp_commits.p, c->grp_stage.p, cw, hipMemcpyDeviceToDevice, s));
-  hipLaunchKernelGGL(k_pubpoly_table_g2, dim3(grid_for(n, 64)), dim3(64), 0, s, n, t,
-                     (const uint32_t*)c->grp_commits.p, (uint32_t*)c->grp_table.p);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_pubpoly_wtable_g2, dim3(grid_for(8 * (size_t)n, 64)), dim3(64), 0, s, n,
-                     (const uint32_t*)c->grp_table.p, (uint32_t*)c->grp_wtab.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(s));
-  c->grp_t = t;
-  c->grp_n = n;
-  c->grp_scheme = scheme;
-  c->grp_g1 = true;
-  return DGPU_OK;
-}
-
-int dgpu_set_group_scheme(dgpu_ctx* c, int scheme, int t, int n, const uint8_t* commits, size_t commit_len) {
-  if (!c || !commits) return set_err(DGPU_EINVAL, "null argument");
-  if (!scheme_known(scheme)) return set_err(DGPU_EINVAL, "bad scheme %d", scheme);
-  const size_t want = sig_on_g1(scheme) ? 96 : 48;
-  if (commit_len != want)
-    return set_err(DGPU_EINVAL, "commitments of scheme %d are %zu bytes (compressed %s), got %zu", scheme, want,
-                   sig_on_g1(scheme) ? "G2" : "G1", commit_len);
-  if (!sig_on_g1(scheme)) return dgpu_set_group(c, t, n, commits);
-  if (t < 1 || t > RECOVER_MAX_T) return set_err(DGPU_EINVAL, "threshold t=%d outside [1, %d]", t, RECOVER_MAX_T);
-  if (n < t || n > 65536) return set_err(DGPU_EINVAL, "group size n=%d invalid for t=%d", n, t);
-  std::lock_guard<std::mutex> lk(c->mu);
-  return set_group_g1_locked(c, scheme, t, n, commits);
-}
-
-}  // extern "C"
-
-// The G1 recovery MSM's launches (recover_g1.cuh): shared affine window tables
-// [1..8] sig_j, then `slices` threads per round of mixed-addition windows.
-static int recover_msm_g1_locked(dgpu_ctx* c, size_t n_rounds, int t, const uint8_t* d_ok, const uint32_t* sel,
-                                 const uint64_t* dig, const uint32_t* sg, size_t items, uint32_t* part, int slices,
-                                 hipStream_t s) {
-  const size_t ne = n_rounds * (size_t)t * 8;
-  int rc;
-  if ((rc = c->rec_tab.ensure(ne * 2 * FP_WORDS * 4)) || (rc = c->rec_tabz.ensure(ne * FP_WORDS * 4)) ||
-      (rc = c->rec_tabpre.ensure(ne * FP_WORDS * 4)))
-    return rc;
-  uint32_t* tab = (uint32_t*)c->rec_tab.p;
-  hipLaunchKernelGGL(k_recover_tables_g1, dim3(grid_for(n_rounds * (size_t)t, 256)), dim3(256), 0, s, n_rounds, t, d_ok,
-                     sel, sg, items, tab, (uint32_t*)c->rec_tabz.p);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_g1_batch_affine, dim3(grid_for((ne + 15) / 16, 256)), dim3(256), 0, s, ne, tab,
-                     (const uint32_t*)c->rec_tabz.p, (uint32_t*)c->rec_tabpre.p);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_recover_msm_g1, dim3(grid_for((size_t)slices * n_rounds, 256)), dim3(256), 0, s, n_rounds, t,
-                     d_ok, dig, (const uint32_t*)tab, part, slices);
-  HIP_TRY(hipGetLastError());
-  return DGPU_OK;
-}
-
-// Exact per-partial recovery over device buffers: VerifyPartial of every
-// partial, selection, Lagrange + MSM, VerifyRecovered -- the reference's
-// walk, pairing by pairing.  d_ok: one byte per round (1 = recovered and
-// VerifyRecovered passed); d_status (optional): ST_* of every partial item.
-static int recover_exact_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_msgs, size_t m,
-                                 const uint8_t* d_parts, size_t stride, const uint32_t* d_plen, uint8_t* d_out,
-                                 uint8_t* d_ok, uint8_t* d_status, hipStream_t s) {
-  if (!c->grp_t) return set_err(DGPU_ENOKEY, "no threshold group installed (dgpu_set_group)");
-  const size_t items = n_rounds * m;
-  if (items > 0xFFFFFFFFull) return set_err(DGPU_EINVAL, "batch too large (%zu items)", items);
-  const uint32_t* consts = (const uint32_t*)c->eng_consts.p;
-  int rc;
-  if ((rc = c->rec_hidx.ensure(items * 4))) return rc;
-  const bool g1 = c->grp_g1;  // G1 signatures: per-item G2 share keys (recover_g1.cuh)
-  const int g1dst = c->grp_scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0;
-  if ((rc = c->rec_pk.ensure(items * (g1 ? (size_t)G2A_WORDS : 2 * FP_LIMBS) * 4))) return rc;
-  if ((rc = c->rec_idx.ensure(items * 4))) return rc;
-  if ((rc = c->rec_lam.ensure(n_rounds * RECOVER_MAX_T * RECOVER_SLOTS * 8))) return rc;
-  if ((rc = c->rec_pts.ensure(n_rounds * G2A_WORDS * 4))) return rc;
-  if ((rc = c->rec_vpk.ensure(n_rounds * 2 * FP_LIMBS * 4))) return rc;
-  if ((rc = c->rec_st.ensure(n_rounds))) return rc;
-  if ((rc = c->h_pts.ensure(n_rounds * G2A_WORDS * 4))) return rc;
-  if ((rc = c->sig_pts.ensure(items * G2A_WORDS * 4))) return rc;
-  if ((rc = c->status.ensure(items))) return rc;
-  uint32_t* h = (uint32_t*)c->h_pts.p;
-  uint32_t* sg = (uint32_t*)c->sig_pts.p;
-  uint8_t* st = (uint8_t*)c->status.p;
-  uint32_t* hidx = (uint32_t*)c->rec_hidx.p;
-  mark(c, s, "recover_hash");
-  if (g1)
-    hipLaunchKernelGGL(k_hash_to_g1_msgs_pts, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds, d_msgs, g1dst, h);
-  else
-    hipLaunchKernelGGL(k_hash_to_g2_msgs_pts, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds, d_msgs, h);
-  HIP_TRY(hipGetLastError());
-  mark(c, s, "recover_decode");
-  hipLaunchKernelGGL(k_round_of_item, dim3(grid_for(items, 256)), dim3(256), 0, s, items, m, hidx);
-  HIP_TRY(hipGetLastError());
-  if (g1)
-    hipLaunchKernelGGL(k_decode_partials_g1, dim3(grid_for(items, 256)), dim3(256), 0, s, items, d_parts, stride,
-                       d_plen, c->grp_n, c->grp_t, (const uint32_t*)c->grp_table.p, (const uint32_t*)c->grp_commits.p,
-                       sg, (uint32_t*)c->rec_pk.p, (uint32_t*)c->rec_idx.p, st);
-  else
-    hipLaunchKernelGGL(k_decode_partials, dim3(grid_for(items, 256)), dim3(256), 0, s, items, d_parts, stride, d_plen,
-                       c->grp_n, c->grp_t, (const uint32_t*)c->grp_table.p, (const uint32_t*)c->grp_commits.p, sg,
-                       (uint32_t*)c->rec_pk.p, (uint32_t*)c->rec_idx.p, st);
-  HIP_TRY(hipGetLastError());
-  // VerifyPartial of every partial on the engine: e(Eval(i), H(msg)) e(-g1, sig) == 1,
-  // G1 signatures: e(H(msg), Eval(i)) e(-sig, g2) == 1
-  if ((rc = eng_pairing_locked(c, consts, items, h, sg, st, s, n_rounds, hidx, g1 ? nullptr : (const uint32_t*)c->rec_pk.p,
-                               nullptr, nullptr, false, g1 ? (const uint32_t*)c->rec_pk.p : nullptr)))
-    return rc;
-  uint32_t* rpts = (uint32_t*)c->rec_pts.p;
-  uint32_t* rpk = (uint32_t*)c->rec_vpk.p;
-  uint8_t* rst = (uint8_t*)c->rec_st.p;
-  if ((rc = c->rec_sel.ensure(n_rounds * RECOVER_MAX_T * 2 * 4)) ||
-      (rc = c->rec_part.ensure(n_rounds * 5 * G2J_WORDS * 4)))
-    return rc;
-  uint32_t* sel = (uint32_t*)c->rec_sel.p;
-  uint32_t* xs = sel + n_rounds * RECOVER_MAX_T;
-  uint64_t* dig = (uint64_t*)c->rec_lam.p;
-  uint32_t* part = (uint32_t*)c->rec_part.p;
-  const int t = c->grp_t;
-  mark(c, s, "recover_select");
-  hipLaunchKernelGGL(k_recover_select, dim3(grid_for(n_rounds, 64)), dim3(64), 0, s, n_rounds, m, t,
-                     (const uint32_t*)c->rec_idx.p, (const uint8_t*)st, sel, xs, d_out, d_ok,
-                     (const uint32_t*)c->grp_commits.p, rpts, rpk, rst);
-  HIP_TRY(hipGetLastError());
-  mark(c, s, "recover_lagrange");
-  hipLaunchKernelGGL(k_recover_lagrange, dim3(grid_for(n_rounds * RECOVER_MAX_T, 256)), dim3(256), 0, s, n_rounds, t,
-                     (const uint8_t*)d_ok, (const uint32_t*)xs, dig, (uint64_t)0);
-  HIP_TRY(hipGetLastError());
-  mark(c, s, "recover_msm");
-  if (g1) {
-    // (k_recover_select's per-round copy of C_0 in rec_vpk is not used on this
-    // side: VerifyRecovered takes the group's fixed-Q line table)
-    if ((rc = recover_msm_g1_locked(c, n_rounds, t, d_ok, sel, dig, sg, items, part, 4, s))) return rc;
-    hipLaunchKernelGGL(k_recover_finish_g1, dim3(grid_for(n_rounds, 64)), dim3(64), 0, s, n_rounds,
-                       (const uint8_t*)d_ok, (const uint32_t*)part, d_out, rpts, rst, 4);
-    HIP_TRY(hipGetLastError());
-    // VerifyRecovered: e(H(msg), C_0) e(-sig, g2) == 1 over C_0's fixed-Q line table
-    if ((rc = eng_pairing_locked(c, (const uint32_t*)c->grp_key.consts.p, n_rounds, h, rpts, rst, s, 0, nullptr, nullptr,
-                                 (const uint32_t*)c->grp_key.table.p)))
-      return rc;
-    mark(c, s, "recover_verdict");
-    hipLaunchKernelGGL(k_recover_verdict, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds, rst, d_out, d_ok);
-    HIP_TRY(hipGetLastError());
-    if (d_status) HIP_TRY(hipMemcpyAsync(d_status, st, items, hipMemcpyDeviceToDevice, s));
-    mark(c, s);
-    return DGPU_OK;
-  }
-#if defined(DG_RECOVER_MSM_BITS)
-  hipLaunchKernelGGL(k_recover_msm, dim3(grid_for(4 * n_rounds, 256)), dim3(256), 0, s, n_rounds, t,
-                     (const uint8_t*)d_ok, (const uint32_t*)sel, (const uint64_t*)dig, (const uint32_t*)sg, items, part);
-#else
-  {
-    // window tables sized to t (private memory: TMAX x 8 Jacobian points per thread)
-    auto msm = t <= 8 ? k_recover_msm_w4<8> : t <= 16 ? k_recover_msm_w4<16> : t <= 24 ? k_recover_msm_w4<24>
-                                                                                         : k_recover_msm_w4<32>;
-    hipLaunchKernelGGL(msm, dim3(grid_for(4 * n_rounds, 256)), dim3(256), 0, s, n_rounds, t, (const uint8_t*)d_ok,
-                       (const uint32_t*)sel, (const uint64_t*)dig, (const uint32_t*)sg, items, part, 4);
-  }
-#endif
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_recover_finish, dim3(grid_for(n_rounds, 64)), dim3(64), 0, s, n_rounds, (const uint8_t*)d_ok,
-                     (const uint32_t*)part, d_out, rpts, rst, 4);
-  HIP_TRY(hipGetLastError());
-  // VerifyRecovered: e(C_0, H(msg)) e(-g1, sig) == 1
-  if ((rc = eng_pairing_locked(c, consts, n_rounds, h, rpts, rst, s, n_rounds, nullptr, rpk))) return rc;
-  mark(c, s, "recover_verdict");
-  hipLaunchKernelGGL(k_recover_verdict, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds, rst, d_out, d_ok);
-  HIP_TRY(hipGetLastError());
-  if (d_status) HIP_TRY(hipMemcpyAsync(d_status, st, items, hipMemcpyDeviceToDevice, s));
-  mark(c, s);
-  return DGPU_OK;
-}
-
-// Recovery over device buffers (the body of every recover entry point):
-// the batched check (recover.cuh) for every round it decides, the exact
-// per-partial path for the rest (compacted, then scattered back).
-static int recover_slots_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_msgs, size_t m,
-                                const uint8_t* d_parts, size_t stride, const uint32_t* d_plen, uint8_t* d_out,
-                                uint8_t* d_ok, uint8_t* d_status, hipStream_t s) {
-  if (!c->grp_t) return set_err(DGPU_ENOKEY, "no threshold group installed (dgpu_set_group)");
-  c->n_ev = 0;
-  c->ev_overflow = false;
-  c->rlc_pending = false;
-  if (c->recover_exact)
-    return recover_exact_locked(c, n_rounds, d_msgs, m, d_parts, stride, d_plen, d_out, d_ok, d_status, s);
-  const size_t items = n_rounds * m;
-  if (items > 0xFFFFFFFFull) return set_err(DGPU_EINVAL, "batch too large (%zu items)", items);
-  const uint32_t* consts = (const uint32_t*)c->eng_consts.p;
-  const int t = c->grp_t;
-  int rc;
-  const bool g1 = c->grp_g1;  // G1 signatures: the check's combination of share keys is a G2 point per round
-  const int g1dst = c->grp_scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0;
-  if ((rc = c->rec_hidx.ensure(items * 4)) ||
-      (rc = c->rec_pk.ensure(items * (g1 ? (size_t)G2A_WORDS : 2 * FP_LIMBS) * 4)) ||
-      (rc = c->rec_idx.ensure(items * 4)) || (rc = c->rec_lam.ensure(n_rounds * RECOVER_MAX_T * RECOVER_SLOTS * 8)) ||
-      (rc = c->rec_pts.ensure(n_rounds * G2A_WORDS * 4)) ||
-      (rc = c->rec_vpk.ensure(n_rounds * (g1 ? (size_t)G2A_WORDS : 2 * FP_LIMBS) * 4)) ||
-      (rc = c->rec_st.ensure(n_rounds)) || (rc = c->rec_cls.ensure(n_rounds)) ||
-      (rc = c->h_pts.ensure(n_rounds * G2A_WORDS * 4)) || (rc = c->sig_pts.ensure(items * G2A_WORDS * 4)) ||
-      (rc = c->status.ensure(items)) || (rc = c->rec_sel.ensure(n_rounds * RECOVER_MAX_T * 2 * 4)) ||
-      (rc = c->rec_part.ensure(n_rounds * 5 * G2J_WORDS * 4)))
-    return rc;
-  uint32_t* h = (uint32_t*)c->h_pts.p;
-  uint32_t* sg = (uint32_t*)c->sig_pts.p;
-  uint8_t* st = (uint8_t*)c->status.p;
-  uint32_t* sel = (uint32_t*)c->rec_sel.p;
-  uint32_t* xs = sel + n_rounds * RECOVER_MAX_T;
-  uint64_t* dig = (uint64_t*)c->rec_lam.p;
-  uint32_t* part = (uint32_t*)c->rec_part.p;
-  uint32_t* rpts = (uint32_t*)c->rec_pts.p;
-  uint32_t* rpk = (uint32_t*)c->rec_vpk.p;
-  uint8_t* rst = (uint8_t*)c->rec_st.p;
-  uint8_t* cls = (uint8_t*)c->rec_cls.p;
-  // fresh, unpredictable coefficients per call (partials come from peers)
-  std::random_device rd;
-  uint64_t seed = ((uint64_t)rd() << 32) ^ rd();
-  if (!seed) seed = 1;
-  mark(c, s, "recover_hash");
-  if (g1)
-    hipLaunchKernelGGL(k_hash_to_g1_msgs_pts, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds, d_msgs, g1dst, h);
-  else
-    hipLaunchKernelGGL(k_hash_to_g2_msgs_pts, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds, d_msgs, h);
-  HIP_TRY(hipGetLastError());
-  mark(c, s, "recover_decode");
-  if (g1)
-    hipLaunchKernelGGL(k_decode_partials_g1, dim3(grid_for(items, 256)), dim3(256), 0, s, items, d_parts, stride,
-                       d_plen, c->grp_n, c->grp_t, (const uint32_t*)c->grp_table.p, (const uint32_t*)c->grp_commits.p,
-                       sg, (uint32_t*)c->rec_pk.p, (uint32_t*)c->rec_idx.p, st);
-  else
-    hipLaunchKernelGGL(k_decode_partials, dim3(grid_for(items, 256)), dim3(256), 0, s, items, d_parts, stride, d_plen,
-                       c->grp_n, c->grp_t, (const uint32_t*)c->grp_table.p, (const uint32_t*)c->grp_commits.p, sg,
-                       (uint32_t*)c->rec_pk.p, (uint32_t*)c->rec_idx.p, st);
-  HIP_TRY(hipGetLastError());
-  mark(c, s, "recover_select");
-  hipLaunchKernelGGL(k_recover_cand, dim3(grid_for(n_rounds, 64)), dim3(64), 0, s, n_rounds, m, t, d_status ? 1 : 0,
-                     (const uint32_t*)c->rec_idx.p, (const uint8_t*)st, sel, xs, cls, d_ok, d_out);
-  HIP_TRY(hipGetLastError());
-  mark(c, s, "recover_lagrange");
-  hipLaunchKernelGGL(k_recover_lagrange, dim3(grid_for(n_rounds * RECOVER_MAX_T, 256)), dim3(256), 0, s, n_rounds, t,
-                     (const uint8_t*)d_ok, (const uint32_t*)xs, dig, seed);
-  HIP_TRY(hipGetLastError());
-  mark(c, s, "recover_msm");
-  if (g1) {
-    if ((rc = recover_msm_g1_locked(c, n_rounds, t, d_ok, sel, dig, sg, items, part, 5, s))) return rc;
-  } else {
-    // shared affine window tables [1..8] sig_j, then 5 slices of mixed-addition windows
-    const size_t ne = n_rounds * (size_t)t * 8;
-    if ((rc = c->rec_tab.ensure(ne * G2A_WORDS * 4)) || (rc = c->rec_tabz.ensure(ne * 2 * FP_WORDS * 4)) ||
-        (rc = c->rec_tabpre.ensure(ne * FP_WORDS * 4)))
-      return rc;
-    uint32_t* tab = (uint32_t*)c->rec_tab.p;
-    hipLaunchKernelGGL(k_recover_tables, dim3(grid_for(n_rounds * (size_t)t, 256)), dim3(256), 0, s, n_rounds, t,
-                       (const uint8_t*)d_ok, (const uint32_t*)sel, (const uint32_t*)sg, items, tab,
-                       (uint32_t*)c->rec_tabz.p);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_g2_batch_affine, dim3(grid_for((ne + 15) / 16, 256)), dim3(256), 0, s, ne, tab,
-                       (const uint32_t*)c->rec_tabz.p, (uint32_t*)c->rec_tabpre.p);
-    HIP_TRY(hipGetLastError());
-    if (c->recover_rows) {  // the entries as 224-byte rows for the gathers
-      if ((rc = c->rec_tab_rows.ensure(ne * G2A_WORDS * 4))) return rc;
-      hipLaunchKernelGGL(k_recover_tab_rows, dim3(grid_for(ne, 256)), dim3(256), 0, s, ne, (const uint32_t*)tab,
-                         (uint32_t*)c->rec_tab_rows.p);
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(k_recover_msm_aff<true>, dim3(grid_for(5 * n_rounds, 256)), dim3(256), 0, s, n_rounds, t,
-                         (const uint8_t*)d_ok, (const uint64_t*)dig, (const uint32_t*)c->rec_tab_rows.p, part, 5);
-    } else {
-      hipLaunchKernelGGL(k_recover_msm_aff<false>, dim3(grid_for(5 * n_rounds, 256)), dim3(256), 0, s, n_rounds, t,
-                         (const uint8_t*)d_ok, (const uint64_t*)dig, (const uint32_t*)tab, part, 5);
-    }
-    HIP_TRY(hipGetLastError());
-  }
-  if (g1)
-    hipLaunchKernelGGL(k_recover_finish_g1, dim3(grid_for(n_rounds, 64)), dim3(64), 0, s, n_rounds,
-                       (const uint8_t*)d_ok, (const uint32_t*)part, d_out, rpts, rst, 5);
-  else
-    hipLaunchKernelGGL(k_recover_finish, dim3(grid_for(n_rounds, 64)), dim3(64), 0, s, n_rounds, (const uint8_t*)d_ok,
-                       (const uint32_t*)part, d_out, rpts, rst, 5);
-  HIP_TRY(hipGetLastError());
-  if (g1) {
-    mark(c, s, "recover_rlc_g2");
-    hipLaunchKernelGGL(k_recover_rlc_g2, dim3(grid_for(n_rounds, 64)), dim3(64), 0, s, n_rounds, t, c->grp_n,
-                       (const uint32_t*)sel, (const uint32_t*)c->rec_idx.p, (const uint64_t*)dig,
-                       (const uint32_t*)c->grp_wtab.p, (const uint32_t*)c->grp_commits.p, cls, d_ok, rpk, rst);
-  } else {
-    mark(c, s, "recover_rlc_g1");
-    hipLaunchKernelGGL(k_recover_rlc_g1, dim3(grid_for(n_rounds, 64)), dim3(64), 0, s, n_rounds, t, c->grp_n,
-                       (const uint32_t*)sel, (const uint32_t*)c->rec_idx.p, (const uint64_t*)dig,
-                       (const uint32_t*)c->grp_wtab.p, (const uint32_t*)c->grp_commits.p, cls, d_ok, rpk, rst);
-  }
-  HIP_TRY(hipGetLastError());
-  // one pairing per round: e(A, H) e(-g1, B) == 1; G1 signatures: e(H, A) e(-B, g2) == 1
-  if ((rc = eng_pairing_locked(c, consts, n_rounds, h, rpts, rst, s, n_rounds, nullptr, g1 ? nullptr : rpk, nullptr,
-                               nullptr, false, g1 ? rpk : nullptr)))
-    return rc;
-  mark(c, s, "recover_verdict");
-  hipLaunchKernelGGL(k_recover_rlc_verdict, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds,
-                     d_status ? 1 : 0, (const uint8_t*)rst, cls, d_ok, d_out);
-  HIP_TRY(hipGetLastError());
-  if (d_status) HIP_TRY(hipMemcpyAsync(d_status, st, items, hipMemcpyDeviceToDevice, s));
-  // rounds left to the exact path
-  std::vector<uint8_t> hc(n_rounds);
-  HIP_TRY(hipMemcpyAsync(hc.data(), cls, n_rounds, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  std::vector<uint32_t> list;
-  for (size_t r = 0; r < n_rounds; ++r)
-    if ((hc[r] & 0x0F) == REC_EXACT) list.push_back((uint32_t)r);
-  mark(c, s);
-  const size_t nx = list.size();
-  if (nx == 0) return DGPU_OK;
-  const size_t xi = nx * m;
-  if ((rc = c->rec_x_list.ensure(nx * 4)) || (rc = c->rec_x_msgs.ensure(nx * 32)) ||
-      (rc = c->rec_x_parts.ensure(xi * stride)) || (rc = c->rec_x_plen.ensure(xi * 4)) ||
-      (rc = c->rec_x_out.ensure(nx * 96)) || (rc = c->rec_x_ok.ensure(nx)) || (rc = c->rec_x_st.ensure(xi)))
-    return rc;
-  HIP_TRY(hipMemcpyAsync(c->rec_x_list.p, list.data(), nx * 4, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_gather_rounds, dim3(grid_for(xi, 256)), dim3(256), 0, s, nx, (const uint32_t*)c->rec_x_list.p,
-                     m, stride, d_msgs, d_parts, d_plen, (uint8_t*)c->rec_x_msgs.p, (uint8_t*)c->rec_x_parts.p,
-                     (uint32_t*)c->rec_x_plen.p);
-  HIP_TRY(hipGetLastError());
-  if ((rc = recover_exact_locked(c, nx, (const uint8_t*)c->rec_x_msgs.p, m, (const uint8_t*)c->rec_x_parts.p, stride,
-                                 (const uint32_t*)c->rec_x_plen.p, (uint8_t*)c->rec_x_out.p, (uint8_t*)c->rec_x_ok.p,
-                                 (uint8_t*)c->rec_x_st.p, s)))
-    return rc;
-  hipLaunchKernelGGL(k_scatter_rounds, dim3(grid_for(xi, 256)), dim3(256), 0, s, nx, (const uint32_t*)c->rec_x_list.p,
-                     m, (const uint8_t*)c->rec_x_out.p, (const uint8_t*)c->rec_x_ok.p, (const uint8_t*)c->rec_x_st.p,
-                     d_out, d_ok, d_status);
-  HIP_TRY(hipGetLastError());
-  return DGPU_OK;
-}
-
-// Bytes of one recovered signature / of a full partial under the installed group.
-static size_t group_sig_bytes(const dgpu_ctx* c) { return c->grp_g1 ? 48 : 96; }
-static size_t group_partial_bytes(const dgpu_ctx* c) { return 2 + group_sig_bytes(c); }
-
-// recover_slots_locked works on 96-byte round slots (its selection, verdict
-// and scatter kernels zero and copy whole slots); a G1-signature group's
-// 48-byte signatures are packed from the context's slots to d_out + 48 r.
-static int recover_device_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_msgs, size_t m,
-                                 const uint8_t* d_parts, size_t stride, const uint32_t* d_plen, uint8_t* d_out,
-                                 uint8_t* d_ok, uint8_t* d_status, hipStream_t s) {
-  if (!c->grp_g1) return recover_slots_locked(c, n_rounds, d_msgs, m, d_parts, stride, d_plen, d_out, d_ok, d_status, s);
-  int rc;
-  if ((rc = c->rec_slots.ensure(n_rounds * 96))) return rc;
-  uint8_t* slots = (uint8_t*)c->rec_slots.p;
-  if ((rc = recover_slots_locked(c, n_rounds, d_msgs, m, d_parts, stride, d_plen, slots, d_ok, d_status, s))) return rc;
-  hipLaunchKernelGGL(k_recover_pack48, dim3(grid_for(n_rounds * 48, 256)), dim3(256), 0, s, n_rounds,
-                     (const uint8_t*)slots, (const uint8_t*)d_ok, d_out);
-  HIP_TRY(hipGetLastError());
-  return DGPU_OK;
-}
-
-extern "C" {
-
-int dgpu_recover_batch_device(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_msgs32, size_t m,
-                              const uint8_t* d_partials, size_t partial_stride, const uint32_t* d_partial_len,
-                              uint8_t* d_out_sigs, uint8_t* d_ok, uint8_t* d_status, void* stream) {
-  if (!c) return set_err(DGPU_EINVAL, "null ctx");
-  if (n_rounds == 0) return DGPU_OK;  // an empty batch: no-op, NULL buffers accepted (as the verify entry points)
-  if (!d_msgs32 || !d_partials || !d_partial_len || !d_out_sigs || !d_ok) return set_err(DGPU_EINVAL, "null argument");
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (m == 0 || partial_stride < group_partial_bytes(c))
-    return set_err(DGPU_EINVAL, "need m >= 1 partial slots and stride >= %zu", group_partial_bytes(c));
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = caller_stream(stream);
-  stream_order ord(c, s);
-  return recover_device_locked(c, n_rounds, d_msgs32, m, d_partials, partial_stride, d_partial_len, d_out_sigs,
-                               d_ok, d_status, s);
-}
-
-int dgpu_recover_batch(dgpu_ctx* c, size_t n_rounds, const uint8_t* msgs32, size_t m, const uint8_t* partials,
-                       size_t partial_stride, const uint32_t* partial_len, uint8_t* out_sigs, uint8_t* ok_bits,
-                       uint8_t* partial_valid) {
-  if (!c) return set_err(DGPU_EINVAL, "null ctx");
-  if (n_rounds == 0) return DGPU_OK;  // an empty batch: no-op, NULL buffers accepted (as the verify entry points)
-  if (!msgs32 || !partials || !partial_len || !out_sigs || !ok_bits) return set_err(DGPU_EINVAL, "null argument");
-  std::lock_guard<std::mutex> lk(c->mu);
-  if (m == 0 || partial_stride < group_partial_bytes(c))
-    return set_err(DGPU_EINVAL, "need m >= 1 partial slots and stride >= %zu", group_partial_bytes(c));
-  if (!c->grp_t) return set_err(DGPU_ENOKEY, "no threshold group installed (dgpu_set_group)");
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  stream_order ord(c, s);
-  const size_t items = n_rounds * m;
-  for (size_t i = 0; i < items; ++i)
-    if (partial_len[i] > partial_stride) return set_err(DGPU_EINVAL, "partial_len[%zu] > stride", i);
-  int rc;
-  if ((rc = c->rec_msgs.ensure(n_rounds * 32))) return rc;
-  if ((rc = c->rec_parts.ensure(items * partial_stride))) return rc;
-  if ((rc = c->rec_plen.ensure(items * 4))) return rc;
-  if ((rc = c->rec_out.ensure(n_rounds * 96))) return rc;
-  if ((rc = c->rec_ok.ensure(n_rounds))) return rc;
-  if ((rc = c->out_reason.ensure(items))) return rc;
-  HIP_TRY(hipMemcpyAsync(c->rec_msgs.p, msgs32, n_rounds * 32, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(c->rec_parts.p, partials, items * partial_stride, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(c->rec_plen.p, partial_len, items * 4, hipMemcpyHostToDevice, s));
-  if ((rc = recover_device_locked(c, n_rounds, (const uint8_t*)c->rec_msgs.p, m, (const uint8_t*)c->rec_parts.p,
-                                  partial_stride, (const uint32_t*)c->rec_plen.p, (uint8_t*)c->rec_out.p,
-                                  (uint8_t*)c->rec_ok.p, partial_valid ? (uint8_t*)c->out_reason.p : nullptr, s)))
-    return rc;
-  std::vector<uint8_t> okv(n_rounds), stv(partial_valid ? items : 0);
-  HIP_TRY(hipMemcpyAsync(out_sigs, c->rec_out.p, n_rounds * group_sig_bytes(c), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(okv.data(), c->rec_ok.p, n_rounds, hipMemcpyDeviceToHost, s));
-  if (partial_valid) HIP_TRY(hipMemcpyAsync(stv.data(), c->out_reason.p, items, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  memset(ok_bits, 0, (n_rounds + 7) / 8);
-  for (size_t r = 0; r < n_rounds; ++r)
-    if (okv[r]) ok_bits[r >> 3] |= (uint8_t)(1u << (r & 7));
-  if (partial_valid)
-    for (size_t i = 0; i < items; ++i) partial_valid[i] = stv[i] == ST_OK;
-  return DGPU_OK;
-}
-
-int dgpu_make_partials(dgpu_ctx* c, size_t n_rounds, const uint8_t* msgs32, size_t m, const uint32_t* sign_idx,
-                       const uint32_t* label, const uint8_t* shares_be32, size_t n_shares, uint8_t* out98) {
-  return dgpu_make_partials_scheme(c, DGPU_SCHEME_CHAINED, n_rounds, msgs32, m, sign_idx, label, shares_be32, n_shares,
-                                   out98);
-}
-
-int dgpu_make_partials_scheme(dgpu_ctx* c, int scheme, size_t n_rounds, const uint8_t* msgs32, size_t m,
-                              const uint32_t* sign_idx, const uint32_t* label, const uint8_t* shares_be32,
-                              size_t n_shares, uint8_t* out98) {
-  if (!c) return set_err(DGPU_EINVAL, "null ctx");
-  if (!scheme_known(scheme)) return set_err(DGPU_EINVAL, "bad scheme %d", scheme);
-  const bool g1 = sig_on_g1(scheme);
-  const size_t pb = g1 ? 50 : 98;  // bytes per partial
-  if (n_rounds == 0 || m == 0) return DGPU_OK;
-  if (!msgs32 || !sign_idx || !label || !shares_be32 || !out98) return set_err(DGPU_EINVAL, "null argument");
-  const size_t items = n_rounds * m;
-  for (size_t i = 0; i < items; ++i)
-    if (sign_idx[i] >= n_shares || label[i] > 0xFFFF) return set_err(DGPU_EINVAL, "bad share index at item %zu", i);
-  std::vector<scalar256> sh(n_shares);
-  for (size_t j = 0; j < n_shares; ++j) sh[j] = scalar_from_be32(shares_be32 + 32 * j);
-  std::lock_guard<std::mutex> lk(c->mu);
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  stream_order ord(c, s);
-  int rc;
-  DevBuf d_msgs, d_h, d_si, d_lb, d_sh, d_out;
-  auto cleanup = [&]() {
-    hipStreamSynchronize(s);
-    d_msgs.release();
-    d_h.release();
-    d_si.release();
-    d_lb.release();
-    d_sh.release();
-    d_out.release();
-  };
-  if ((rc = d_msgs.ensure(n_rounds * 32)) || (rc = d_h.ensure(n_rounds * G2A_WORDS * 4)) ||
-      (rc = d_si.ensure(items * 4)) || (rc = d_lb.ensure(items * 4)) || (rc = d_sh.ensure(n_shares * sizeof(scalar256))) ||
-      (rc = d_out.ensure(items * pb))) {
-    cleanup();
-    return rc;
-  }
-  hipError_t e = hipMemcpyAsync(d_msgs.p, msgs32, n_rounds * 32, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_si.p, sign_idx, items * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_lb.p, label, items * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_sh.p, sh.data(), n_shares * sizeof(scalar256), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) {
-    if (g1)
-      hipLaunchKernelGGL(k_hash_to_g1_msgs_pts, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds,
-                         (const uint8_t*)d_msgs.p, scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, (uint32_t*)d_h.p);
-    else
-      hipLaunchKernelGGL(k_hash_to_g2_msgs_pts, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds,
-                         (const uint8_t*)d_msgs.p, (uint32_t*)d_h.p);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) {
-    if (g1)
-      hipLaunchKernelGGL(k_sign_partials_g1, dim3(grid_for(items, 64)), dim3(64), 0, s, items, m, n_rounds,
-                         (const uint32_t*)d_h.p, (const uint32_t*)d_si.p, (const uint32_t*)d_lb.p,
-                         (const scalar256*)d_sh.p, (uint8_t*)d_out.p);
-    else
-      hipLaunchKernelGGL(k_sign_partials, dim3(grid_for(items, 64)), dim3(64), 0, s, items, m, n_rounds,
-                         (const uint32_t*)d_h.p, (const uint32_t*)d_si.p, (const uint32_t*)d_lb.p,
-                         (const scalar256*)d_sh.p, (uint8_t*)d_out.p);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(out98, d_out.p, items * pb, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  cleanup();
-  if (e != hipSuccess) return set_err(DGPU_EDEVICE, "make_partials: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return set_err(DGPU_EDEVICE, "make_chain: %s", hipGetErrorString(e));
   return DGPU_OK;
 }
 
 }  // extern "C"
 
+#include "threshold_host.h"
 #include "multi_gpu.h"

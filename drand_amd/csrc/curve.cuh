@@ -408,13 +408,6 @@ DG_FN g2j g2_psi2_body(const g2j& p) {
   return g2j{fp2_mul_fp(p.x, fp2(C_PSI2_CX).c0), fp2_mul_fp(p.y, fp2(C_PSI2_CY).c0), p.z};
 }
 
-#ifdef DG_LADDER_DBL_PLAIN  // A/B: every doubling fully reduced (g2_dbl_body)
-#define G2_LADDER_DBL g2_dbl_body
-#define G2_LADDER_ZRED(r) (r)
-#else
-#define G2_LADDER_DBL g2_dbl_lz
-#define G2_LADDER_ZRED(r) g2_z_reduce(r)
-#endif
 // [|x|] of the point in stash slot k, |x| = 0xd201000000010000 (bits 63, 62,
 // 60, 57, 48, 16): runs of 1, 2, 3, 9 and 32 doublings, each closed by an
 // addition of the point reloaded from the slot, then 16 doublings -- only the
@@ -426,12 +419,12 @@ DG_FN g2j g2_mul_absx_stash(Stash& st, int k, bool& exc) {
   for (int a = 0; a < 5; ++a) {
     const int nd = a == 0 ? 1 : a == 1 ? 2 : a == 2 ? 3 : a == 3 ? 9 : 32;
 #pragma unroll 1
-    for (int d = 0; d < nd; ++d) r = G2_LADDER_DBL(r);
-    r = g2_add_nx_q(G2_LADDER_ZRED(r), st.at(k), exc);
+    for (int d = 0; d < nd; ++d) r = g2_dbl_lz(r);
+    r = g2_add_nx_q(g2_z_reduce(r), st.at(k), exc);
   }
 #pragma unroll 1
-  for (int d = 0; d < 16; ++d) r = G2_LADDER_DBL(r);
-  return G2_LADDER_ZRED(r);
+  for (int d = 0; d < 16; ++d) r = g2_dbl_lz(r);
+  return g2_z_reduce(r);
 }
 
 // madd-2007-bl (g2_add_affine_body) for operands that are neither equal,
@@ -468,12 +461,12 @@ DG_FN bool g2_in_subgroup_ladder(const g2a& p, const Q& q, bool& exc) {
   for (int a = 0; a < 5; ++a) {
     const int nd = a == 0 ? 1 : a == 1 ? 2 : a == 2 ? 3 : a == 3 ? 9 : 32;
 #pragma unroll 1
-    for (int d = 0; d < nd; ++d) r = G2_LADDER_DBL(r);
-    r = g2_madd_nx_q(G2_LADDER_ZRED(r), q, exc);
+    for (int d = 0; d < nd; ++d) r = g2_dbl_lz(r);
+    r = g2_madd_nx_q(g2_z_reduce(r), q, exc);
   }
 #pragma unroll 1
-  for (int d = 0; d < 16; ++d) r = G2_LADDER_DBL(r);
-  return g2_eq(g2_psi(g2_from_affine(q.get())), g2_neg(G2_LADDER_ZRED(r)));
+  for (int d = 0; d < 16; ++d) r = g2_dbl_lz(r);
+  return g2_eq(g2_psi(g2_from_affine(q.get())), g2_neg(g2_z_reduce(r)));
 }
 
 // h_eff (Q0 + Q1) in the order of g2_clear_cofactor (RFC 9380 G.3) with the
@@ -498,19 +491,6 @@ DG_FN g2j g2_clear_cofactor_stash(const g2j& q0, const g2j& q1, Stash& st, bool&
   return g2_add_nx(st.get(1), g2_neg(nB), exc);
 }
 
-// Clear cofactor with the whole computation inlined (k_h2c_finish).
-DG_FN g2j g2_clear_cofactor_inl(const g2j& p) {
-  g2j t1 = g2_neg(g2_mul_absx_inl(p));
-  g2j t2 = g2_psi(p);
-  g2j t3 = g2_psi2(g2_dbl_body(p));
-  t3 = g2_add_body(t3, g2_neg(t2));
-  t2 = g2_add_body(t1, t2);
-  t2 = g2_neg(g2_mul_absx_inl(t2));
-  t3 = g2_add_body(t3, t2);
-  t3 = g2_add_body(t3, g2_neg(t1));
-  return g2_add_body(t3, g2_neg(p));
-}
-
 // Clear cofactor: h_eff * P = [x^2 - x - 1] P + [x - 1] psi(P) + psi^2(2P)
 // (RFC 9380 appendix G.3 sequence).
 DG_NOINL g2j g2_clear_cofactor_generic(const g2j& p) {
@@ -533,12 +513,12 @@ DG_FN g2j g2_mul_absx_fast(const g2j& p, bool& exc) {
   for (int a = 0; a < 5; ++a) {
     const int nd = a == 0 ? 1 : a == 1 ? 2 : a == 2 ? 3 : a == 3 ? 9 : 32;
 #pragma unroll 1
-    for (int d = 0; d < nd; ++d) r = G2_LADDER_DBL(r);
-    r = g2_add_nx(G2_LADDER_ZRED(r), p, exc);
+    for (int d = 0; d < nd; ++d) r = g2_dbl_lz(r);
+    r = g2_add_nx(g2_z_reduce(r), p, exc);
   }
 #pragma unroll 1
-  for (int d = 0; d < 16; ++d) r = G2_LADDER_DBL(r);
-  return G2_LADDER_ZRED(r);
+  for (int d = 0; d < 16; ++d) r = g2_dbl_lz(r);
+  return g2_z_reduce(r);
 }
 
 // h_eff P (the sequence above) for the one-off callers -- the RLC node
@@ -546,7 +526,6 @@ DG_FN g2j g2_mul_absx_fast(const g2j& p, bool& exc) {
 // form in registers (round 6), the generic form when an addition is
 // exceptional or P is the identity.
 DG_NOINL g2j g2_clear_cofactor(const g2j& p) {
-#ifndef DG_COFACTOR_GENERIC
   bool exc = g2_is_inf(p);
   const g2j nt1 = g2_mul_absx_fast(p, exc);  // -[x]P
   const g2j t2 = g2_psi_body(p);
@@ -557,7 +536,6 @@ DG_NOINL g2j g2_clear_cofactor(const g2j& p) {
   t3 = g2_add_nx(t3, nt1, exc);
   t3 = g2_add_nx(t3, g2_neg(p), exc);
   if (!exc) return t3;
-#endif
   return g2_clear_cofactor_generic(p);
 }
 
@@ -628,7 +606,6 @@ DG_FN fp fp_mulk_lz(const fp& a, uint32_t k) {
   return r;
 }
 
-#ifndef DG_G1_DBL_PLAIN
 // dbl-2009-l (a = 0) with g2_dbl_body's lazy linear steps, in Fp (round 6;
 // 7 products and 3 reductions where the form below, every step reduced, makes
 // 14).  CI in, CI out; bounds in units of p: 2Y lazy (< 4.02p, limbs < 2^29)
@@ -651,25 +628,9 @@ DG_FN g1j g1_dbl_body(const g1j& p) {
   r.y = fp_reduce(fp_norm(fp_sub2_lz(fp_mul(E, DX), fp_norm(fp_mulk_lz(C, 8)))));
   return r;
 }
-#else  // A/B: rounds 1-5, every step reduced
-DG_FN g1j g1_dbl_body(const g1j& p) {
-  fp A = fp_sqr(p.x);
-  fp B = fp_sqr(p.y);
-  fp C = fp_sqr(B);
-  fp D = fp_dbl(fp_sub(fp_sqr(fp_add(p.x, B)), fp_add(A, C)));
-  fp E = fp_add(fp_dbl(A), A);
-  fp F = fp_sqr(E);
-  g1j r;
-  r.x = fp_sub(F, fp_dbl(D));
-  r.y = fp_sub(fp_mul(E, fp_sub(D, r.x)), fp_dbl(fp_dbl(fp_dbl(C))));
-  r.z = fp_dbl(fp_mul(p.y, p.z));
-  return r;
-}
-#endif
 
 DG_NOINL g1j g1_dbl(const g1j& p) { return g1_dbl_body(p); }
 
-#ifndef DG_G1_ADD_PLAIN
 // add-2007-bl with g2_add_body's lazy linear steps, in Fp (round 6: 4
 // reductions where the every-step-reduced form makes 13; same bounds as the G2
 // form: rr = 2(s2 - s1) and 2h normalized (< 4.02p); X3 = rr^2 - (J + 2V)
@@ -698,34 +659,11 @@ DG_FN g1j g1_add_body(const g1j& p, const g1j& q) {
   if (q_inf) r = p;
   return r;
 }
-#else  // A/B: rounds 1-5, every step reduced
-DG_FN g1j g1_add_body(const g1j& p, const g1j& q) {
-  fp z1z1 = fp_sqr(p.z), z2z2 = fp_sqr(q.z);
-  fp u1 = fp_mul(p.x, z2z2), u2 = fp_mul(q.x, z1z1);
-  fp s1 = fp_mul(fp_mul(p.y, q.z), z2z2), s2 = fp_mul(fp_mul(q.y, p.z), z1z1);
-  fp h = fp_sub(u2, u1);
-  fp rr = fp_dbl(fp_sub(s2, s1));
-  bool p_inf = g1_is_inf(p), q_inf = g1_is_inf(q);
-  bool h0 = fp_is_zero(h), r0 = fp_is_zero(rr);
-  fp i = fp_sqr(fp_dbl(h));
-  fp j = fp_mul(h, i);
-  fp v = fp_mul(u1, i);
-  g1j r;
-  r.x = fp_sub(fp_sub(fp_sqr(rr), j), fp_dbl(v));
-  r.y = fp_sub(fp_mul(rr, fp_sub(v, r.x)), fp_dbl(fp_mul(s1, j)));
-  r.z = fp_mul(fp_sub(fp_sqr(fp_add(p.z, q.z)), fp_add(z1z1, z2z2)), h);
-  if (h0 && !p_inf && !q_inf) r = r0 ? g1_dbl(p) : g1_infinity();
-  if (p_inf) r = q;
-  if (q_inf) r = p;
-  return r;
-}
-#endif
 
 DG_NOINL g1j g1_add(const g1j& p, const g1j& q) { return g1_add_body(p, q); }
 
 // Mixed addition p + q, q affine (madd-2007-bl, a = 0: 7M + 4S), exceptional
 // cases resolved (p == q -> dbl, p == -q -> infinity, p infinity -> q).
-#ifndef DG_G1_ADD_PLAIN
 // madd-2007-bl with g2_add_affine_body's lazy linear steps, in Fp (4
 // reductions where the every-step-reduced form makes 12; I = 4 HH normalized,
 // < 4.04p).
@@ -751,28 +689,6 @@ DG_FN g1j g1_add_affine_body(const g1j& p, const g1a& q) {
   if (p_inf) r = g1j{q.x, q.y, fp_one()};
   return r;
 }
-#else
-DG_FN g1j g1_add_affine_body(const g1j& p, const g1a& q) {
-  const fp z1z1 = fp_sqr(p.z);
-  const fp u2 = fp_mul(q.x, z1z1);
-  const fp s2 = fp_mul(fp_mul(q.y, p.z), z1z1);
-  const fp h = fp_sub(u2, p.x);
-  const fp rr = fp_dbl(fp_sub(s2, p.y));
-  const bool p_inf = g1_is_inf(p);
-  const bool h0 = fp_is_zero(h), r0 = fp_is_zero(rr);
-  const fp hh = fp_sqr(h);
-  const fp i = fp_dbl(fp_dbl(hh));
-  const fp j = fp_mul(h, i);
-  const fp v = fp_mul(p.x, i);
-  g1j r;
-  r.x = fp_sub(fp_sub(fp_sqr(rr), j), fp_dbl(v));
-  r.y = fp_sub(fp_mul(rr, fp_sub(v, r.x)), fp_dbl(fp_mul(p.y, j)));
-  r.z = fp_sub(fp_sqr(fp_add(p.z, h)), fp_add(z1z1, hh));
-  if (h0 && !p_inf) r = r0 ? g1_dbl(g1j{q.x, q.y, fp_one()}) : g1_infinity();
-  if (p_inf) r = g1j{q.x, q.y, fp_one()};
-  return r;
-}
-#endif
 
 DG_FN g1j g1_cmov(const g1j& a, const g1j& b, bool take_b) {
   return g1j{fp_cmov(a.x, b.x, take_b), fp_cmov(a.y, b.y, take_b), fp_cmov(a.z, b.z, take_b)};

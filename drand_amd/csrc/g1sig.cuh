@@ -27,22 +27,11 @@ DG_FN fp fp_row(const uint32_t (*t)[FP_LIMBS], int i) {
 // RFC 9380 sgn0 for Fp: parity of the canonical value
 DG_FN uint32_t fp_sgn0(const fp& a) { return fp_from_mont(a).l[0] & 1u; }
 
-// sum_i c_i N^i D^(deg - i): a polynomial in x = N / D, homogenized (Horner)
-DG_NOINL fp iso11_hom(const uint32_t (*c)[FP_LIMBS], int deg, const fp& N, const fp& D) {
-  fp acc = fp_row(c, deg);
-  fp dk = fp_one();
-  for (int i = deg - 1; i >= 0; --i) {
-    dk = fp_mul(dk, D);
-    acc = fp_add(fp_mul(acc, N), fp_mul(fp_row(c, i), dk));
-  }
-  return acc;
-}
-
 // The four polynomials of the 11-isogeny (x numerator degree 11, denominator
 // 10, y numerator and denominator 15), homogenized in x = N / D, in one Horner
 // pass (round 6): at step s every polynomial of degree >= s takes
 // acc = acc N + c_(deg - s) D^s, so D^s is formed once per step (15 products
-// where four iso11_hom calls form 51), and the sums stay unreduced between
+// where a Horner pass per polynomial forms 51), and the sums stay unreduced between
 // steps -- two products < 1.01p each, the sum < 2.02p with limbs < 2^29, is
 // the next product's operand -- reduced once at the end (51 reductions fewer).
 DG_FN void iso11_hom4(const fp& N, const fp& D, fp& xn, fp& xd, fp& yn, fp& yd) {
@@ -83,15 +72,8 @@ DG_FN g1j map_to_curve_sswu_iso11_body(const fp& u) {
     N = fp_mul(zu2, N);
   }
   if (fp_sgn0(u) != fp_sgn0(y)) y = fp_neg(y);
-#ifdef DG_ISO11_PLAIN  // A/B: rounds 2-5, four Horner passes, every sum reduced
-  const fp xn = iso11_hom(ISO11_XNUM, 11, N, D);
-  const fp xd = iso11_hom(ISO11_XDEN, 10, N, D);
-  const fp yn = iso11_hom(ISO11_YNUM, 15, N, D);
-  const fp yd = iso11_hom(ISO11_YDEN, 15, N, D);
-#else
   fp xn, xd, yn, yd;
   iso11_hom4(N, D, xn, xd, yn, yd);
-#endif
   // x_E1 = xn / (xd D), y_E1 = y yn / yd; Jacobian Z = xd D yd (0 for the exceptional inputs)
   const fp xdd = fp_mul(xd, D);
   const fp T = fp_mul(xdd, fp_sqr(yd));

@@ -286,8 +286,7 @@ DG_FN void hash_to_field_g2(fp2& u0, fp2& u1, const uint32_t msg[8]) {
 // included -- gives y = sqrt(w)/D^2 = fp2_sqrt_scaled(w, g, norm(D))
 // conj(D)^2.  The isogeny is evaluated on x = N/D homogeneously.  Model and
 // derivation: tools/sswu_model.py (tests/test_sswu_model.py).
-// The body in stages (k_sswu_a / _b / _c run them as separate launches with
-// the two exponentiations between them, k_fp_pow_planes):
+// The body in stages, one before and one after each exponentiation:
 //   sswu_pre   x1 = N/D and w = U D;  alpha = Norm(w) goes to the first exponentiation
 //   sswu_mid   g = alpha^((p+1)/4): gx1 square or not (then x2, w scaled); returns
 //              d (fp2_sqrt_scaled's real part) and dm4 = d Norm(D)^4 for the second
@@ -301,10 +300,6 @@ DG_FN void sswu_pre(const fp2& zu2, fp2& N, fp2& D, fp2& D2, fp2& D3, fp2& w) {
   D2 = fp2_sqr(D);
   D3 = fp2_mul(D2, D);
   w = fp2_mul(fp2_add(fp2_mul(N, fp2_add(fp2_sqr(N), fp2_mul(C_SSWU_A, D2))), fp2_mul(C_SSWU_B, D3)), D);
-}
-DG_FN void sswu_pre(const fp2& u, fp2& N, fp2& D, fp2& w) {
-  fp2 D2, D3;
-  sswu_pre(sswu_zu2(u), N, D, D2, D3, w);
 }
 // g: the candidate root of alpha = Norm(w); N, w updated to x2's when gx1 is
 // not a square.  Returns d; dm4 = d Norm(D)^4 (fp2_sqrt_scaled's steps).
@@ -342,12 +337,6 @@ DG_FN g2j sswu_post(const fp2& u, const fp2& N, const fp2& D, const fp2& D2, con
   r.y = fp2_mul(fp2_mul(y, yn), fp2_mul(fp2_sqr(xdd), tt));
   // an exceptional input (xd or yd = 0) gives Z = 0: the identity (RFC 9380 section 6.6.3)
   return r;
-}
-
-DG_FN g2j sswu_post(const fp2& u, const fp2& N, const fp2& D, const fp2& w, const fp& d, const fp& dm4,
-                    const fp& t) {
-  const fp2 D2 = fp2_sqr(D);
-  return sswu_post(u, N, D, D2, fp2_mul(D2, D), w, d, dm4, t);
 }
 
 DG_FN g2j map_to_curve_sswu_iso3_body(const fp2& u) {

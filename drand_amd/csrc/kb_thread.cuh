@@ -64,13 +64,7 @@ DG_FN void kb_sqr_thr(fp2& f1, fp2& f2, fp2& f4, fp2& f5) {
     const fp2 c25 = fp2_sqr(fp2_carry(fp2_add_lz(f2, f5)));
     const fp2 q = kb_t_qsum(c2, c5);
     n4 = fp2{kb_t_out(q.c0, f4.c0, true), kb_t_out(q.c1, f4.c1, true)};
-#ifdef DG_KB_XI_REDUCED  // A/B: 2 f2 f5 reduced before the twist (rounds 3-5)
-    const fp2 x = kb_t_cross(c25, c2, c5);
-    const fp2 xr{fp_reduce(x.c0), fp_reduce(x.c1)};
-    const fp2 xx{fp_norm(fp_sub_lz(xr.c0, xr.c1)), fp_norm(fp_add_lz(xr.c0, xr.c1))};  // xi (2 f2 f5)
-#else
     const fp2 xx = kb_t_xi_cross(c25, c2, c5);
-#endif
     n1 = fp2{kb_t_out(xx.c0, f1.c0, false), kb_t_out(xx.c1, f1.c1, false)};
   }
   // B side: f2' and f5'

@@ -56,27 +56,9 @@ struct lt_pt_val {
   DG_FN fp y() const { return y_; }
 };
 
-// T.x and T.z leave the doubling with their second coefficient reduced and
-// the first only normalized (t0 + 8p - t1 < 9.2p; lt_fp2_mul_c1r, round 6):
-// every consumer takes that -- fp2_sqr(X), fp2_sqr(Z) and the carried X + Y,
-// Y + Z need c1 < 7.99p for their a0 - a1 and see products < 300 p^2; the
-// addition step's products and fp2_sub minuends take any normalized operand
-// -- and lt_pair_p reduces the final T (the membership test compares it).
-// Two reductions fewer per doubling (A/B: -DDG_LINES_DBL_C1R).
-DG_FN fp2 lt_fp2_mul_c1r(const fp2& a, const fp2& b) {
-  const fp t0 = fp_mul(a.c0, b.c0);
-  const fp t1 = fp_mul(a.c1, b.c1);
-  const fp t2 = fp_mul(fp_add_lz(a.c0, a.c1), fp_add_lz(b.c0, b.c1));
-  return fp2{fp_norm(fp_sub_lz(t0, t1)), fp_reduce(fp_norm(fp_sub2_lz(t2, fp_add_lz(t0, t1))))};
-}
-// Measured without gain (r06s: eng_lines 128.3 vs 127.6 ms per 2M, noise);
-// the A/B build variant -DDG_LINES_DBL_C1R keeps it, both outputs reduced ship.
-#ifdef DG_LINES_DBL_C1R
-#define LT_MUL_OUT lt_fp2_mul_c1r
-#else
-#define LT_MUL_OUT fp2_mul
-#endif
-
+// (The doubling's T.x and T.z with their first coefficient only normalized,
+// two reductions fewer, measured without gain: profiles/r06/
+// r06s_lines_dbl_c1r_ab.txt; the code is in git history.)
 template <class PT, class Emit>
 DG_FN void lt_dbl_p(g2p& T, const PT& P, Emit&& emit) {
   const fp nxp = P.nx();
@@ -90,9 +72,9 @@ DG_FN void lt_dbl_p(g2p& T, const PT& P, Emit&& emit) {
   const fp2 xt1 = fp2_carry(fp2{fp_sub_lz(t1.c0, t1.c1), fp_add_lz(t1.c0, t1.c1)});
   const fp2 t2 = fp2{fp_reduce(fp_norm(fp2_mulk_lz(xt1, 12).c0)), fp_reduce(fp_norm(fp2_mulk_lz(xt1, 12).c1))};
   emit(0, fp2_sub(t0, t2));
-  T.z = LT_MUL_OUT(fp2_carry(fp2_mulk_lz(t0, 4)), yz2);
+  T.z = fp2_mul(fp2_carry(fp2_mulk_lz(t0, 4)), yz2);
   const fp2 t3 = fp2_carry(fp2_add_lz(fp2_add_lz(t2, t2), t2));
-  T.x = LT_MUL_OUT(xy2, fp2_carry(fp2{fp_sub_lz(t0.c0, t3.c0), fp_sub_lz(t0.c1, t3.c1)}));
+  T.x = fp2_mul(xy2, fp2_carry(fp2{fp_sub_lz(t0.c0, t3.c0), fp_sub_lz(t0.c1, t3.c1)}));
   const fp2 t2sq = fp2_sqr(t2);
   T.y = fp2_sub32(fp2_sqr(fp2_carry(fp2_add_lz(t0, t3))), fp2_carry(fp2_mulk_lz(t2sq, 12)));
 }

@@ -142,13 +142,10 @@ void dgpu_multi_close(dgpu_multi* m) {
     if (m->comm[i]) m->api.comm_destroy(m->comm[i]);
   for (size_t i = 0; i < m->ctx.size(); ++i) {
     hipSetDevice(m->devs[i]);
-    for (DevBuf* b : {&m->buf[i].bits, &m->buf[i].reasons, &m->buf[i].all_bits, &m->buf[i].all_reasons,
-                      &m->buf[i].root, &m->buf[i].all_roots})
-      b->release();
     if (i < m->gev.size() && m->gev[i]) hipEventDestroy(m->gev[i]);
-    dgpu_close(m->ctx[i]);
+    dgpu_close(m->ctx[i]);  // drains the context's streams, which the gathers ran on
   }
-  delete m;
+  delete m;  // the gather buffers go with the handle
 }
 
 int dgpu_multi_context(dgpu_multi* m, int k, dgpu_ctx** out) {

@@ -12,7 +12,7 @@
 // compressed to 96 bytes; then VerifyRecovered (chain.go:165) of every
 // recovered signature under C_0 on the engine.
 //
-// Batched check (the default path, capi.hip recover_device_locked): all
+// Batched check (the default path, threshold_host.h recover_slots_locked): all
 // partials of a round sign the same H(msg), so instead of t VerifyPartial
 // pairings the round's first t decodable partials (the candidates) are
 // checked together with the recovered signature in ONE two-pair pairing:
@@ -177,7 +177,7 @@ __global__ void __launch_bounds__(64) k_sign_partials(size_t n_items, size_t m, 
 //                       failures are final here (zero output, ok = 0)
 //   k_recover_lagrange  per (round, j): the Lagrange coefficient at 0 over Fr
 //                       as base-|x| digits, lambda = d0 + d1|x| + d2|x|^2 + d3|x|^3
-//   k_recover_msm       per (round, i < 4): P_i = sum_j d_{j,i} sig_j (Straus, 64 bits)
+//   k_recover_msm_w4    per (round, i < 4): P_i = sum_j d_{j,i} sig_j (signed radix-16 windows)
 //   k_recover_finish    per round: sum_j lambda_j sig_j = P0 - psi(P1) + psi^2(P2)
 //                       - psi^3(P3) (psi = [x] on G2, x < 0: [|x|] = -psi), compressed
 constexpr uint64_t RECOVER_ABSX_ODD = 0xd20100000001ull;  // |x| = 2^16 RECOVER_ABSX_ODD
@@ -259,27 +259,6 @@ __global__ void __launch_bounds__(256) k_recover_lagrange(size_t n_rounds, int t
   d[4] = rlc_seed ? rlc_coeff(rlc_seed, g) : 0;
 }
 
-__global__ void __launch_bounds__(256, 2) k_recover_msm(size_t n_rounds, int t, const uint8_t* __restrict__ ok,
-                                                     const uint32_t* __restrict__ sel,
-                                                     const uint64_t* __restrict__ digits,
-                                                     const uint32_t* __restrict__ sig_pts, size_t n_items,
-                                                     uint32_t* __restrict__ part) {
-  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= 4 * n_rounds) return;
-  const size_t r = g >> 2;
-  const int i = (int)(g & 3);
-  if (!ok[r]) return;
-  const uint64_t* d = digits + r * RECOVER_MAX_T * RECOVER_SLOTS + i;
-  const uint32_t* sl = sel + r * RECOVER_MAX_T;
-  g2j acc = g2_infinity();
-  for (int b = 63; b >= 0; --b) {
-    acc = g2_dbl_body(acc);
-    for (int j = 0; j < t; ++j)
-      if ((d[RECOVER_SLOTS * j] >> b) & 1ull) acc = g2_add_affine_body(acc, ld_g2a(sig_pts, n_items, sl[j]));
-  }
-  st_g2j(part + (size_t)i * G2J_WORDS * n_rounds, n_rounds, r, acc);
-}
-
 // Signed radix-16 digit j (0..16) of a 64-bit k: d_j = w_j + b_{4j-1} - 16
 // b_{4j+3} (w_j the 4-bit window, b the bits of k), in [-8, 8];
 // k = sum_j d_j 16^j.
@@ -290,10 +269,11 @@ DG_FN int win4_digit64(uint64_t k, int j) {
   return w + cin - 16 * cout;
 }
 
-// k_recover_msm with the same operation sequence in every lane.  The lanes
+// The recovery MSM with the same operation sequence in every lane.  The lanes
 // of a wave hold different rounds, whose signer sets (so Lagrange digits)
-// differ; the bit-driven loop above runs an addition whenever any lane's bit
-// is set, i.e. about 64 t per thread.  Here: per point j a table
+// differ; a bit-driven Straus loop runs an addition whenever any lane's bit
+// is set, i.e. about 64 t per thread (measured: profiles/r02/
+// r02zj_recover_msm_window_ab.json; in git history).  Here: per point j a table
 // [1..8] sig_j (Jacobian, private memory, 1 doubling + 6 mixed additions),
 // then 17 signed radix-16 windows of 4 doublings + t additions (a zero
 // digit's addition computed and discarded): 16 t + 7 t additions in all.
@@ -471,13 +451,12 @@ __global__ void __launch_bounds__(256, 2) k_recover_msm_aff(size_t n_rounds, int
   const size_t base = r * (size_t)t * 8;
   bool exc = false;
   g2j acc = g2_infinity();
-#ifndef DG_RECOVER_MSM_GENERIC
 #pragma unroll 1
   for (int w = 16; w >= 0; --w) {
     if (w < 16) {
 #pragma unroll 1
-      for (int s = 0; s < 4; ++s) acc = G2_LADDER_DBL(acc);
-      acc = G2_LADDER_ZRED(acc);
+      for (int s = 0; s < 4; ++s) acc = g2_dbl_lz(acc);
+      acc = g2_z_reduce(acc);
     }
 #pragma unroll 1
     for (int j = 0; j < t; ++j) {
@@ -492,9 +471,6 @@ __global__ void __launch_bounds__(256, 2) k_recover_msm_aff(size_t n_rounds, int
       acc = g2_cmov(acc, sum, mag != 0);
     }
   }
-#else
-  exc = true;
-#endif
   if (exc || DG_FORCE_EXC) {  // the generic mixed addition (rounds 2-5): exceptional cases resolved
     acc = g2_infinity();
 #pragma unroll 1

@@ -299,7 +299,6 @@ __global__ void __launch_bounds__(256, 2) k_msm_bucket_seg(size_t n, size_t T, c
   if (p0 >= L) return;
   const size_t p1 = p0 + S < L ? p0 + S : L;
   bool exc = false;
-#ifndef DG_MSM_GENERIC
   if constexpr (std::is_same<Gr, G2Ops>::value) {
     uint32_t key = keys[p0];
     size_t s = p0;
@@ -326,7 +325,6 @@ __global__ void __launch_bounds__(256, 2) k_msm_bucket_seg(size_t n, size_t T, c
     msm_seg_emit<Gr>(key, s, p1, t, T, offsets, counts, acc, buckets, part);
     if (!exc && !DG_FORCE_EXC) return;
   }
-#endif
   uint32_t key = keys[p0];
   size_t s = p0;
   typename Gr::jac acc = Gr::inf();

@@ -101,7 +101,7 @@ DG_FN bool fp2_is_square(const fp2& a) { return fp_is_square(fp2_norm(a)); }
 // d square -> d t + (w1 t / 2) u, else (w1 t / 2) - d t u.
 // Derivation and model: tools/sswu_model.py (sqrt_scaled).
 // fp2_sqrt_scaled in two halves around its exponentiation t = dm4^((p-3)/4)
-// (the staged SSWU runs that exponentiation as its own launch): _pre returns
+// (h2c.cuh's SSWU body calls them as its stages): _pre returns
 // d and dm4 = d m^4, _post the root from t.
 DG_FN fp fp2_sqrt_scaled_pre(const fp2& w, const fp& g, const fp& m, fp& dm4) {
   fp d = fp_half(fp_add(w.c0, g));

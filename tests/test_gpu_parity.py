@@ -429,3 +429,44 @@ def test_two_lane_per_round_large_chain():
     expect = np.ones(n, dtype=bool)
     expect[list(bad.keys())] = False
     assert np.array_equal(two == 0, expect)
+
+
+def test_key_cache_eviction_reuses_slots_across_key_kinds():
+    """Ten distinct keys through one context's cache of eight (capi.hip
+    get_key_locked), alternating pedersen-bls-chained (48-byte G1 key) and
+    bls-unchained-on-g1 (96-byte G2 key with its fixed-Q line table), so a
+    reused slot changes kind.  Each batch has 7 rounds -- one full 5-round
+    engine block and a ragged one -- with one round's signature negated.  All
+    ten verify; then key 0 again (evicted: decoded into a reused slot) and key
+    9 (still cached).  Reasons equal the construction every time: a stale or
+    mixed-up key would fail every round with REASON_PAIRING."""
+    from drand_amd import _lib
+    from drand_amd.synth import make_chain
+    chains = []
+    for k in range(10):
+        code = _lib.SCHEME_UNCHAINED_G1 if k & 1 else _lib.SCHEME_CHAINED
+        c = make_chain(100 + k, 7, code, seg_len=7, sk=1000 + k)
+        c.sigs[k % 7, 0] ^= 0x20  # -sigma: a valid point, the pairing fails
+        chains.append(c)
+    assert len({c.pk for c in chains}) == 10
+    ctx = open_ctx({})
+    try:
+        def reasons(c):
+            n = len(c)
+            pk = np.frombuffer(c.pk, dtype=np.uint8).copy()
+            bits = np.zeros((n + 7) // 8, dtype=np.uint8)
+            reason = np.full(n, 0xFF, dtype=np.uint8)
+            _lib.check(ctx.lib.dgpu_verify_beacons(ctx.handle, c.scheme_code, _lib.ptr(pk), pk.size, n,
+                                                   _lib.ptr(c.rounds), _lib.ptr(c.sigs), c.sigs.shape[1],
+                                                   _lib.ptr(c.sig_len), _lib.ptr(c.prev), c.prev.shape[1],
+                                                   _lib.ptr(c.prev_len), _lib.MODE_PER_ROUND, 0, _lib.ptr(bits),
+                                                   _lib.ptr(reason)), ctx.lib)
+            assert np.array_equal(np.unpackbits(bits, bitorder="little")[:n].astype(bool), reason == 0)
+            return reason.tolist()
+
+        for k in list(range(10)) + [0, 9]:
+            expect = [_lib.REASON_OK] * 7
+            expect[k % 7] = _lib.REASON_PAIRING
+            assert reasons(chains[k]) == expect, k
+    finally:
+        ctx.close()
