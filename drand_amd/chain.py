@@ -180,6 +180,47 @@ class Verifier:
             raise _lib.DrandGPUError(_lib.DGPU_EINVAL, "verdict bitmap and reasons disagree")
         return reason
 
+    def verify_segment(self, first_round, sigs, prev_sig, pubkey, mode=_lib.MODE_PER_ROUND, rlc_seed=None,
+                       randomness=True, sig_len=None):
+        """A linked run of rounds known by its signatures alone
+        (dgpu_verify_segment; the walk of client/verify.go:118-178): round
+        first_round + i carries sigs[i], its previous signature is prev_sig
+        for i = 0 and sigs[i - 1] after (ignored by the unchained schemes).
+        sigs: a list of bytes, or an (n, stride) uint8 array with sig_len.
+        Returns (reasons, randomness): the DGPU_REASON_* codes as
+        verify_records returns them, and the (n, 32) uint8 array of
+        SHA-256(sigs[i]) for the rounds that verify (zeros for the others;
+        client/verify.go:207), or None when randomness is False."""
+        width = 48 if self._code in (_lib.SCHEME_UNCHAINED_G1, _lib.SCHEME_G1_RFC9380) else 96
+        if isinstance(sigs, np.ndarray):
+            if sig_len is None:
+                raise ValueError("a signature array needs sig_len")
+            buf = np.ascontiguousarray(sigs, dtype=np.uint8)
+            lens = np.ascontiguousarray(sig_len, dtype=np.uint32)
+            if buf.ndim != 2 or lens.shape != (buf.shape[0],):
+                raise ValueError("sigs must be (n, stride) and sig_len (n,)")
+        else:
+            buf, lens = _pack_msgs([bytes(s or b"") for s in sigs])
+        if buf.shape[1] < width:
+            buf = np.pad(buf, ((0, 0), (0, width - buf.shape[1])))
+        n = buf.shape[0]
+        rand = np.zeros((n, 32), dtype=np.uint8) if randomness else None
+        if n == 0:
+            return np.zeros(0, dtype=np.uint8), rand
+        seed = np.frombuffer(bytes(prev_sig or b""), dtype=np.uint8).copy()
+        bits = np.zeros((n + 7) // 8, dtype=np.uint8)
+        reason = np.zeros(n, dtype=np.uint8)
+        pk = np.frombuffer(bytes(pubkey), dtype=np.uint8).copy()
+        _lib.check(self.ctx.lib.dgpu_verify_segment(self.ctx.handle, self._code, _lib.ptr(pk), pk.size, int(first_round),
+                                                    n, _lib.ptr(buf), buf.shape[1], _lib.ptr(lens),
+                                                    _lib.ptr(seed) if seed.size else None, seed.size, mode,
+                                                    rlc_seed_for(mode, rlc_seed), _lib.ptr(bits), _lib.ptr(reason),
+                                                    None if rand is None else _lib.ptr(rand)), self.ctx.lib)
+        valid = np.unpackbits(bits, bitorder="little")[:n].astype(bool)
+        if not np.array_equal(valid, reason == _lib.REASON_OK):
+            raise _lib.DrandGPUError(_lib.DGPU_EINVAL, "verdict bitmap and reasons disagree")
+        return reason, rand
+
     def verify_beacon(self, b: Beacon, pubkey: bytes):
         """chain/verify.go:38-45: raises VerifyError (the reference's non-nil
         error) or returns None."""

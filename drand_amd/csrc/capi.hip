@@ -169,7 +169,7 @@ struct key_entry {
 struct verify_args {
   int scheme;
   size_t n;
-  msg_src m;
+  msg_src_linked m;  // (linked = 0: an explicit or raw source, its msg_src part)
   const uint8_t* sigs;
   size_t sig_stride;
   const uint32_t* sig_len;
@@ -177,9 +177,9 @@ struct verify_args {
   uint64_t seed;
 };
 
-msg_src beacon_src(const uint64_t* rounds, const uint8_t* prev, size_t prev_stride, const uint32_t* prev_len,
-                   bool chained) {
-  msg_src m{};
+msg_src_linked beacon_src(const uint64_t* rounds, const uint8_t* prev, size_t prev_stride, const uint32_t* prev_len,
+                          bool chained) {
+  msg_src_linked m{};
   m.rounds = rounds;
   m.chained = chained ? 1 : 0;
   m.prev = chained ? prev : nullptr;
@@ -188,13 +188,42 @@ msg_src beacon_src(const uint64_t* rounds, const uint8_t* prev, size_t prev_stri
   return m;
 }
 
-msg_src raw_src(const uint8_t* msgs, size_t stride, const uint32_t* len) {
-  msg_src m{};
+// The linked form (kernels.cuh msg_src_linked): round first_round + g, previous
+// signature = the seed (copied into the source) for g = 0, else signature
+// g - 1 of the call's signature array.  seed_len <= 96 (checked by the entry
+// points).
+msg_src_linked linked_src(uint64_t first_round, const uint8_t* sigs, size_t sig_stride, const uint32_t* sig_len,
+                          const uint8_t* seed, size_t seed_len, bool chained) {
+  msg_src_linked m{};
+  m.linked = 1;
+  m.first_round = first_round;
+  m.chained = chained ? 1 : 0;
+  if (chained) {
+    m.prev = sigs;
+    m.prev_stride = sig_stride;
+    m.prev_len = sig_len;
+    m.seed_len = (uint32_t)seed_len;
+    if (seed_len) memcpy(m.seed, seed, seed_len);
+  }
+  return m;
+}
+
+msg_src_linked raw_src(const uint8_t* msgs, size_t stride, const uint32_t* len) {
+  msg_src_linked m{};
   m.msgs = msgs;
   m.msg_stride = stride;
   m.msg_len = len;
   return m;
 }
+
+// f(source) with the source as the type its kernels are instantiated for:
+// the linked form, or the msg_src part of any other.
+template <class F>
+auto with_src(const msg_src_linked& m, F&& f) {
+  return m.linked ? f(m) : f(static_cast<const msg_src&>(m));
+}
+// the kernel template K for the source type of `src` (inside with_src)
+#define SRC_KERNEL(K, src) K<std::decay_t<decltype(src)>>
 
 }  // namespace
 
@@ -291,7 +320,7 @@ struct dgpu_ctx {
                                  // (k_eng_miller_xw), bit 1 the FE segments (k_eng_fe_seg_xw); A/B: DGPU_ENG_XW
   bool stage_pageable = false;   // A/B build, DGPU_STAGE=pageable: the round-5 whole-batch pageable copy
   // staging for host-pointer entry points
-  DevBuf in_rounds, in_sigs, in_sig_len, in_prev, in_prev_len, in_msgs, in_msg_len, out_bits, out_reason, misc;
+  DevBuf in_rounds, in_sigs, in_sig_len, in_prev, in_prev_len, in_msgs, in_msg_len, out_bits, out_reason, out_rand, misc;
   // optional per-stage HIP-event timing of the last verify call (event pool;
   // durations are summed per stage name: chunked stages repeat)
   bool profile = false;
@@ -771,12 +800,16 @@ int rlc_points_locked(dgpu_ctx* c, const verify_args& a, hipStream_t s) {
   uint8_t* st = (uint8_t*)c->status.p;
   if (G.g1) {
     mark(c, s, "rlc_hash_to_g1_raw");
-    hipLaunchKernelGGL(k_hash_to_g1_raw, dim3(grid_for(n, B)), dim3(B), 0, s, n, a.m,
-                       a.scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, rpts, rpts + 2 * FP_WORDS * n);
+    with_src(a.m, [&](const auto& m) {
+      hipLaunchKernelGGL(SRC_KERNEL(k_hash_to_g1_raw, m), dim3(grid_for(n, B)), dim3(B), 0, s, n, m,
+                         a.scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, rpts, rpts + 2 * FP_WORDS * n);
+    });
     HIP_TRY(hipGetLastError());
     mark(c, s, "decode_g1");
-    hipLaunchKernelGGL(k_decode_g1_sigs, dim3(grid_for(n, B)), dim3(B), 0, s, n, a.sigs, a.sig_stride, a.sig_len,
-                       a.m, sg, st);
+    with_src(a.m, [&](const auto& m) {
+      hipLaunchKernelGGL(SRC_KERNEL(k_decode_g1_sigs, m), dim3(grid_for(n, B)), dim3(B), 0, s, n, a.sigs, a.sig_stride,
+                         a.sig_len, m, sg, st);
+    });
     HIP_TRY(hipGetLastError());
     mark(c, s, "rlc_affine");
     hipLaunchKernelGGL(k_g1_batch_affine, dim3(grid_for((n + 15) / 16, B)), dim3(B), 0, s, n, rpts,
@@ -790,15 +823,19 @@ int rlc_points_locked(dgpu_ctx* c, const verify_args& a, hipStream_t s) {
     // the per-round hash's field and SSWU stages, then Q0 + Q1 without the cofactor
     uint32_t* u = (uint32_t*)c->h_tmp.p;
     uint32_t* q = u + 4 * FP_WORDS * n;
-    hipLaunchKernelGGL(k_h2c_field, dim3(grid_for(n, B)), dim3(B), 0, s, n, a.m, u);
+    with_src(a.m, [&](const auto& m) {
+      hipLaunchKernelGGL(SRC_KERNEL(k_h2c_field, m), dim3(grid_for(n, B)), dim3(B), 0, s, n, m, u);
+    });
     HIP_TRY(hipGetLastError());
     HIP_TRY(launch_sswu(n, u, q, s));
     hipLaunchKernelGGL(k_h2c_sum, dim3(grid_for(n, B)), dim3(B), 0, s, n, (const uint32_t*)q, rpts);
     HIP_TRY(hipGetLastError());
   }
   mark(c, s, "decode_g2");
-  hipLaunchKernelGGL(k_decode_g2_sigs_sub, dim3(grid_for(n, B)), dim3(B), 0, s, n, a.sigs, a.sig_stride, a.sig_len,
-                     a.m, sg, st);
+  with_src(a.m, [&](const auto& m) {
+    hipLaunchKernelGGL(SRC_KERNEL(k_decode_g2_sigs_sub, m), dim3(grid_for(n, B)), dim3(B), 0, s, n, a.sigs, a.sig_stride,
+                       a.sig_len, m, sg, st);
+  });
   HIP_TRY(hipGetLastError());
   mark(c, s, "rlc_affine");
   // R_i to affine in place (X, Y slots; Z follows them in the Jacobian SoA)
@@ -1152,14 +1189,18 @@ int verify_g1_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a, ui
   if (side) {
     HIP_TRY(hipEventRecord(c->lane_ev[0], s));
     HIP_TRY(hipStreamWaitEvent(c->stream2, c->lane_ev[0], 0));
-    hipLaunchKernelGGL(k_decode_g1_sigs, dim3(grid_for(n, B)), dim3(B), 0, c->stream2, n, a.sigs, a.sig_stride,
-                       a.sig_len, a.m, sg, st);
+    with_src(a.m, [&](const auto& m) {
+      hipLaunchKernelGGL(SRC_KERNEL(k_decode_g1_sigs, m), dim3(grid_for(n, B)), dim3(B), 0, c->stream2, n, a.sigs,
+                         a.sig_stride, a.sig_len, m, sg, st);
+    });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->lane_ev[1], c->stream2));
   }
   mark(c, s, "hash_to_g1");
-  hipLaunchKernelGGL(k_hash_to_g1_beacons, dim3(grid_for(n, B)), dim3(B), 0, s, n, a.m,
-                     a.scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, h, (uint32_t*)c->h_z.p);
+  with_src(a.m, [&](const auto& m) {
+    hipLaunchKernelGGL(SRC_KERNEL(k_hash_to_g1_beacons, m), dim3(grid_for(n, B)), dim3(B), 0, s, n, m,
+                       a.scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, h, (uint32_t*)c->h_z.p);
+  });
   HIP_TRY(hipGetLastError());
   mark(c, s, "h_affine");
   hipLaunchKernelGGL(k_g1_batch_affine, dim3(grid_for((n + 15) / 16, B)), dim3(B), 0, s, n, h,
@@ -1170,8 +1211,10 @@ int verify_g1_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a, ui
     join.release();
   } else {
     mark(c, s, "decode_g1");
-    hipLaunchKernelGGL(k_decode_g1_sigs, dim3(grid_for(n, B)), dim3(B), 0, s, n, a.sigs, a.sig_stride, a.sig_len, a.m,
-                       sg, st);
+    with_src(a.m, [&](const auto& m) {
+      hipLaunchKernelGGL(SRC_KERNEL(k_decode_g1_sigs, m), dim3(grid_for(n, B)), dim3(B), 0, s, n, a.sigs, a.sig_stride,
+                         a.sig_len, m, sg, st);
+    });
     HIP_TRY(hipGetLastError());
   }
   return eng_pairing_locked(c,
@@ -1199,7 +1242,7 @@ int stager_wait_all(host_stager* stg, hipStream_t s);
 // consts (the key's engine constants; optional): calls of at most
 // cof_engine_max rounds clear the cofactor on the engine ladder
 // (pairing_engine.cuh k_cof_*) instead of k_h2c_finish.
-int g2_lane_hash_locked(dgpu_ctx* c, const lane_bufs& L, size_t n, const msg_src& m, const uint8_t* sigs,
+int g2_lane_hash_locked(dgpu_ctx* c, const lane_bufs& L, size_t n, const msg_src_linked& m, const uint8_t* sigs,
                         size_t sig_stride, const uint32_t* sig_len, uint8_t* st, hipStream_t s,
                         hipStream_t s_dec = nullptr, const uint32_t* consts = nullptr, host_stager* stg = nullptr,
                         size_t slice = 0) {
@@ -1215,12 +1258,14 @@ int g2_lane_hash_locked(dgpu_ctx* c, const lane_bufs& L, size_t n, const msg_src
   uint32_t* q = u + 4 * FP_WORDS * n;
   // membership of the signature: checked by the lines kernel (eng_pairing_locked sig_subgroup)
   auto decode = [&](hipStream_t sd) {
-    if (c->decode_subgroup)
-      hipLaunchKernelGGL(k_decode_g2_sigs_sub, dim3(grid_for(n, B)), dim3(B), 0, sd, n, sigs, sig_stride, sig_len, m,
-                         sg, st);
-    else
-      hipLaunchKernelGGL(k_decode_g2_sigs, dim3(grid_for(n, B)), dim3(B), 0, sd, n, sigs, sig_stride, sig_len, m, 0,
-                         sg, st);
+    with_src(m, [&](const auto& ms) {
+      if (c->decode_subgroup)
+        hipLaunchKernelGGL(SRC_KERNEL(k_decode_g2_sigs_sub, ms), dim3(grid_for(n, B)), dim3(B), 0, sd, n, sigs,
+                           sig_stride, sig_len, ms, sg, st);
+      else
+        hipLaunchKernelGGL(SRC_KERNEL(k_decode_g2_sigs, ms), dim3(grid_for(n, B)), dim3(B), 0, sd, n, sigs, sig_stride,
+                           sig_len, ms, 0, sg, st);
+    });
     return hipGetLastError();
   };
   const bool cof_engine = consts && n <= c->cof_engine_max;
@@ -1237,7 +1282,9 @@ int g2_lane_hash_locked(dgpu_ctx* c, const lane_bufs& L, size_t n, const msg_src
     HIP_TRY(hipEventRecord(c->lane_ev[1], s_dec));
   }
   mark(c, s, "hash_to_g2");
-  hipLaunchKernelGGL(k_h2c_field, dim3(grid_for(n, B)), dim3(B), 0, s, n, m, u);
+  with_src(m, [&](const auto& ms) {
+    hipLaunchKernelGGL(SRC_KERNEL(k_h2c_field, ms), dim3(grid_for(n, B)), dim3(B), 0, s, n, ms, u);
+  });
   HIP_TRY(hipGetLastError());
   HIP_TRY(launch_sswu(n, u, q, s));
   if (cof_engine) {
@@ -1293,10 +1340,14 @@ int g2_lane_hash_locked(dgpu_ctx* c, const lane_bufs& L, size_t n, const msg_src
   return DGPU_OK;
 }
 
-// msg_src of items [off, off + cnt) of m
-msg_src src_slice(const msg_src& m, size_t off) {
-  msg_src r = m;
-  if (m.msgs) {
+// msg_src of items [off, off + cnt) of m.  The linked form keeps its base
+// pointers (the slice's first item reads the record before the slice) and
+// carries the offset.
+msg_src_linked src_slice(const msg_src_linked& m, size_t off) {
+  msg_src_linked r = m;
+  if (m.linked) {
+    r.g0 = m.g0 + off;
+  } else if (m.msgs) {
     r.msgs = m.msgs + off * m.msg_stride;
     r.msg_len = m.msg_len + off;
   } else {
@@ -1320,7 +1371,7 @@ int check_args(const dgpu_ctx* c, const key_entry* key, const verify_args& a) {
   if (!a.sigs || !a.sig_len || a.sig_stride < sig_bytes) return set_err(DGPU_EINVAL, "bad signature buffers");
   if (a.m.msgs || a.m.msg_len) {
     if (!a.m.msgs || !a.m.msg_len) return set_err(DGPU_EINVAL, "bad message buffers");
-  } else {
+  } else if (!a.m.linked) {  // (the linked form's records are the signature arrays, checked above)
     if (!a.m.rounds) return set_err(DGPU_EINVAL, "null rounds");
     if (a.m.chained && (!a.m.prev_len || (!a.m.prev && a.m.prev_stride)))
       return set_err(DGPU_EINVAL, "chained scheme needs previous signatures");
@@ -1428,20 +1479,33 @@ int verify_status_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a
   return DGPU_OK;
 }
 
-// status -> verdict bitmap and optional reasons (device buffers)
-int verify_device_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a, uint8_t* d_bits,
-                         uint8_t* d_reason, hipStream_t s) {
-  int rc = check_args(c, key, a);
-  if (rc || a.n == 0) return rc;
-  if (!d_bits) return set_err(DGPU_EINVAL, "null verdict buffer");
-  if ((rc = verify_status_locked(c, key, a, s))) return rc;
+// The final statuses -> verdict bitmap, then (d_rand: optional, 32 bytes per
+// round) the verified rounds' randomness.  a's signature arrays are device
+// memory.  Closes the call's stage markers.
+int pack_results_locked(dgpu_ctx* c, const verify_args& a, uint8_t* d_bits, uint8_t* d_rand, hipStream_t s) {
   const unsigned B = 256;
   const uint8_t* st = (const uint8_t*)c->status.p;
   mark(c, s, "pack_verdicts");
   hipLaunchKernelGGL(k_pack_verdicts, dim3(grid_for((a.n + 7) / 8, B)), dim3(B), 0, s, a.n, st, d_bits);
   HIP_TRY(hipGetLastError());
+  if (d_rand) {
+    mark(c, s, "randomness");
+    hipLaunchKernelGGL(k_randomness, dim3(grid_for(a.n, B)), dim3(B), 0, s, a.n, a.sigs, a.sig_stride, a.sig_len, st,
+                       d_rand);
+    HIP_TRY(hipGetLastError());
+  }
   mark(c, s);
-  if (d_reason) HIP_TRY(hipMemcpyAsync(d_reason, st, a.n, hipMemcpyDeviceToDevice, s));
+  return DGPU_OK;
+}
+
+// status -> verdict bitmap, optional reasons and randomness (device buffers)
+int verify_device_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a, uint8_t* d_bits,
+                         uint8_t* d_reason, hipStream_t s, uint8_t* d_rand = nullptr) {
+  int rc = check_args(c, key, a);
+  if (rc || a.n == 0) return rc;
+  if (!d_bits) return set_err(DGPU_EINVAL, "null verdict buffer");
+  if ((rc = verify_status_locked(c, key, a, s)) || (rc = pack_results_locked(c, a, d_bits, d_rand, s))) return rc;
+  if (d_reason) HIP_TRY(hipMemcpyAsync(d_reason, c->status.p, a.n, hipMemcpyDeviceToDevice, s));
   return DGPU_OK;
 }
 
@@ -1456,7 +1520,11 @@ int stage_inputs_locked(dgpu_ctx* c, verify_args& a, hipStream_t s) {
   HIP_TRY(hipMemcpyAsync(c->in_sig_len.p, a.sig_len, n * 4, hipMemcpyHostToDevice, s));
   a.sigs = (const uint8_t*)c->in_sigs.p;
   a.sig_len = (const uint32_t*)c->in_sig_len.p;
-  msg_src& m = a.m;
+  msg_src_linked& m = a.m;
+  if (m.linked) {  // the records are the signature arrays
+    if (m.chained) m.prev = a.sigs, m.prev_len = a.sig_len;
+    return DGPU_OK;
+  }
   if (m.msgs) {
     for (size_t i = 0; i < n; ++i)
       if (m.msg_len[i] > m.msg_stride) return set_err(DGPU_EINVAL, "msg_len[%zu]=%u > msg_stride", i, m.msg_len[i]);
@@ -1588,10 +1656,12 @@ struct host_stager {
   // the message arrays of items [a, b) (checked against their stride), then
   // its signature arrays; an event after each part
   int stage_slice(const verify_args& dev, size_t k, size_t a, size_t b) {
-    const msg_src& m = host.m;
+    const msg_src_linked& m = host.m;
     const size_t n = b - a;
     int r;
-    if (m.msgs) {
+    if (m.linked) {
+      // no message part: the slice's digests read its signatures (wait_part)
+    } else if (m.msgs) {
       for (size_t i = a; i < b; ++i)
         if (m.msg_len[i] > m.msg_stride) return set_err(DGPU_EINVAL, "msg_len[%zu]=%u > msg_stride", i, m.msg_len[i]);
       if ((r = ring_copy_locked(c, (uint8_t*)dev.m.msgs + a * m.msg_stride, m.msgs + a * m.msg_stride,
@@ -1649,6 +1719,14 @@ struct host_stager {
     });
   }
   int wait_part(size_t k, hipStream_t s, bool sig) {
+    // A linked slice has no message part of its own: a chained one hashes its
+    // signatures (and the last record of slice k - 1, which the in-order copy
+    // stream put on the device before slice k's event); an unchained one
+    // hashes nothing that is staged.
+    if (host.m.linked && !sig) {
+      if (!host.m.chained) return DGPU_OK;
+      sig = true;
+    }
     std::unique_lock<std::mutex> lk(mu);
     cv.wait(lk, [&] { return (sig ? staged : staged_msg) > k || rc != DGPU_OK; });
     if ((sig ? staged : staged_msg) <= k) return set_err(rc, "%s", err.c_str());
@@ -1671,7 +1749,11 @@ int stage_prepare_locked(dgpu_ctx* c, verify_args& a) {
   if ((rc = c->in_sigs.ensure(n * a.sig_stride)) || (rc = c->in_sig_len.ensure(n * 4))) return rc;
   a.sigs = (const uint8_t*)c->in_sigs.p;
   a.sig_len = (const uint32_t*)c->in_sig_len.p;
-  msg_src& m = a.m;
+  msg_src_linked& m = a.m;
+  if (m.linked) {  // the records are the signature arrays: no rounds, no second copy of the signatures
+    if (m.chained) m.prev = a.sigs, m.prev_len = a.sig_len;
+    return DGPU_OK;
+  }
   if (m.msgs) {
     if ((rc = c->in_msgs.ensure(n * m.msg_stride + 1)) || (rc = c->in_msg_len.ensure(n * 4))) return rc;
     m.msgs = (const uint8_t*)c->in_msgs.p;
@@ -1724,25 +1806,27 @@ int stage_all_host_locked(dgpu_ctx* c, verify_args& a, hipStream_t s) {
 }
 
 // Host-buffer verify: stage, verify, copy the verdicts back (synchronous).
+// rand32 (optional, n x 32 bytes): the verified rounds' randomness, returned
+// with the verdicts.
 int verify_host_pageable_locked(dgpu_ctx* c, const key_entry* key, verify_args a, uint8_t* verdict_bits,
-                                uint8_t* reason);
-int verify_host_locked(dgpu_ctx* c, const key_entry* key, verify_args a, uint8_t* verdict_bits, uint8_t* reason) {
-  if (c->stage_pageable) return verify_host_pageable_locked(c, key, a, verdict_bits, reason);
+                                uint8_t* reason, uint8_t* rand32);
+int verify_host_locked(dgpu_ctx* c, const key_entry* key, verify_args a, uint8_t* verdict_bits, uint8_t* reason,
+                       uint8_t* rand32 = nullptr) {
+  if (c->stage_pageable) return verify_host_pageable_locked(c, key, a, verdict_bits, reason, rand32);
   int rc = check_args(c, key, a);
   if (rc || a.n == 0) return rc;
   if (!verdict_bits) return set_err(DGPU_EINVAL, "null verdict buffer");
   hipStream_t s = c->stream;
   stream_order ord(c, s);
   if ((rc = c->out_bits.ensure((a.n + 7) / 8)) || (rc = c->out_reason.ensure(a.n))) return rc;
-  if ((rc = verify_status_host_locked(c, key, a, s))) return rc;
-  const uint8_t* st = (const uint8_t*)c->status.p;
-  mark(c, s, "pack_verdicts");
-  hipLaunchKernelGGL(k_pack_verdicts, dim3(grid_for((a.n + 7) / 8, 256)), dim3(256), 0, s, a.n, st,
-                     (uint8_t*)c->out_bits.p);
-  HIP_TRY(hipGetLastError());
-  mark(c, s);
+  if (rand32 && (rc = c->out_rand.ensure(a.n * 32))) return rc;
+  // (a's signature pointers are the device copies from here on)
+  if ((rc = verify_status_host_locked(c, key, a, s)) ||
+      (rc = pack_results_locked(c, a, (uint8_t*)c->out_bits.p, rand32 ? (uint8_t*)c->out_rand.p : nullptr, s)))
+    return rc;
   HIP_TRY(hipMemcpyAsync(verdict_bits, c->out_bits.p, (a.n + 7) / 8, hipMemcpyDeviceToHost, s));
-  if (reason) HIP_TRY(hipMemcpyAsync(reason, st, a.n, hipMemcpyDeviceToHost, s));
+  if (reason) HIP_TRY(hipMemcpyAsync(reason, c->status.p, a.n, hipMemcpyDeviceToHost, s));
+  if (rand32) HIP_TRY(hipMemcpyAsync(rand32, c->out_rand.p, a.n * 32, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return DGPU_OK;
 }
@@ -1750,7 +1834,7 @@ int verify_host_locked(dgpu_ctx* c, const key_entry* key, verify_args a, uint8_t
 // The pre-ring host path (whole batch staged by pageable hipMemcpyAsync, then
 // verified): kept for the A/B build's DGPU_STAGE=pageable comparison.
 int verify_host_pageable_locked(dgpu_ctx* c, const key_entry* key, verify_args a, uint8_t* verdict_bits,
-                                uint8_t* reason) {
+                                uint8_t* reason, uint8_t* rand32) {
   int rc = check_args(c, key, a);
   if (rc || a.n == 0) return rc;
   if (!verdict_bits) return set_err(DGPU_EINVAL, "null verdict buffer");
@@ -1758,9 +1842,13 @@ int verify_host_pageable_locked(dgpu_ctx* c, const key_entry* key, verify_args a
   stream_order ord(c, s);
   if ((rc = stage_inputs_locked(c, a, s))) return rc;
   if ((rc = c->out_bits.ensure((a.n + 7) / 8)) || (rc = c->out_reason.ensure(a.n))) return rc;
-  if ((rc = verify_device_locked(c, key, a, (uint8_t*)c->out_bits.p, (uint8_t*)c->out_reason.p, s))) return rc;
+  if (rand32 && (rc = c->out_rand.ensure(a.n * 32))) return rc;
+  if ((rc = verify_device_locked(c, key, a, (uint8_t*)c->out_bits.p, (uint8_t*)c->out_reason.p, s,
+                                 rand32 ? (uint8_t*)c->out_rand.p : nullptr)))
+    return rc;
   HIP_TRY(hipMemcpyAsync(verdict_bits, c->out_bits.p, (a.n + 7) / 8, hipMemcpyDeviceToHost, s));
   if (reason) HIP_TRY(hipMemcpyAsync(reason, c->out_reason.p, a.n, hipMemcpyDeviceToHost, s));
+  if (rand32) HIP_TRY(hipMemcpyAsync(rand32, c->out_rand.p, a.n * 32, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return DGPU_OK;
 }
@@ -2001,6 +2089,56 @@ int dgpu_verify_beacons_device(dgpu_ctx* c, int scheme, const uint8_t* pk, size_
   const verify_args a{scheme, n, beacon_src(d_rounds, d_prev, prev_stride, d_prev_len, scheme == DGPU_SCHEME_CHAINED),
                       d_sigs, sig_stride, d_sig_len, mode, rlc_seed};
   return verify_device_locked(c, k, a, d_bits, d_reason, s);
+}
+
+// The arguments of the two segment entry points that no other call has.
+static int check_segment_args(int scheme, uint64_t first_round, size_t n, const uint8_t* seed_prev,
+                              size_t seed_prev_len) {
+  if (seed_prev_len > sizeof(msg_src_linked::seed))
+    return set_err(DGPU_EINVAL, "seed_prev_len %zu > %zu", seed_prev_len, sizeof(msg_src_linked::seed));
+  if (n && first_round + (uint64_t)(n - 1) < first_round)
+    return set_err(DGPU_EINVAL, "rounds %llu + %zu overflow", (unsigned long long)first_round, n);
+  if (scheme == DGPU_SCHEME_CHAINED && seed_prev_len && !seed_prev) return set_err(DGPU_EINVAL, "null seed_prev");
+  return DGPU_OK;
+}
+
+int dgpu_verify_segment(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t pk_len, uint64_t first_round, size_t n,
+                        const uint8_t* sigs, size_t sig_stride, const uint32_t* sig_len, const uint8_t* seed_prev,
+                        size_t seed_prev_len, int mode, uint64_t rlc_seed, uint8_t* verdict_bits, uint8_t* reason,
+                        uint8_t* randomness32) {
+  if (!c) return set_err(DGPU_EINVAL, "null ctx");
+  int rc = check_segment_args(scheme, first_round, n, seed_prev, seed_prev_len);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  key_entry* k = nullptr;
+  if ((rc = get_key_locked(c, scheme, pk, pk_len, &k))) return rc;
+  const verify_args a{scheme, n,
+                      linked_src(first_round, sigs, sig_stride, sig_len, seed_prev, seed_prev_len,
+                                 scheme == DGPU_SCHEME_CHAINED),
+                      sigs, sig_stride, sig_len, mode, rlc_seed};
+  return verify_host_locked(c, k, a, verdict_bits, reason, randomness32);
+}
+
+int dgpu_verify_segment_device(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t pk_len, uint64_t first_round,
+                               size_t n, const uint8_t* d_sigs, size_t sig_stride, const uint32_t* d_sig_len,
+                               const uint8_t* seed_prev, size_t seed_prev_len, int mode, uint64_t rlc_seed,
+                               uint8_t* d_bits, uint8_t* d_reason, uint8_t* d_randomness32, void* stream) {
+  if (!c) return set_err(DGPU_EINVAL, "null ctx");
+  int rc = check_segment_args(scheme, first_round, n, seed_prev, seed_prev_len);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  key_entry* k = nullptr;
+  if ((rc = get_key_locked(c, scheme, pk, pk_len, &k))) return rc;
+  hipStream_t s = caller_stream(stream);
+  stream_order ord(c, s);
+  // the seed travels inside the source (a kernel argument): seed_prev is not read after this line
+  const verify_args a{scheme, n,
+                      linked_src(first_round, d_sigs, sig_stride, d_sig_len, seed_prev, seed_prev_len,
+                                 scheme == DGPU_SCHEME_CHAINED),
+                      d_sigs, sig_stride, d_sig_len, mode, rlc_seed};
+  return verify_device_locked(c, k, a, d_bits, d_reason, s, d_randomness32);
 }
 
 int dgpu_rlc_root_bytes(int scheme) {
@@ -2326,10 +2464,10 @@ int dgpu_decode_signatures(dgpu_ctx* c, int scheme, size_t n, const uint8_t* sig
   uint32_t* pts = (uint32_t*)c->sig_pts.p;
   uint8_t* st = (uint8_t*)c->status.p;
   if (g1)
-    hipLaunchKernelGGL(k_decode_g1_sigs, dim3(grid_for(n, 256)), dim3(256), 0, s, n, d_sigs, sig_stride, d_len, m, pts,
+    hipLaunchKernelGGL(k_decode_g1_sigs<msg_src>, dim3(grid_for(n, 256)), dim3(256), 0, s, n, d_sigs, sig_stride, d_len, m, pts,
                        st);
   else
-    hipLaunchKernelGGL(k_decode_g2_sigs_sub, dim3(grid_for(n, 256)), dim3(256), 0, s, n, d_sigs, sig_stride, d_len, m,
+    hipLaunchKernelGGL(k_decode_g2_sigs_sub<msg_src>, dim3(grid_for(n, 256)), dim3(256), 0, s, n, d_sigs, sig_stride, d_len, m,
                        pts, st);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(reason, st, n, hipMemcpyDeviceToHost, s));

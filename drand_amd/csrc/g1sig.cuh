@@ -167,7 +167,8 @@ DG_NOINL int g1_decompress_sig(g1a* out, const uint8_t* in) { return g1_decompre
 // H(m) in G1 of each item's message (msg_src: the unchained DigestMessage
 // SHA-256(BE64(round)), chain/verify.go:24-32, or raw bytes): X, Y into h_out
 // ([x, y][limb][n]), Z into z_out.
-__global__ void __launch_bounds__(256, 2) k_hash_to_g1_beacons(size_t n, msg_src m, int g1dst,
+template <class Src>
+__global__ void __launch_bounds__(256, 2) k_hash_to_g1_beacons(size_t n, Src m, int g1dst,
                                                              uint32_t* __restrict__ h_out, uint32_t* __restrict__ z_out) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -185,7 +186,8 @@ __global__ void __launch_bounds__(256, 2) k_hash_to_g1_beacons(size_t n, msg_src
 // RLC mode (rlc_msm.cuh): the pre-cofactor hash point R = Q0 + Q1 on E1
 // (Jacobian X, Y into r_out, Z into z_out): h_eff = 1 + |x| is applied once per
 // checked node, by linearity, instead of a 64-step ladder per round.
-__global__ void __launch_bounds__(256, 2) k_hash_to_g1_raw(size_t n, msg_src m, int g1dst,
+template <class Src>
+__global__ void __launch_bounds__(256, 2) k_hash_to_g1_raw(size_t n, Src m, int g1dst,
                                                          uint32_t* __restrict__ r_out, uint32_t* __restrict__ z_out) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -247,8 +249,9 @@ __global__ void __launch_bounds__(256) k_g1_batch_affine(size_t n, uint32_t* __r
 }
 
 // G1 signature decode + membership: affine [x, y][limb][n], status ST_*.
+template <class Src>
 __global__ void __launch_bounds__(256, 2) k_decode_g1_sigs(size_t n, const uint8_t* __restrict__ sigs, size_t sig_stride,
-                                                         const uint32_t* __restrict__ sig_len, msg_src m,
+                                                         const uint32_t* __restrict__ sig_len, Src m,
                                                          uint32_t* __restrict__ sig_out, uint8_t* __restrict__ status) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;

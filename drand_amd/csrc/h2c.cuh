@@ -145,6 +145,19 @@ DG_FN void sha_stream(sha_state& s, uint32_t L, uint64_t pre_bytes, Get&& get) {
   }
 }
 
+// SHA-256 of len bytes at p: a round's randomness from its signature
+// (chain/beacon.go:51-54 RandomnessFromSignature; client/verify.go:207).
+DG_FN void sha256_bytes(uint8_t out[32], const uint8_t* p, uint32_t len) {
+  sha_state s = sha_init();
+  sha_stream(s, len, 0, [&](uint32_t pos) -> uint32_t { return p[pos]; });
+  for (int w = 0; w < 8; ++w) {
+    out[4 * w] = (uint8_t)(s.h[w] >> 24);
+    out[4 * w + 1] = (uint8_t)(s.h[w] >> 16);
+    out[4 * w + 2] = (uint8_t)(s.h[w] >> 8);
+    out[4 * w + 3] = (uint8_t)s.h[w];
+  }
+}
+
 // ================================================================ expand_message_xmd
 // DST bytes as big-endian words: "BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_NUL_" (43 bytes)
 // followed by I2OSP(43, 1): DST_prime = 44 bytes = 11 words.

@@ -98,24 +98,86 @@ struct msg_src {
   const uint32_t* msg_len;
 };
 
-__device__ __forceinline__ uint32_t clamp_len(uint32_t len, size_t stride) {
+// The linked form (dgpu_verify_segment) is a beacon record that is not
+// stored: the walk of client/verify.go:118-178 builds each beacon from the
+// signature before it, so item i of a slice whose first item is global item
+// g0 has g = g0 + i, round first_round + g, and as previous signature the
+// seed (carried by value: nothing of the caller's is read after the launch)
+// when g == 0, else signature g - 1 of the call's own signature array --
+// prev / prev_stride / prev_len are that array's *base*, whatever the slice,
+// because a slice's first item reads the record before the slice.
+//
+// A type of its own, selected at compile time: every kernel that takes a
+// message source is a template over it and reaches it only through
+// msg_bad_record / msg_digest / msg_expand.  Behind a run-time flag of
+// msg_src the seed's SHA-256 stream cost the explicit-record kernels 96 bytes
+// of scratch (k_h2c_field) and spills in the two G1 hash kernels
+// (profiles/r08/segment_resource_usage.txt); as instantiated for msg_src they
+// are the kernels they were.  The host holds every source as a
+// msg_src_linked (linked = 0: its msg_src part is the source).
+struct msg_src_linked : msg_src {
+  int linked;         // host-side selector of the instantiation; the device type is always linked
+  uint32_t seed_len;  // <= 96
+  uint64_t first_round;
+  size_t g0;
+  uint32_t seed[24];  // 96 bytes, byte k in bits 8 (k % 4) of word k / 4
+};
+
+DG_FN uint32_t clamp_len(uint32_t len, size_t stride) {
   return (size_t)len > stride ? (uint32_t)stride : len;
 }
 
-__device__ __forceinline__ bool msg_bad_record(const msg_src& m, size_t i) {
+// Round number of item i of a beacon source; whether its previous signature
+// is the linked form's seed; the index of the record that holds its previous
+// signature otherwise (i itself, or in the linked form the signature before
+// it, global item g - 1).
+DG_FN uint64_t msg_round(const msg_src& m, size_t i) { return m.rounds[i]; }
+DG_FN uint64_t msg_round(const msg_src_linked& m, size_t i) { return m.first_round + (m.g0 + i); }
+DG_FN bool msg_prev_is_seed(const msg_src&, size_t) { return false; }
+DG_FN bool msg_prev_is_seed(const msg_src_linked& m, size_t i) { return m.g0 + i == 0; }
+DG_FN size_t msg_prev_index(const msg_src&, size_t i) { return i; }
+DG_FN size_t msg_prev_index(const msg_src_linked& m, size_t i) { return m.g0 + i - 1; }
+
+// SHA-256(seed || BE64(round)): the digest of the linked form's first item.
+// The seed word is picked by selects over constant indices, not by an indexed
+// load (which would first copy the kernel argument to scratch).
+DG_FN void msg_seed_digest(const msg_src&, uint64_t, uint32_t*) {}
+DG_FN void msg_seed_digest(const msg_src_linked& m, uint64_t round, uint32_t msg[8]) {
+  const uint32_t plen = m.seed_len;
+  sha_state s = sha_init();
+  sha_stream(s, plen + 8, 0, [&](uint32_t pos) -> uint32_t {
+    if (pos >= plen) return (uint32_t)(round >> (8 * (7 - (pos - plen)))) & 0xffu;
+    uint32_t w = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 24; ++k) w = (pos >> 2) == k ? m.seed[k] : w;
+    return (w >> (8 * (pos & 3))) & 0xffu;
+  });
+  for (int w = 0; w < 8; ++w) msg[w] = s.h[w];
+}
+
+template <class Src>
+DG_FN bool msg_bad_record(const Src& m, size_t i) {
   if (m.msgs) return (size_t)m.msg_len[i] > m.msg_stride;
-  return m.chained && (size_t)m.prev_len[i] > m.prev_stride;
+  if (!m.chained || msg_prev_is_seed(m, i)) return false;
+  return (size_t)m.prev_len[msg_prev_index(m, i)] > m.prev_stride;
 }
 
 // drand digest of a beacon record (32 bytes as 8 big-endian words)
-__device__ __forceinline__ void msg_digest(const msg_src& m, size_t i, uint32_t msg[8]) {
-  const uint32_t plen = m.chained ? clamp_len(m.prev_len[i], m.prev_stride) : 0u;
-  drand_digest(msg, m.chained ? m.prev + i * m.prev_stride : nullptr, plen, m.rounds[i]);
+template <class Src>
+DG_FN void msg_digest(const Src& m, size_t i, uint32_t msg[8]) {
+  const uint64_t round = msg_round(m, i);
+  if (m.chained && msg_prev_is_seed(m, i)) {
+    msg_seed_digest(m, round, msg);
+    return;
+  }
+  const size_t j = m.chained ? msg_prev_index(m, i) : 0;
+  const uint32_t plen = m.chained ? clamp_len(m.prev_len[j], m.prev_stride) : 0u;
+  drand_digest(msg, m.chained ? m.prev + j * m.prev_stride : nullptr, plen, round);
 }
 
 // expand_message_xmd of item i's message under DST G1DST with ELL 32-byte blocks
-template <bool G1DST, int ELL>
-__device__ __forceinline__ void msg_expand(const msg_src& m, size_t i, uint32_t* uni) {
+template <bool G1DST, int ELL, class Src>
+DG_FN void msg_expand(const Src& m, size_t i, uint32_t* uni) {
   if (m.msgs) {
     expand_xmd_var<G1DST, ELL>(uni, m.msgs + i * m.msg_stride, clamp_len(m.msg_len[i], m.msg_stride));
   } else {
@@ -125,6 +187,7 @@ __device__ __forceinline__ void msg_expand(const msg_src& m, size_t i, uint32_t*
   }
 }
 
+#ifndef DG_NO_KERNELS  // (a host-only test program takes the message-source helpers alone)
 // ---------------------------------------------------------------- kernels
 // The per-round hash to G2 as three launches (the fused kernel needs 512
 // registers per lane -- one wave per SIMD -- and 6 KB of scratch; each stage
@@ -132,7 +195,8 @@ __device__ __forceinline__ void msg_expand(const msg_src& m, size_t i, uint32_t*
 //   k_h2c_field   message (DigestMessage or raw) + expand_message_xmd -> u0, u1 ([4 fp][n])
 //   k_h2c_sswu    SSWU + 3-isogeny of each of the 2n field elements -> Jacobian ([2][6 fp][n])
 //   k_h2c_finish  Q0 + Q1, cofactor clearing -> X, Y (h_out) and Z (z_out)
-__global__ void __launch_bounds__(256) k_h2c_field(size_t n, msg_src m, uint32_t* __restrict__ u_out) {
+template <class Src>
+__global__ void __launch_bounds__(256) k_h2c_field(size_t n, Src m, uint32_t* __restrict__ u_out) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   uint32_t uni[64];
@@ -339,8 +403,9 @@ __global__ void __launch_bounds__(256) k_digest(size_t n, const uint64_t* __rest
 // decode error without its signature being read.  check_subgroup = 0: the
 // membership test is left to the pairing engine's lines kernel (the Miller
 // loop's ladder of the signature gives [x] sig for free, k_eng_lines).
+template <class Src>
 __global__ void __launch_bounds__(256, 4) k_decode_g2_sigs(size_t n, const uint8_t* __restrict__ sigs, size_t sig_stride,
-                                                         const uint32_t* __restrict__ sig_len, msg_src m,
+                                                         const uint32_t* __restrict__ sig_len, Src m,
                                                          int check_subgroup, uint32_t* __restrict__ sig_out,
                                                          uint8_t* __restrict__ status) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -365,9 +430,10 @@ __global__ void __launch_bounds__(256, 4) k_decode_g2_sigs(size_t n, const uint8
 // the kernel at 2 waves/SIMD -- out of line in g2_decompress its registers
 // escaped the kernel's budget (4.6 KB of scratch at 4 waves/SIMD): 389.6 ->
 // 360.2 ms per 10M (tools/engbench/dec_g2.hip, profiles/r04/r04f_dec_g2_variants.txt).
+template <class Src>
 __global__ void __launch_bounds__(256, 2) k_decode_g2_sigs_sub(size_t n, const uint8_t* __restrict__ sigs,
                                                              size_t sig_stride, const uint32_t* __restrict__ sig_len,
-                                                             msg_src m, uint32_t* __restrict__ sig_out,
+                                                             Src m, uint32_t* __restrict__ sig_out,
                                                              uint8_t* __restrict__ status) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -486,6 +552,23 @@ __global__ void k_pack_verdicts(size_t n, const uint8_t* __restrict__ status, ui
   bits[j] = b;
 }
 
+// Randomness of the verified rounds (dgpu_verify_segment, after the status is
+// final): out32 + 32 i = SHA-256 of round i's signature where status[i] ==
+// ST_OK (its length is then exactly the scheme's 48 or 96 bytes, within the
+// stride), 32 zero bytes otherwise.
+__global__ void __launch_bounds__(256) k_randomness(size_t n, const uint8_t* __restrict__ sigs, size_t sig_stride,
+                                                     const uint32_t* __restrict__ sig_len,
+                                                     const uint8_t* __restrict__ status, uint8_t* __restrict__ out32) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint8_t* o = out32 + i * 32;
+  if (status[i] == ST_OK) {
+    sha256_bytes(o, sigs + i * sig_stride, clamp_len(sig_len[i], sig_stride));
+  } else {
+    for (int k = 0; k < 32; ++k) o[k] = 0;
+  }
+}
+
 // nonzero bytes -> bitmap (bit = 1 where ok[i] != 0): recovery verdicts
 __global__ void k_pack_ok(size_t n, const uint8_t* __restrict__ ok, uint8_t* __restrict__ bits) {
   size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -527,5 +610,7 @@ __global__ void __launch_bounds__(256) k_fp_soa_to_be48(size_t n, int nfp, const
   if (neg_first && j == 0) v = fp_neg(v);
   fp_std_to_be48(fp_from_mont(v), out + t * 48);
 }
+
+#endif  // DG_NO_KERNELS
 
 }  // namespace dgpu

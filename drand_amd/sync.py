@@ -340,3 +340,37 @@ def trusted_previous_signature(verifier, pubkey, get_signature, genesis_seed, ro
     if trust_round == round_ - 1 and trust_round > initial:
         new_pot = (trust_round, trust_sig)
     return trust_sig, new_pot
+
+
+def trusted_previous_signature_segments(verifier, pubkey, get_signatures, genesis_seed, round_, point_of_trust=None,
+                                        window=1 << 14, mode=0):
+    """trusted_previous_signature (client/verify.go:118-178) over the linked
+    segment form: same contract and return value, but a window is fetched
+    with one `get_signatures(lo, hi)` call -- the signatures of rounds lo ..
+    hi inclusive, in order (raise to signal a fetch error) -- and verified
+    with `verifier.verify_segment(lo, sigs, trust_sig, pubkey, mode)`, which
+    derives each round's number and previous signature from the window
+    itself: no Beacon objects, no second copy of the signatures.  Raises
+    VerifyError at the first invalid round, the point of trust unchanged."""
+    from .chain import VerifyError
+    if round_ == 1:
+        return genesis_seed, point_of_trust
+    if point_of_trust is None or point_of_trust[0] > round_:
+        trust_round, trust_sig = 1, genesis_seed  # slow path: from round 1
+    else:
+        trust_round, trust_sig = point_of_trust
+    initial = trust_round
+    new_pot = point_of_trust
+    while trust_round < round_ - 1:
+        lo, hi = trust_round + 1, min(round_ - 1, trust_round + window)
+        sigs = list(get_signatures(lo, hi))
+        if len(sigs) != hi - lo + 1:
+            raise ValueError(f"get_signatures({lo}, {hi}) returned {len(sigs)} signatures")
+        reasons, _ = verifier.verify_segment(lo, sigs, trust_sig, pubkey, mode, randomness=False)
+        for k, rs in enumerate(reasons):
+            if int(rs) != 0:
+                raise VerifyError(lo + k, int(rs))
+        trust_round, trust_sig = hi, bytes(sigs[-1])
+    if trust_round == round_ - 1 and trust_round > initial:
+        new_pot = (trust_round, trust_sig)
+    return trust_sig, new_pot

@@ -60,7 +60,9 @@ extern "C" {
  * recovery for the G1-signature schemes -- dgpu_set_group_scheme,
  * dgpu_multi_set_group_scheme, dgpu_make_partials_scheme; the recover entry
  * points follow the installed group's scheme (their out_sigs96 parameters
- * are now out_sigs, stride 96 or 48 bytes per round). */
+ * are now out_sigs, stride 96 or 48 bytes per round).  Also additive:
+ * dgpu_verify_segment and dgpu_verify_segment_device, a linked chain segment
+ * verified from its signatures alone, with the rounds' randomness. */
 #define DGPU_ABI_VERSION 3
 
 /* scheme IDs (common/scheme/scheme.go:9,12; bls-unchained-on-g1 added by this build) */
@@ -162,6 +164,44 @@ int dgpu_verify_beacons_device(dgpu_ctx *ctx, int scheme, const uint8_t *pk, siz
                                const uint32_t *d_prev_len, int mode, uint64_t rlc_seed, uint8_t *d_verdict_bits,
                                uint8_t *d_reason, void *stream);
 
+/* A linked chain segment verified from its signatures alone: the walk from a
+ * point of trust, client/verify.go:118-178, which builds each beacon as
+ * {PreviousSig: the signature before it, Round, Signature} and (line 207)
+ * takes the verified round's randomness, chain/beacon.go:51-54
+ * RandomnessFromSignature = SHA-256(signature).  The caller passes the first
+ * round, the n signatures (records as dgpu_verify_beacons: sig_len[i] bytes
+ * at sigs + i*sig_stride) and one seed "previous signature" (host pointer,
+ * seed_prev_len <= 96 bytes, else DGPU_EINVAL; may be NULL with length 0; it
+ * is copied before the call returns, in the _device form too); round numbers
+ * and previous signatures are derived on the device.  Verdict bits and
+ * reasons equal dgpu_verify_beacons_device on the records
+ *   rounds[i] = first_round + i          (first_round + n - 1 must not
+ *                                         overflow 64 bits: DGPU_EINVAL)
+ *   prev[0] = seed_prev, prev_len[0] = seed_prev_len
+ *   prev[i] = sigs[i-1], prev_len[i] = sig_len[i-1], prev_stride = sig_stride
+ * under the same key, mode and rlc_seed, so the first zero bit is where the
+ * reference's walk returns "verifying beacon".  A sig_len[i] above sig_stride
+ * is a decode failure of round i and (chained scheme) of round i + 1, never
+ * an argument error, in both forms.  The unchained and G1-signature schemes
+ * ignore previous signatures: only the implicit round numbers apply.
+ * randomness32 (optional, n x 32 bytes): SHA-256 of round i's signature where
+ * round i verifies, 32 zero bytes where it does not.
+ * The host form stages each signature once -- n x (sig_stride + 4) bytes
+ * (dgpu_staging_stats), where the explicit records of a chained scheme take
+ * n x (2 sig_stride + 16) -- and returns the randomness with the verdicts. */
+int dgpu_verify_segment(dgpu_ctx *ctx, int scheme, const uint8_t *pk, size_t pk_len, uint64_t first_round, size_t n,
+                        const uint8_t *sigs, size_t sig_stride, const uint32_t *sig_len, const uint8_t *seed_prev,
+                        size_t seed_prev_len, int mode, uint64_t rlc_seed, uint8_t *verdict_bits, uint8_t *reason,
+                        uint8_t *randomness32);
+
+/* dgpu_verify_segment over device-resident signatures, asynchronous on
+ * `stream` (as dgpu_verify_beacons_device); seed_prev is a host pointer, like
+ * pk, and may be freed on return. */
+int dgpu_verify_segment_device(dgpu_ctx *ctx, int scheme, const uint8_t *pk, size_t pk_len, uint64_t first_round,
+                               size_t n, const uint8_t *d_sigs, size_t sig_stride, const uint32_t *d_sig_len,
+                               const uint8_t *seed_prev, size_t seed_prev_len, int mode, uint64_t rlc_seed,
+                               uint8_t *d_verdict_bits, uint8_t *d_reason, uint8_t *d_randomness32, void *stream);
+
 /* Per-rank RLC protocol for callers that run one process (or one context)
  * per GPU and exchange data themselves -- the multi-process form of
  * dgpu_verify_multi's RLC mode (chain/beacon/sync_manager.go:188-222 sharded
@@ -234,7 +274,8 @@ int dgpu_verify_batch_device(dgpu_ctx *ctx, int scheme, size_t n, const uint64_t
  * per kernel stage on the stream it runs on; dgpu_stage_times writes the
  * stage durations (ms) and names of the last call, summed per name over
  * chunks (per-round mode: hash_to_g2, h_affine, decode_g2, eng_lines,
- * eng_miller, eng_inv, eng_fe, eng_fe_chain, eng_fe_kbinv, pack_verdicts; G1
+ * eng_miller, eng_inv, eng_fe, eng_fe_chain, eng_fe_kbinv, pack_verdicts,
+ * randomness (dgpu_verify_segment with a randomness buffer); G1
  * signatures: hash_to_g1, h_affine, decode_g1, eng_miller (eng_lines_fixed
  * first under DGPU_G1_LINES=buffer), ...; RLC mode: rlc_hash_to_g2_raw /
  * rlc_hash_to_g1_raw, decode_g2 / decode_g1, rlc_affine, rlc_root_msm,

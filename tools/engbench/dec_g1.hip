@@ -116,7 +116,7 @@ int main(int argc, char** argv) {
     printf("%-28s %8.3f ms per %zu  (%.1f ms per 10M)  status mismatches %zu\n", name, ms, n, ms * 1e7 / n, bad);
     return 0;
   };
-  float t = timeit([&] { hipLaunchKernelGGL(k_decode_g1_sigs, g, b, 0, 0, n, sigs, (size_t)48, len, m, out, st); }, 5);
+  float t = timeit([&] { hipLaunchKernelGGL(k_decode_g1_sigs<msg_src>, g, b, 0, 0, n, sigs, (size_t)48, len, m, out, st); }, 5);
   CK(hipMemcpy(ref.data(), st, n, hipMemcpyDeviceToHost));
   size_t ok = 0;
   for (size_t i = 0; i < n; ++i) ok += ref[i] == ST_OK;

@@ -75,7 +75,7 @@ int main(int argc, char** argv) {
   msg_src m{};
   const dim3 g((n + 255) / 256), b(256);
   std::vector<uint8_t> ref(n), got(n);
-  float t = timeit([&] { hipLaunchKernelGGL(k_decode_g2_sigs, g, b, 0, 0, n, sigs, (size_t)96, len, m, 1, out, st); }, 5);
+  float t = timeit([&] { hipLaunchKernelGGL(k_decode_g2_sigs<msg_src>, g, b, 0, 0, n, sigs, (size_t)96, len, m, 1, out, st); }, 5);
   CK(hipMemcpy(ref.data(), st, n, hipMemcpyDeviceToHost));
   size_t ok = 0;
   for (size_t i = 0; i < n; ++i) ok += ref[i] == ST_OK;
