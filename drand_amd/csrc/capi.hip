@@ -1248,14 +1248,19 @@ int g2_lane_hash_locked(dgpu_ctx* c, const lane_bufs& L, size_t n, const msg_src
                         size_t slice = 0) {
   const unsigned B = 256;
   int rc;
+  // h_tmp: u, q, then k_h2c_finish's park region (whole 64-round blocks; the
+  // 896 n bytes before it keep it 16-byte aligned) and its n redo flags
+  const size_t uq_words = n * (4 + 12) * FP_WORDS;
   if ((rc = L.h_pts->ensure(n * G2A_WORDS * 4)) || (rc = L.sig_pts->ensure(n * G2A_WORDS * 4)) ||
       (rc = L.h_z->ensure(n * 2 * FP_WORDS * 4)) || (rc = L.h_pre->ensure(n * FP_WORDS * 4)) ||
-      (rc = L.h_tmp->ensure(n * (4 + 12) * FP_WORDS * 4)))
+      (rc = L.h_tmp->ensure((uq_words + h2c_park_words(n)) * 4 + n)))
     return rc;
   uint32_t* h = (uint32_t*)L.h_pts->p;
   uint32_t* sg = (uint32_t*)L.sig_pts->p;
   uint32_t* u = (uint32_t*)L.h_tmp->p;
   uint32_t* q = u + 4 * FP_WORDS * n;
+  uint32_t* park = u + uq_words;
+  uint8_t* redo = (uint8_t*)(park + h2c_park_words(n));
   // membership of the signature: checked by the lines kernel (eng_pairing_locked sig_subgroup)
   auto decode = [&](hipStream_t sd) {
     with_src(m, [&](const auto& ms) {
@@ -1321,7 +1326,10 @@ int g2_lane_hash_locked(dgpu_ctx* c, const lane_bufs& L, size_t n, const msg_src
     if (side) HIP_TRY(hipStreamWaitEvent(s, c->cof_ev[1], 0));
     hipLaunchKernelGGL(k_cof_final, dim3(grid_for(n, B)), dim3(B), 0, s, n, (const uint32_t*)w, h, (uint32_t*)L.h_z->p);
   } else {
-    hipLaunchKernelGGL(k_h2c_finish, dim3(grid_for(n, B)), dim3(B), 0, s, n, q, h,
+    hipLaunchKernelGGL(k_h2c_finish, dim3(grid_for(n, B)), dim3(B), 0, s, n, (const uint32_t*)q, park, redo, h,
+                       (uint32_t*)L.h_z->p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_h2c_finish_redo, dim3(grid_for(n, B)), dim3(B), 0, s, n, (const uint8_t*)redo, park, h,
                        (uint32_t*)L.h_z->p);
   }
   HIP_TRY(hipGetLastError());

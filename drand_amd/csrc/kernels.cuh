@@ -187,7 +187,78 @@ DG_FN void msg_expand(const Src& m, size_t i, uint32_t* uni) {
   }
 }
 
-#ifndef DG_NO_KERNELS  // (a host-only test program takes the message-source helpers alone)
+// ---------------------------------------------------------------- k_h2c_finish's park region
+// The three point slots of g2_clear_cofactor_stash as a register extension in
+// HBM, blocked by wave: a block is 64 consecutive rounds, and slot k (0..2) of
+// a block holds each round's 84 words (w = coord * 28 + comp * 14 + limb) as
+// 21 quads, [block][slot][quad][lane][4].  One wave's point is 21 KB
+// contiguous and an Fp2 coordinate (28 words = 7 quads) moves as seven
+// 16-byte accesses per lane, 1 KB per wave each -- where the round's own SoA
+// words ([coord][limb][n]) cost 84 dword accesses to planes 4n bytes apart on
+// every fetch of the ladder's critical path.
+constexpr int PARK_LANES = 64;
+constexpr int PARK_SLOTS = 3;
+constexpr int PARK_COORD_QUADS = 2 * FP_WORDS / 4;  // 7
+constexpr int PARK_QUADS = 3 * PARK_COORD_QUADS;    // 21
+static_assert(2 * FP_WORDS % 4 == 0, "an Fp2 coordinate is a whole number of quads");
+// word offset of word w (0..83) of round i's slot k
+DG_FN size_t h2c_park_word(size_t i, int k, int w) {
+  return ((((i / PARK_LANES) * PARK_SLOTS + k) * PARK_QUADS + w / 4) * PARK_LANES + i % PARK_LANES) * 4 + w % 4;
+}
+// words of the region for n rounds: whole blocks, so the last partial block
+// lies inside it for every n (sized per round it would not: DESIGN 2b')
+DG_FN size_t h2c_park_words(size_t n) {
+  return (n + PARK_LANES - 1) / PARK_LANES * PARK_LANES * (size_t)(PARK_SLOTS * G2J_WORDS);
+}
+
+struct h2c_finish_stash {
+  uint32_t* park;  // 16-byte aligned, h2c_park_words(n) words
+  size_t i;
+  // word j (0..27) of an Fp2 coordinate: c0's limbs, then c1's
+  static DG_FN uint32_t& word(fp2& a, int j) { return j < FP_WORDS ? a.c0.l[j] : a.c1.l[j - FP_WORDS]; }
+  static DG_FN void st_coord(uint4* q, fp2 a) {
+#pragma unroll
+    for (int t = 0; t < PARK_COORD_QUADS; ++t)
+      q[(size_t)t * PARK_LANES] = make_uint4(word(a, 4 * t), word(a, 4 * t + 1), word(a, 4 * t + 2), word(a, 4 * t + 3));
+  }
+  static DG_FN fp2 ld_coord(const uint4* q) {
+    fp2 a;
+#pragma unroll
+    for (int t = 0; t < PARK_COORD_QUADS; ++t) {
+      const uint4 v = q[(size_t)t * PARK_LANES];
+      word(a, 4 * t) = v.x, word(a, 4 * t + 1) = v.y, word(a, 4 * t + 2) = v.z, word(a, 4 * t + 3) = v.w;
+    }
+    return a;
+  }
+  struct fetch {  // slot k's coordinates, each loaded where g2_add_nx_q uses it
+    const uint4* q;  // the round's quad 0 of the slot
+    DG_FN fp2 x() const { return ld_coord(q); }
+    DG_FN fp2 y() const { return ld_coord(q + (size_t)PARK_COORD_QUADS * PARK_LANES); }
+    DG_FN fp2 z() const { return ld_coord(q + (size_t)2 * PARK_COORD_QUADS * PARK_LANES); }
+  };
+  DG_FN uint4* slot(uint32_t* base, int k) const { return (uint4*)(base + h2c_park_word(i, k, 0)); }
+  DG_FN void put(int k, const g2j& p) {
+    uint4* q = slot(park, k);
+    st_coord(q, p.x);
+    st_coord(q + (size_t)PARK_COORD_QUADS * PARK_LANES, p.y);
+    st_coord(q + (size_t)2 * PARK_COORD_QUADS * PARK_LANES, p.z);
+  }
+  // (the base passes through an empty asm: the slot is re-read at each
+  // addition instead of hoisted out of the ladder and spilled)
+  DG_FN fetch at(int k) const {
+    uint32_t* b = park;
+#ifdef __HIP_DEVICE_COMPILE__
+    __asm__ volatile("" : "+s"(b));
+#endif
+    return fetch{slot(b, k)};
+  }
+  DG_FN g2j get(int k) const {
+    const fetch f{slot(park, k)};
+    return g2j{f.x(), f.y(), f.z()};
+  }
+};
+
+#ifndef DG_NO_KERNELS  // (a host-only test program takes the helpers above alone)
 // ---------------------------------------------------------------- kernels
 // The per-round hash to G2 as three launches (the fused kernel needs 512
 // registers per lane -- one wave per SIMD -- and 6 KB of scratch; each stage
@@ -259,66 +330,38 @@ __device__ __forceinline__ bool g2_in_subgroup_stored(const g2a& p, uint32_t* pt
   return exc || DG_FORCE_EXC ? g2_in_subgroup(g2_from_affine(f.get())) : in;
 }
 
-// Point slots of g2_clear_cofactor_stash in the round's own SoA words: 0, 1 =
-// the two SSWU outputs' slots of q (each read once, before it is written),
-// 2 = the output slot (X, Y in h_out, Z in z_out).
-struct h2c_finish_stash {
-  uint32_t* q;
-  uint32_t* h_out;
-  uint32_t* z_out;
-  size_t n, i;
-  __device__ __forceinline__ void put(int k, const g2j& p) {
-    if (k < 2) {
-      st_g2j(q + (size_t)k * G2J_WORDS * n, n, i, p);
-    } else {
-      st_g2a(h_out, n, i, g2a{p.x, p.y});
-      st_fp(z_out, n, i, p.z.c0);
-      st_fp(z_out + FP_WORDS * n, n, i, p.z.c1);
-    }
-  }
-  struct fetch {  // slot k's coordinates, each loaded where g2_add_nx_q uses it
-    const uint32_t* xy;
-    const uint32_t* zp;
-    size_t n, i;
-    __device__ __forceinline__ fp2 x() const { return fp2{ld_fp(xy, n, i), ld_fp(xy + FP_WORDS * n, n, i)}; }
-    __device__ __forceinline__ fp2 y() const {
-      return fp2{ld_fp(xy + 2 * FP_WORDS * n, n, i), ld_fp(xy + 3 * FP_WORDS * n, n, i)};
-    }
-    __device__ __forceinline__ fp2 z() const { return fp2{ld_fp(zp, n, i), ld_fp(zp + FP_WORDS * n, n, i)}; }
-  };
-  // (the bases pass through an empty asm: the slot is re-read at each
-  // addition instead of hoisted out of the ladder and spilled)
-  __device__ __forceinline__ fetch at(int k) const {
-    const uint32_t* qb = q;
-    const uint32_t* hb = h_out;
-    const uint32_t* zb = z_out;
-#ifdef __HIP_DEVICE_COMPILE__
-    __asm__ volatile("" : "+s"(qb), "+s"(hb), "+s"(zb));
-#endif
-    const uint32_t* xy = k < 2 ? qb + (size_t)k * G2J_WORDS * n : hb;
-    return fetch{xy, k < 2 ? xy + 4 * FP_WORDS * n : zb, n, i};
-  }
-  __device__ __forceinline__ g2j get(int k) const {
-    if (k < 2) return ld_g2j(q + (size_t)k * G2J_WORDS * n, n, i);
-    const g2a a = ld_g2a(h_out, n, i);
-    return g2j{a.x, a.y, fp2{ld_fp(z_out, n, i), ld_fp(z_out + FP_WORDS * n, n, i)}};
-  }
-};
-
 // Q0 + Q1 and the cofactor clearing, its cold points parked in HBM (one
 // point live per [|x|] ladder, no call sites in the loops; VERDICT r05 item
-// 3).  An exceptional addition on the fast path (Q0 = +-Q1, a small-order
-// point, ...) redoes the round with the generic g2_clear_cofactor from P,
-// which slot 0 still holds.  Overwrites q.
-__global__ void __launch_bounds__(256, DG_FINISH_OCC) k_h2c_finish(size_t n, uint32_t* __restrict__ q,
+// 3) in the wave-blocked slots of `park` (h2c_finish_stash).  An exceptional
+// addition on the fast path (Q0 = +-Q1, a small-order point, ...) flags the
+// round in `redo`, and k_h2c_finish_redo recomputes it from P, which slot 0
+// still holds.  The redo is a kernel of its own because a kernel is allotted
+// the registers of everything it can call: g2_clear_cofactor and
+// g2_clear_cofactor_generic take 256 and 32 accumulation registers, and with
+// the call in this kernel it ran at one wave per SIMD instead of two
+// (profiles/r09/finish_pmc_change.txt: 65.2 against 45.9 ms per 1M rounds).
+__device__ __forceinline__ void st_h2c_out(uint32_t* h_out, uint32_t* z_out, size_t n, size_t i, const g2j& h) {
+  st_g2a(h_out, n, i, g2a{h.x, h.y});
+  st_fp(z_out, n, i, h.z.c0);
+  st_fp(z_out + FP_WORDS * n, n, i, h.z.c1);
+}
+__global__ void __launch_bounds__(256, DG_FINISH_OCC) k_h2c_finish(size_t n, const uint32_t* __restrict__ q,
+                                                     uint32_t* __restrict__ park, uint8_t* __restrict__ redo,
                                                      uint32_t* __restrict__ h_out, uint32_t* __restrict__ z_out) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  h2c_finish_stash st{q, h_out, z_out, n, i};
+  h2c_finish_stash st{park, i};
   bool exc = false;
-  g2j h = g2_clear_cofactor_stash(ld_g2j(q, n, i), ld_g2j(q + G2J_WORDS * n, n, i), st, exc);
-  if (exc || DG_FORCE_EXC) h = DG_FORCE_EXC ? g2_clear_cofactor_generic(st.get(0)) : g2_clear_cofactor(st.get(0));
-  st.put(2, h);
+  const g2j h = g2_clear_cofactor_stash(ld_g2j(q, n, i), ld_g2j(q + G2J_WORDS * n, n, i), st, exc);
+  redo[i] = exc || DG_FORCE_EXC;
+  st_h2c_out(h_out, z_out, n, i, h);
+}
+__global__ void __launch_bounds__(256) k_h2c_finish_redo(size_t n, const uint8_t* __restrict__ redo, uint32_t* park,
+                                                         uint32_t* __restrict__ h_out, uint32_t* __restrict__ z_out) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || !redo[i]) return;
+  const h2c_finish_stash st{park, i};
+  st_h2c_out(h_out, z_out, n, i, DG_FORCE_EXC ? g2_clear_cofactor_generic(st.get(0)) : g2_clear_cofactor(st.get(0)));
 }
 
 // RLC mode's pre-cofactor hash point R = Q0 + Q1 (Jacobian, [6 fp][n]) from
