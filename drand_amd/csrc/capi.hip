@@ -30,6 +30,7 @@
 #include "g1sig.cuh"
 #include "rlc_msm.cuh"
 #include "recover_g1.cuh"
+#include "scratch_layouts.h"
 
 using namespace dgpu;
 
@@ -104,6 +105,16 @@ struct DevBuf {
   }
 };
 
+// Size, allocate and carve a buffer with more than one region: the layout's
+// one fill() (scratch_layouts.h) gives the bytes and then the pointers.
+template <class L, class... D>
+int carve(DevBuf& b, L* lay, D... dims) {
+  int rc = b.ensure(layout_bytes<L>(dims...));
+  if (rc) return rc;
+  *lay = layout_at<L>(b.p, dims...);
+  return DGPU_OK;
+}
+
 inline unsigned grid_for(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
 
 // SplitMix64 step on the host: independent RLC seeds derived from a call's
@@ -130,14 +141,6 @@ inline bool scheme_known(int scheme) { return scheme >= DGPU_SCHEME_CHAINED && s
 // at most half the free HBM (two lanes x ~53 KB per round = 112 GB at 1Mi).
 constexpr size_t ENG_CHUNK = 1048576;
 constexpr size_t ENG_CHUNK_MIN = 16384;
-// Karabina FE state per round and lane: the planes (t, t2, m, six stored
-// values), the product of the six norms + its prefix products (k_eng_inv),
-// the six excluded products, the flag and the fallback list entry
-constexpr size_t ENG_KB_XWORDS = (size_t)ENG_KB_PLANES * 12 * FP_LIMBS;
-constexpr size_t ENG_KB_BYTES_PER_ROUND = ENG_KB_XWORDS * 4 + (2 + (size_t)ENG_KB_NSNAP) * FP_LIMBS * 4 + 1 + 4;
-// engine bytes per round and lane: line buffer + f planes + N1 + Karabina state
-constexpr size_t ENG_BYTES_PER_ROUND =
-    (size_t)ENG_LINE_STEPS * FP_LIMBS * 12 * 4 + 2 * FP_LIMBS * 12 * 4 + FP_LIMBS * 4 + ENG_KB_BYTES_PER_ROUND;
 // per-round G2 batches of at least this many rounds run on two lanes
 constexpr size_t LANE_MIN = 262144;
 // decoded public keys cached per context (chain/verify.go:38 passes the key per call)
@@ -149,9 +152,12 @@ constexpr int STAGE_COPY_THREADS = 8;
 
 // Per-round G2 path scratch of one "lane" (a stream working on a contiguous
 // slice of the batch).  Two lanes overlap one slice's register-bound hash /
-// decode kernels with the other slice's LDS-bound pairing engine.
-struct lane_bufs {
-  DevBuf *h_pts, *sig_pts, *h_z, *h_pre, *h_tmp, *lines, *f, *n1, *kb;
+// decode kernels with the other slice's LDS-bound pairing engine.  Lane 0 is
+// also the context's general scratch (RLC, recovery, the G1 path).
+struct lane_scratch {
+  DevBuf h_pts, sig_pts, h_z, h_pre, h_tmp;
+  // pairing engine (per-round mode): per-chunk lines / f / norms / Karabina state
+  DevBuf lines, f, n1, kb;
 };
 
 // One decoded public key: the engine's block constants carry its pairing
@@ -242,7 +248,8 @@ struct dgpu_ctx {
   // engine block constants without a key (recovery: per-item keys)
   DevBuf eng_consts;
   // scratch
-  DevBuf h_pts, sig_pts, status, h_z, h_pre, h_tmp;
+  lane_scratch lane[2];
+  DevBuf status;
   // RLC mode: pre-cofactor hash points, segment-tree levels, bisection scratch
   DevBuf rlc_tree, rlc_idx, rlc_fail, rlc_h, rlc_s, rlc_st, rlc_root;
   // localize-then-confirm: the confirmation root + compacted list, the marked rounds' leaf sums
@@ -250,10 +257,6 @@ struct dgpu_ctx {
   // RLC root by bucket MSM (rlc_msm.cuh): AoS points, flags, counts / offsets /
   // cursors, bucket lists, bucket sums, per-run window sums
   DevBuf msm_aos, msm_flags, msm_counts, msm_list, msm_buckets, msm_runs, msm_root, msm_part;
-  // pairing engine (per-round mode): per-chunk lines / f / norms
-  DevBuf eng_lines, eng_f, eng_n1, eng_kb;
-  // second lane's scratch (same roles as h_pts .. eng_kb)
-  DevBuf l2_h_pts, l2_sig_pts, l2_h_z, l2_h_pre, l2_h_tmp, l2_lines, l2_f, l2_n1, l2_kb;
   bool fe_gs = false;            // DGPU_FE=gs: the Granger-Scott FE kernel instead of the Karabina chain (A/B)
   size_t fe_gs_max = 16384;      // DGPU_FE_GS_MAX=<items>: pairing calls up to this size take the Granger-Scott FE
                                  // (one launch, no batched inversions: the latency path; 0 = always Karabina)
@@ -444,17 +447,15 @@ int upload_eng_consts(DevBuf* dst, const g1_key* key, bool unit_points = false) 
 // Decode a 48-byte G1 key into e (public-key decode of InfoFromProto,
 // chain/convert.go:20-23); synchronous on the context's stream.
 int decode_g1_key_locked(dgpu_ctx* c, key_entry* e, const uint8_t* pk) {
-  int rc = c->misc.ensure(256);
+  g1_key_misc M;
+  int rc = carve(c->misc, &M);
   if (rc) return rc;
   hipStream_t s = c->stream;
-  uint8_t* d = (uint8_t*)c->misc.p;
-  HIP_TRY(hipMemcpyAsync(d, pk, 48, hipMemcpyHostToDevice, s));
-  uint32_t* d_out = (uint32_t*)(d + 64);
-  int* d_rc = (int*)(d + 64 + 2 * FP_LIMBS * 4);
-  hipLaunchKernelGGL(k_decode_g1_pk, dim3(1), dim3(64), 0, s, d, d_out, d_rc);
+  HIP_TRY(hipMemcpyAsync(M.in, pk, 48, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_decode_g1_pk, dim3(1), dim3(64), 0, s, M.in, M.out, M.rc);
   HIP_TRY(hipGetLastError());
-  uint32_t host[2 * FP_LIMBS + 1];
-  HIP_TRY(hipMemcpyAsync(host, d_out, sizeof host, hipMemcpyDeviceToHost, s));
+  uint32_t host[2 * FP_LIMBS + 1];  // out and, next to it, rc
+  HIP_TRY(hipMemcpyAsync(host, M.out, sizeof host, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   const int drc = (int)host[2 * FP_LIMBS];
   if (drc != DEC_OK) return set_err(DGPU_EINVAL, "public key rejected (decode code %d)", drc);
@@ -467,16 +468,14 @@ int decode_g1_key_locked(dgpu_ctx* c, key_entry* e, const uint8_t* pk) {
 // line table: the LINES program for (pk, g2) at P = (1, 1).
 int decode_g2_key_locked(dgpu_ctx* c, key_entry* e, const uint8_t* pk) {
   int rc;
-  const size_t tbl_words = (size_t)ENG_LINE_STEPS * FP_LIMBS * ENG_WAVE_WORDS;
-  if ((rc = e->table.ensure(tbl_words * 4)) || (rc = c->misc.ensure(4096))) return rc;
+  g2_key_misc M;
+  if ((rc = e->table.ensure(eng_blk_words(1, ENG_LINE_STEPS) * 4)) || (rc = carve(c->misc, &M))) return rc;
   if ((rc = upload_eng_consts(&e->consts, nullptr))) return rc;
   DevBuf unit;  // read by k_eng_lines below, which every return path after its launch waits for
   if ((rc = upload_eng_consts(&unit, nullptr, true))) return rc;
-  uint8_t* aux = (uint8_t*)c->misc.p;
-  uint32_t* d_pk = (uint32_t*)aux;           // affine G2, stride 1 (224 B)
-  uint32_t* d_g2 = (uint32_t*)(aux + 1024);  // generator, stride 1
-  int* d_rc = (int*)(aux + 2048);
-  uint8_t* d_in = aux + 3072;
+  uint32_t *const d_pk = M.pk, *const d_g2 = M.g2;
+  int* const d_rc = M.rc;
+  uint8_t* const d_in = M.in;
   g2a gen{C_G2_X, C_G2_Y};
   uint32_t gw[G2A_WORDS];
   memcpy(gw, gen.x.c0.l, 56);
@@ -547,17 +546,13 @@ int get_key_locked(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t len, key_e
 // one thread per round inverting and decompressing -- measured slower, r04j,
 // and removed in round 6); last, the Granger-Scott kernel for the listed
 // blocks with a flagged item.  capb: the chunk capacity
-// rounded up to whole blocks of 5 rounds (>= cnt); kb: ENG_KB_BYTES_PER_ROUND
-// x capb bytes.
+// rounded up to whole blocks of 5 rounds (>= cnt); kb: the chunk's state,
+// carved for capb / 5 blocks.
 int eng_fe_kb_locked(dgpu_ctx* c, const uint32_t* consts, size_t cnt, size_t capb, size_t r0, uint32_t* f,
-                     const uint32_t* n1inv, uint8_t* kb, uint8_t* st, hipStream_t s) {
+                     const uint32_t* n1inv, const eng_kb_layout& kb, uint8_t* st, hipStream_t s) {
   if (capb % ENG_ROUNDS_PER_BLOCK || cnt > capb) return set_err(DGPU_EINVAL, "karabina FE: bad chunk capacity");
-  uint32_t* xbuf = (uint32_t*)kb;  // [capb / 5 blocks][ENG_KB_PLANES][limb][60]
-  uint32_t* pbuf = xbuf + ENG_KB_XWORDS * capb;
-  uint32_t* pre = pbuf + (size_t)FP_LIMBS * capb;
-  uint32_t* ebuf = pre + (size_t)FP_LIMBS * capb;
-  uint32_t* fb = ebuf + (size_t)ENG_KB_NSNAP * FP_LIMBS * capb;
-  uint8_t* flags = (uint8_t*)(fb + capb);
+  uint32_t *const xbuf = kb.xbuf, *const pbuf = kb.pbuf, *const pre = kb.pre, *const ebuf = kb.ebuf, *const fb = kb.fb;
+  uint8_t* const flags = kb.flags;
   const unsigned blocks = grid_for(cnt, ENG_ROUNDS_PER_BLOCK);
   const size_t inv_threads = std::max<size_t>(1, (cnt + c->kb_inv_chain - 1) / c->kb_inv_chain);
   constexpr int nseg = (int)(sizeof(ENG_PROG_FEK_OFF) / sizeof(ENG_PROG_FEK_OFF[0])) - 1;
@@ -626,7 +621,7 @@ struct pairing_job {
   const uint32_t* h_idx = nullptr;   // item i's hash point index (null: i)
   const uint32_t* pk_items = nullptr;     // a G1 key per item (recovery)
   const uint32_t* fixed_table = nullptr;  // G1 signatures: the key's fixed-Q line table
-  const lane_bufs* lanes = nullptr;       // the lane's engine scratch (null: the context's first)
+  lane_scratch* lane = nullptr;           // the lane's engine scratch (null: lane 0)
   bool sig_subgroup = false;              // the lines kernel checks the signatures' G2 membership
   const uint32_t* g1form_keys = nullptr;  // G1 signatures: a G2 key per item (recovery)
 };
@@ -641,31 +636,28 @@ int eng_pairing_locked(dgpu_ctx* c, const pairing_job& job, hipStream_t s) {
   uint8_t* const st = job.st;
   const size_t h_stride = job.h_stride ? job.h_stride : n;
   const uint32_t *const h_idx = job.h_idx, *const pk_items = job.pk_items, *const fixed_table = job.fixed_table;
-  const lane_bufs* const L = job.lanes;
+  lane_scratch& L = job.lane ? *job.lane : c->lane[0];
   const bool sig_subgroup = job.sig_subgroup;
   const uint32_t* const g1form_keys = job.g1form_keys;
-  DevBuf* b_lines = L ? L->lines : &c->eng_lines;
-  DevBuf* b_f = L ? L->f : &c->eng_f;
-  DevBuf* b_n1 = L ? L->n1 : &c->eng_n1;
-  DevBuf* b_kb = L ? L->kb : &c->eng_kb;
   const bool need_lines = !(fixed_table && c->fused_fixed);
   // small calls: the Granger-Scott FE (one launch; the Karabina side's five
   // chain / norm / batched-inversion / decompression rounds are latency there)
   const bool fe_gs = c->fe_gs || n <= c->fe_gs_max;
   int rc;
   size_t cap = 0, cap_blk = 0;
+  eng_kb_layout kb{};
   bool retried = false;
   for (;;) {
     // equal chunks of at most eng_chunk items (whole 5-item blocks): no short tail launch
     const size_t nchunks = (n + c->eng_chunk - 1) / c->eng_chunk;
     cap = (n + nchunks - 1) / nchunks;
     cap = std::min(n, (cap + ENG_ROUNDS_PER_BLOCK - 1) / ENG_ROUNDS_PER_BLOCK * ENG_ROUNDS_PER_BLOCK);
-    cap_blk = (cap + ENG_ROUNDS_PER_BLOCK - 1) / ENG_ROUNDS_PER_BLOCK;  // blocked layouts
+    cap_blk = eng_blocks(cap);  // blocked layouts
     // the Karabina planes are wave-blocked: whole blocks of 5 rounds (cap may be n, not a multiple of 5)
-    rc = fe_gs ? DGPU_OK : b_kb->ensure(cap_blk * ENG_ROUNDS_PER_BLOCK * ENG_KB_BYTES_PER_ROUND);
-    if (!rc && need_lines) rc = b_lines->ensure(cap_blk * (size_t)ENG_LINE_STEPS * FP_LIMBS * ENG_WAVE_WORDS * 4);
-    if (!rc) rc = b_f->ensure(cap_blk * 2 * FP_LIMBS * ENG_WAVE_WORDS * 4);
-    if (!rc) rc = b_n1->ensure(cap * FP_LIMBS * 4);
+    rc = fe_gs ? DGPU_OK : carve(L.kb, &kb, cap_blk);
+    if (!rc && need_lines) rc = L.lines.ensure(eng_blk_words(cap_blk, ENG_LINE_STEPS) * 4);
+    if (!rc) rc = L.f.ensure(eng_blk_words(cap_blk, ENG_F_PLANES) * 4);
+    if (!rc) rc = L.n1.ensure(eng_n1_words(cap) * 4);
     if (rc != DGPU_ENOMEM || c->eng_chunk <= ENG_CHUNK_MIN || cap <= ENG_CHUNK_MIN) break;
     // HBM is shared (other contexts, torch): the chunk was sized from the free
     // memory at dgpu_open; halve it for this context and retry.
@@ -674,21 +666,23 @@ int eng_pairing_locked(dgpu_ctx* c, const pairing_job& job, hipStream_t s) {
     HIP_TRY(hipStreamSynchronize(s));
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream2));
-    for (DevBuf* b : {b_kb, b_lines, b_f, b_n1}) b->release();
+    for (DevBuf* b : {&L.kb, &L.lines, &L.f, &L.n1}) b->release();
     c->eng_chunk = std::max(ENG_CHUNK_MIN, c->eng_chunk / 2);
     ++c->chunk_retries;
     retried = true;
   }
   if (rc) return rc;
   if (retried) g_last_error.clear();  // the failed attempt's message is stale
-  // k_eng_inv's prefix products reuse the line buffer (or f, on the fused path)
-  uint32_t* lines = need_lines ? (uint32_t*)b_lines->p : nullptr;
-  uint32_t* f = (uint32_t*)b_f->p;
-  uint32_t* n1 = (uint32_t*)b_n1->p;
+  // k_eng_inv's prefix products (eng_n1_words(cap)) reuse the line buffer: they fit
+  // in its cap_blk blocks (scratch_layouts.h's static_assert); the fused path has
+  // no line buffer and sizes lane 0's for them alone
+  uint32_t* lines = need_lines ? (uint32_t*)L.lines.p : nullptr;
+  uint32_t* f = (uint32_t*)L.f.p;
+  uint32_t* n1 = (uint32_t*)L.n1.p;
   uint32_t* pre = need_lines ? lines : nullptr;
   if (!pre) {
-    if ((rc = c->eng_lines.ensure(cap * FP_LIMBS * 4))) return rc;
-    pre = (uint32_t*)c->eng_lines.p;
+    if ((rc = c->lane[0].lines.ensure(eng_n1_words(cap) * 4))) return rc;
+    pre = (uint32_t*)c->lane[0].lines.p;
   }
   for (size_t r0 = 0; r0 < n; r0 += cap) {
     const size_t cnt = std::min(cap, n - r0);
@@ -739,8 +733,7 @@ int eng_pairing_locked(dgpu_ctx* c, const pairing_job& job, hipStream_t s) {
       mark(c, s, "eng_fe");
       hipLaunchKernelGGL(k_eng_fe, dim3(blocks), dim3(ENG_BLOCK), 0, s, cnt, r0, consts, f, n1, st);
       HIP_TRY(hipGetLastError());
-    } else if ((rc = eng_fe_kb_locked(c, consts, cnt, cap_blk * ENG_ROUNDS_PER_BLOCK, r0, f, n1, (uint8_t*)b_kb->p,
-                                      st, s))) {
+    } else if ((rc = eng_fe_kb_locked(c, consts, cnt, cap_blk * ENG_ROUNDS_PER_BLOCK, r0, f, n1, kb, st, s))) {
       return rc;
     }
   }
@@ -749,11 +742,7 @@ int eng_pairing_locked(dgpu_ctx* c, const pairing_job& job, hipStream_t s) {
 
 // ---------------------------------------------------------------- RLC
 // The segment trees of one RLC batch (level l: P[l], S[l], sz[l] nodes).
-struct rlc_trees {
-  std::vector<size_t> sz;
-  std::vector<uint32_t*> P, S;
-  int top() const { return (int)sz.size() - 1; }
-};
+using rlc_trees = sum_levels;
 
 // Word sizes of one signature group's points in the RLC buffers.
 struct rlc_geom {
@@ -769,18 +758,11 @@ hipError_t launch_sswu(size_t n, const uint32_t* u, uint32_t* q, hipStream_t s) 
   return hipGetLastError();
 }
 
-size_t rlc_tree_points(size_t n) {
-  size_t total = 0;
-  for (size_t v = n;; v = (v + 1) / 2) {
-    total += v;
-    if (v <= 1) break;
-  }
-  return total;
-}
-
-uint32_t* rlc_rpts(dgpu_ctx* c, size_t n, int jw) {
-  // R_i after the two trees' levels: the layout rlc_tree_t keeps
-  return (uint32_t*)c->rlc_tree.p + 2 * rlc_tree_points(n) * jw;
+// rlc_tree of a batch of n rounds: the trees' levels and the points R_i.
+// rlc_points_locked allocates it; the later stages of the batch carve the
+// same buffer again (same n, same group: nothing is reallocated).
+int rlc_tree_carve(dgpu_ctx* c, size_t n, const rlc_geom& G, rlc_tree_layout* t) {
+  return carve(c->rlc_tree, t, n, G.aw, G.jw);
 }
 
 // RLC phase 1: R_i = pre-cofactor H(m_i) (affine, in rlc_tree's tail),
@@ -793,16 +775,18 @@ int rlc_points_locked(dgpu_ctx* c, const verify_args& a, hipStream_t s) {
   const size_t n = a.n;
   const rlc_geom G = rlc_geom_of(sig_on_g1(a.scheme));
   int rc;
-  if ((rc = c->rlc_tree.ensure(2 * rlc_tree_points(n) * G.jw * 4 + n * G.jw * 4))) return rc;
-  if ((rc = c->sig_pts.ensure(n * G.aw * 4)) || (rc = c->h_pre.ensure(n * FP_WORDS * 4))) return rc;
-  uint32_t* rpts = rlc_rpts(c, n, G.jw);
-  uint32_t* sg = (uint32_t*)c->sig_pts.p;
+  lane_scratch& L = c->lane[0];
+  rlc_tree_layout tree;
+  if ((rc = rlc_tree_carve(c, n, G, &tree))) return rc;
+  if ((rc = L.sig_pts.ensure(n * G.aw * 4)) || (rc = L.h_pre.ensure(n * FP_WORDS * 4))) return rc;
+  uint32_t* const rpts = tree.rpts;
+  uint32_t* sg = (uint32_t*)L.sig_pts.p;
   uint8_t* st = (uint8_t*)c->status.p;
   if (G.g1) {
     mark(c, s, "rlc_hash_to_g1_raw");
     with_src(a.m, [&](const auto& m) {
       hipLaunchKernelGGL(SRC_KERNEL(k_hash_to_g1_raw, m), dim3(grid_for(n, B)), dim3(B), 0, s, n, m,
-                         a.scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, rpts, rpts + 2 * FP_WORDS * n);
+                         a.scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, rpts, tree.rz);
     });
     HIP_TRY(hipGetLastError());
     mark(c, s, "decode_g1");
@@ -813,16 +797,16 @@ int rlc_points_locked(dgpu_ctx* c, const verify_args& a, hipStream_t s) {
     HIP_TRY(hipGetLastError());
     mark(c, s, "rlc_affine");
     hipLaunchKernelGGL(k_g1_batch_affine, dim3(grid_for((n + 15) / 16, B)), dim3(B), 0, s, n, rpts,
-                       (const uint32_t*)(rpts + 2 * FP_WORDS * n), (uint32_t*)c->h_pre.p);
+                       (const uint32_t*)tree.rz, (uint32_t*)L.h_pre.p);
     HIP_TRY(hipGetLastError());
     return DGPU_OK;
   }
-  if ((rc = c->h_tmp.ensure(n * (4 + 12) * FP_WORDS * 4))) return rc;
+  h2c_tmp_layout tmp;
+  if ((rc = carve(L.h_tmp, &tmp, n, false))) return rc;
   mark(c, s, "rlc_hash_to_g2_raw");
   {
     // the per-round hash's field and SSWU stages, then Q0 + Q1 without the cofactor
-    uint32_t* u = (uint32_t*)c->h_tmp.p;
-    uint32_t* q = u + 4 * FP_WORDS * n;
+    uint32_t *const u = tmp.u, *const q = tmp.q;
     with_src(a.m, [&](const auto& m) {
       hipLaunchKernelGGL(SRC_KERNEL(k_h2c_field, m), dim3(grid_for(n, B)), dim3(B), 0, s, n, m, u);
     });
@@ -840,7 +824,7 @@ int rlc_points_locked(dgpu_ctx* c, const verify_args& a, hipStream_t s) {
   mark(c, s, "rlc_affine");
   // R_i to affine in place (X, Y slots; Z follows them in the Jacobian SoA)
   hipLaunchKernelGGL(k_g2_batch_affine, dim3(grid_for((n + 15) / 16, B)), dim3(B), 0, s, n, rpts,
-                     (const uint32_t*)(rpts + 4 * FP_WORDS * n), (uint32_t*)c->h_pre.p);
+                     (const uint32_t*)tree.rz, (uint32_t*)L.h_pre.p);
   HIP_TRY(hipGetLastError());
   return DGPU_OK;
 }
@@ -848,31 +832,33 @@ int rlc_points_locked(dgpu_ctx* c, const verify_args& a, hipStream_t s) {
 // RLC root by bucket MSM (rlc_msm.cuh) into root (P then S, stride-1
 // Jacobian of the signature group).  Asynchronous on s.
 template <class Gr>
-int rlc_root_msm_t(dgpu_ctx* c, const verify_args& a, hipStream_t s, uint32_t* root, const char* stage) {
+int rlc_root_msm_t(dgpu_ctx* c, const verify_args& a, hipStream_t s, const rlc_root_layout& root, const char* stage) {
   using M = GrMem<Gr>;
   const unsigned B = 256;
   const size_t n = a.n;
   // list positions and bucket offsets are 32-bit: up to MSM_MW entries per round
   if (n > 0xFFFFFFFFull / MSM_MW) return set_err(DGPU_EINVAL, "RLC batch too large for one MSM (%zu rounds)", n);
   int rc;
-  if ((rc = c->msm_aos.ensure(2 * n * M::AFF * 4)) || (rc = c->msm_flags.ensure(n)) ||
-      (rc = c->msm_counts.ensure(3 * MSM_KEYS * 4)) || (rc = c->msm_list.ensure(2 * MSM_MW * n * 4 + 4)) ||
-      (rc = c->msm_buckets.ensure(MSM_KEYS * M::JAC * 4)) ||
-      (rc = c->msm_runs.ensure(2 * (size_t)MSM_MW * MSM_RUNS * M::JAC * 4)))
+  rlc_tree_layout tree;
+  msm_counts_layout mc;
+  msm_list_layout ml;
+  msm_runs_layout mr;
+  if ((rc = rlc_tree_carve(c, n, rlc_geom_of(sig_on_g1(a.scheme)), &tree)) ||
+      (rc = c->msm_aos.ensure(2 * n * M::AFF * 4)) || (rc = c->msm_flags.ensure(n)) ||
+      (rc = carve(c->msm_counts, &mc)) || (rc = carve(c->msm_list, &ml, n)) ||
+      (rc = c->msm_buckets.ensure(MSM_KEYS * M::JAC * 4)) || (rc = carve(c->msm_runs, &mr, M::JAC)))
     return rc;
   uint32_t* aos = (uint32_t*)c->msm_aos.p;
   uint8_t* flags = (uint8_t*)c->msm_flags.p;
-  uint32_t* counts = (uint32_t*)c->msm_counts.p;
-  uint32_t* offsets = counts + MSM_KEYS;
-  uint32_t* cursor = offsets + MSM_KEYS;
-  uint32_t* list = (uint32_t*)c->msm_list.p;
-  uint32_t* keys = c->msm_seg ? list + MSM_MW * n : nullptr;  // the key of every list entry
+  uint32_t *const counts = mc.counts, *const offsets = mc.offsets, *const cursor = mc.cursor;
+  uint32_t* const list = ml.list;
+  uint32_t* const keys = c->msm_seg ? ml.keys : nullptr;  // the key of every list entry
   // load-balanced sums: 4 SIMDs x 2 resident waves (launch bounds 256, 2) per CU
   const size_t seg_threads = (size_t)c->n_cu * 4 * 2 * 64;
   if (c->msm_seg && (rc = c->msm_part.ensure(2 * seg_threads * M::JAC * 4))) return rc;
   mark(c, s, stage);
-  hipLaunchKernelGGL(k_msm_aos<Gr>, dim3(grid_for(n, B)), dim3(B), 0, s, n, (const uint32_t*)rlc_rpts(c, n, M::JAC),
-                     (const uint32_t*)c->sig_pts.p, (const uint8_t*)c->status.p, aos, flags);
+  hipLaunchKernelGGL(k_msm_aos<Gr>, dim3(grid_for(n, B)), dim3(B), 0, s, n, (const uint32_t*)tree.rpts,
+                     (const uint32_t*)c->lane[0].sig_pts.p, (const uint8_t*)c->status.p, aos, flags);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemsetAsync(counts, 0, MSM_KEYS * 4, s));
   hipLaunchKernelGGL(k_msm_count, dim3(grid_for(n, B)), dim3(B), 0, s, n, a.seed, (const uint8_t*)flags, counts);
@@ -896,8 +882,7 @@ int rlc_root_msm_t(dgpu_ctx* c, const verify_args& a, hipStream_t s, uint32_t* r
                        (const uint32_t*)counts, (const uint32_t*)list, (const uint32_t*)aos, buckets);
   }
   HIP_TRY(hipGetLastError());
-  uint32_t* runs = (uint32_t*)c->msm_runs.p;
-  uint32_t* runs2 = runs + (size_t)MSM_MW * MSM_RUNS * M::JAC;
+  uint32_t *runs = mr.runs, *runs2 = mr.runs2;
   hipLaunchKernelGGL(k_msm_window<Gr>, dim3(grid_for((size_t)MSM_MW * MSM_RUNS, B)), dim3(B), 0, s,
                      (const uint32_t*)buckets, runs);
   HIP_TRY(hipGetLastError());
@@ -910,13 +895,18 @@ int rlc_root_msm_t(dgpu_ctx* c, const verify_args& a, hipStream_t s, uint32_t* r
     std::swap(runs, runs2);
     len = nl;
   }
-  hipLaunchKernelGGL(k_msm_root<Gr>, dim3(1), dim3(64), 0, s, (const uint32_t*)runs, root, root + M::JAC);
+  hipLaunchKernelGGL(k_msm_root<Gr>, dim3(1), dim3(64), 0, s, (const uint32_t*)runs, root.P, root.S);
   HIP_TRY(hipGetLastError());
   return DGPU_OK;
 }
 
-int rlc_root_msm_locked(dgpu_ctx* c, const verify_args& a, hipStream_t s, uint32_t* root,
+// The root goes to `dst` (rlc_root_layout: P then S).
+int rlc_root_msm_locked(dgpu_ctx* c, const verify_args& a, hipStream_t s, DevBuf& dst, rlc_root_layout* out = nullptr,
                         const char* stage = "rlc_root_msm") {
+  rlc_root_layout root;
+  int rc = carve(dst, &root, rlc_geom_of(sig_on_g1(a.scheme)).jw);
+  if (rc) return rc;
+  if (out) *out = root;
   return sig_on_g1(a.scheme) ? rlc_root_msm_t<G1Ops>(c, a, s, root, stage)
                              : rlc_root_msm_t<G2Ops>(c, a, s, root, stage);
 }
@@ -926,32 +916,23 @@ int rlc_root_msm_locked(dgpu_ctx* c, const verify_args& a, hipStream_t s, uint32
 // built from rlc_points_locked's points.  Asynchronous on s.
 template <class Gr>
 int rlc_tree_t(dgpu_ctx* c, const verify_args& a, hipStream_t s, rlc_trees& T, bool plain) {
-  using M = GrMem<Gr>;
   const unsigned B = 256;
   const size_t n = a.n;
-  T.sz.assign(1, n);
-  while (T.sz.back() > 1) T.sz.push_back((T.sz.back() + 1) / 2);
-  uint32_t* tree = (uint32_t*)c->rlc_tree.p;
-  T.P.assign(T.sz.size(), nullptr);
-  T.S.assign(T.sz.size(), nullptr);
-  size_t off = 0;
-  for (size_t l = 0; l < T.sz.size(); ++l) {
-    T.P[l] = tree + off;
-    off += T.sz[l] * M::JAC;
-    T.S[l] = tree + off;
-    off += T.sz[l] * M::JAC;
-  }
+  rlc_tree_layout tree;
+  int rc = rlc_tree_carve(c, n, rlc_geom_of(sig_on_g1(a.scheme)), &tree);
+  if (rc) return rc;
+  T = tree.T;
   mark(c, s, plain ? "rlc_plain_tree" : "rlc_leaves_tree");
   if (plain)
     hipLaunchKernelGGL(k_rlc_leaves_plain<Gr>, dim3(grid_for(2 * n, B)), dim3(B), 0, s, n,
-                       (const uint32_t*)rlc_rpts(c, n, M::JAC), (const uint32_t*)c->sig_pts.p,
+                       (const uint32_t*)tree.rpts, (const uint32_t*)c->lane[0].sig_pts.p,
                        (const uint8_t*)c->status.p, T.P[0], T.S[0]);
   else
     hipLaunchKernelGGL(k_rlc_leaves<Gr>, dim3(grid_for(2 * n, B)), dim3(B), 0, s, n, a.seed,
-                       (const uint32_t*)rlc_rpts(c, n, M::JAC), (const uint32_t*)c->sig_pts.p,
+                       (const uint32_t*)tree.rpts, (const uint32_t*)c->lane[0].sig_pts.p,
                        (const uint8_t*)c->status.p, T.P[0], T.S[0]);
   HIP_TRY(hipGetLastError());
-  for (size_t l = 0; l + 1 < T.sz.size(); ++l) {
+  for (int l = 0; l < T.top(); ++l) {
     hipLaunchKernelGGL(k_rlc_level<Gr>, dim3(grid_for(2 * T.sz[l + 1], B)), dim3(B), 0, s, T.sz[l], T.P[l], T.S[l],
                        T.sz[l + 1], T.P[l + 1], T.S[l + 1]);
     HIP_TRY(hipGetLastError());
@@ -1097,17 +1078,20 @@ int rlc_descend_locked(dgpu_ctx* c, const key_entry* key, const rlc_trees& T, hi
 //  3. Only if the confirmation fails: the random-coefficient tree (leaves
 //     [a] R + [b] endo(R)) over what is left, descended as before.
 template <class Gr>
-int rlc_confirm_t(dgpu_ctx* c, const key_entry* key, const verify_args& a, hipStream_t s, const uint32_t* shard_root,
-                  const std::vector<uint32_t>& leaf_cand, bool* ok) {
+int rlc_confirm_t(dgpu_ctx* c, const key_entry* key, const verify_args& a, hipStream_t s,
+                  const rlc_root_layout& shard_root, const std::vector<uint32_t>& leaf_cand, bool* ok) {
   using M = GrMem<Gr>;
   const unsigned B = 256;
   int rc;
   mark(c, s, "rlc_confirm");
   const size_t mc = leaf_cand.size();
-  if ((rc = c->rlc_conf.ensure((mc + 1) * 4 + 2 * (size_t)M::JAC * 4))) return rc;
-  uint32_t* conf = (uint32_t*)c->rlc_conf.p;       // confirmation root (P, S)
-  uint32_t* count = conf + 2 * M::JAC;             // compaction counter, then the list
-  uint32_t* list = count + 1;
+  rlc_conf_layout cf;
+  rlc_tree_layout tree;
+  if ((rc = carve(c->rlc_conf, &cf, mc, M::JAC)) ||
+      (rc = rlc_tree_carve(c, a.n, rlc_geom_of(sig_on_g1(a.scheme)), &tree)))
+    return rc;
+  const rlc_root_layout& conf = cf.root;  // confirmation root
+  uint32_t *const count = cf.count, *const list = cf.list;
   uint32_t nf = 0;
   if (mc) {
     HIP_TRY(hipMemsetAsync(count, 0, 4, s));
@@ -1117,45 +1101,38 @@ int rlc_confirm_t(dgpu_ctx* c, const key_entry* key, const verify_args& a, hipSt
     HIP_TRY(hipMemcpyAsync(&nf, count, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
   }
-  const uint32_t* fsum = nullptr;
   if (nf) {  // the marked rounds' leaves, summed pairwise to one (P, S)
-    std::vector<size_t> sz{nf};
-    while (sz.back() > 1) sz.push_back((sz.back() + 1) / 2);
-    size_t words = 0;
-    for (size_t v : sz) words += 2 * v * M::JAC;
-    if ((rc = c->rlc_fsum.ensure(words * 4))) return rc;
-    uint32_t* lv = (uint32_t*)c->rlc_fsum.p;
+    sum_levels F;
+    if ((rc = carve(c->rlc_fsum, &F, (size_t)nf, M::JAC))) return rc;
     hipLaunchKernelGGL(k_rlc_leaves_list<Gr>, dim3(grid_for(2 * (size_t)nf, B)), dim3(B), 0, s, (size_t)nf,
-                       (const uint32_t*)list, a.n, a.seed, (const uint32_t*)rlc_rpts(c, a.n, M::JAC),
-                       (const uint32_t*)c->sig_pts.p, lv, lv + (size_t)nf * M::JAC);
+                       (const uint32_t*)list, a.n, a.seed, (const uint32_t*)tree.rpts,
+                       (const uint32_t*)c->lane[0].sig_pts.p, F.P[0], F.S[0]);
     HIP_TRY(hipGetLastError());
-    for (size_t l = 0; l + 1 < sz.size(); ++l) {
-      uint32_t* nx = lv + 2 * sz[l] * M::JAC;
-      hipLaunchKernelGGL(k_rlc_level<Gr>, dim3(grid_for(2 * sz[l + 1], B)), dim3(B), 0, s, sz[l], lv,
-                         lv + sz[l] * M::JAC, sz[l + 1], nx, nx + sz[l + 1] * M::JAC);
+    for (int l = 0; l < F.top(); ++l) {
+      hipLaunchKernelGGL(k_rlc_level<Gr>, dim3(grid_for(2 * F.sz[l + 1], B)), dim3(B), 0, s, F.sz[l], F.P[l], F.S[l],
+                         F.sz[l + 1], F.P[l + 1], F.S[l + 1]);
       HIP_TRY(hipGetLastError());
-      lv = nx;
     }
-    fsum = lv;  // P at lv, S at lv + JAC (one node: stride 1)
-    hipLaunchKernelGGL(k_rlc_sub_root<Gr>, dim3(1), dim3(64), 0, s, shard_root, fsum, fsum + M::JAC, conf);
+    // (one node: stride 1; the kernel reads the shard's root and writes conf as P | S)
+    hipLaunchKernelGGL(k_rlc_sub_root<Gr>, dim3(1), dim3(64), 0, s, (const uint32_t*)shard_root.P,
+                       (const uint32_t*)F.P[F.top()], (const uint32_t*)F.S[F.top()], conf.P);
     HIP_TRY(hipGetLastError());
   } else {
-    HIP_TRY(hipMemcpyAsync(conf, shard_root, 2 * (size_t)M::JAC * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(conf.P, shard_root.P, layout_bytes<rlc_root_layout>(M::JAC), hipMemcpyDeviceToDevice, s));
   }
   std::vector<uint8_t> fail;
-  if ((rc = rlc_check_locked(c, key, std::vector<uint32_t>{0}, 1, conf, conf + M::JAC, s, &fail))) return rc;
+  if ((rc = rlc_check_locked(c, key, std::vector<uint32_t>{0}, 1, conf.P, conf.S, s, &fail))) return rc;
   *ok = !fail[0];
   return DGPU_OK;
 }
 
 int rlc_resolve_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a, hipStream_t s,
-                       const uint32_t* shard_root, bool root_failed) {
+                       const rlc_root_layout& shard_root, bool root_failed) {
   int rc;
   const bool g1 = sig_on_g1(a.scheme);
-  const int jw = rlc_geom_of(g1).jw;
   if (!root_failed) {
     std::vector<uint8_t> fail;
-    if ((rc = rlc_check_locked(c, key, std::vector<uint32_t>{0}, 1, shard_root, shard_root + jw, s, &fail))) return rc;
+    if ((rc = rlc_check_locked(c, key, std::vector<uint32_t>{0}, 1, shard_root.P, shard_root.S, s, &fail))) return rc;
     if (!fail[0]) return DGPU_OK;
   }
   rlc_trees T;
@@ -1178,11 +1155,12 @@ int verify_g1_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a, ui
   const unsigned B = 256;
   const size_t n = a.n;
   int rc;
-  if ((rc = c->h_pts.ensure(n * 2 * FP_WORDS * 4)) || (rc = c->sig_pts.ensure(n * 2 * FP_WORDS * 4)) ||
-      (rc = c->h_z.ensure(n * FP_WORDS * 4)) || (rc = c->h_pre.ensure(n * FP_WORDS * 4)))
+  lane_scratch& L = c->lane[0];
+  if ((rc = L.h_pts.ensure(n * 2 * FP_WORDS * 4)) || (rc = L.sig_pts.ensure(n * 2 * FP_WORDS * 4)) ||
+      (rc = L.h_z.ensure(n * FP_WORDS * 4)) || (rc = L.h_pre.ensure(n * FP_WORDS * 4)))
     return rc;
-  uint32_t* h = (uint32_t*)c->h_pts.p;
-  uint32_t* sg = (uint32_t*)c->sig_pts.p;
+  uint32_t* h = (uint32_t*)L.h_pts.p;
+  uint32_t* sg = (uint32_t*)L.sig_pts.p;
   // the signature decode beside the hash on the second stream (as the G2 path, g2_lane_hash_locked)
   const bool side = c->dec_overlap && c->lanes > 1 && !c->profile;
   side_join join(side ? c->stream2 : nullptr, s, c->lane_ev[1]);
@@ -1199,12 +1177,12 @@ int verify_g1_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a, ui
   mark(c, s, "hash_to_g1");
   with_src(a.m, [&](const auto& m) {
     hipLaunchKernelGGL(SRC_KERNEL(k_hash_to_g1_beacons, m), dim3(grid_for(n, B)), dim3(B), 0, s, n, m,
-                       a.scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, h, (uint32_t*)c->h_z.p);
+                       a.scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, h, (uint32_t*)L.h_z.p);
   });
   HIP_TRY(hipGetLastError());
   mark(c, s, "h_affine");
   hipLaunchKernelGGL(k_g1_batch_affine, dim3(grid_for((n + 15) / 16, B)), dim3(B), 0, s, n, h,
-                     (const uint32_t*)c->h_z.p, (uint32_t*)c->h_pre.p);
+                     (const uint32_t*)L.h_z.p, (uint32_t*)L.h_pre.p);
   HIP_TRY(hipGetLastError());
   if (side) {
     HIP_TRY(hipStreamWaitEvent(s, c->lane_ev[1], 0));
@@ -1242,25 +1220,21 @@ int stager_wait_all(host_stager* stg, hipStream_t s);
 // consts (the key's engine constants; optional): calls of at most
 // cof_engine_max rounds clear the cofactor on the engine ladder
 // (pairing_engine.cuh k_cof_*) instead of k_h2c_finish.
-int g2_lane_hash_locked(dgpu_ctx* c, const lane_bufs& L, size_t n, const msg_src_linked& m, const uint8_t* sigs,
+int g2_lane_hash_locked(dgpu_ctx* c, lane_scratch& L, size_t n, const msg_src_linked& m, const uint8_t* sigs,
                         size_t sig_stride, const uint32_t* sig_len, uint8_t* st, hipStream_t s,
                         hipStream_t s_dec = nullptr, const uint32_t* consts = nullptr, host_stager* stg = nullptr,
                         size_t slice = 0) {
   const unsigned B = 256;
   int rc;
-  // h_tmp: u, q, then k_h2c_finish's park region (whole 64-round blocks; the
-  // 896 n bytes before it keep it 16-byte aligned) and its n redo flags
-  const size_t uq_words = n * (4 + 12) * FP_WORDS;
-  if ((rc = L.h_pts->ensure(n * G2A_WORDS * 4)) || (rc = L.sig_pts->ensure(n * G2A_WORDS * 4)) ||
-      (rc = L.h_z->ensure(n * 2 * FP_WORDS * 4)) || (rc = L.h_pre->ensure(n * FP_WORDS * 4)) ||
-      (rc = L.h_tmp->ensure((uq_words + h2c_park_words(n)) * 4 + n)))
+  h2c_tmp_layout tmp;  // u, q, then k_h2c_finish's park region and its redo flags
+  if ((rc = L.h_pts.ensure(n * G2A_WORDS * 4)) || (rc = L.sig_pts.ensure(n * G2A_WORDS * 4)) ||
+      (rc = L.h_z.ensure(n * 2 * FP_WORDS * 4)) || (rc = L.h_pre.ensure(n * FP_WORDS * 4)) ||
+      (rc = carve(L.h_tmp, &tmp, n, true)))
     return rc;
-  uint32_t* h = (uint32_t*)L.h_pts->p;
-  uint32_t* sg = (uint32_t*)L.sig_pts->p;
-  uint32_t* u = (uint32_t*)L.h_tmp->p;
-  uint32_t* q = u + 4 * FP_WORDS * n;
-  uint32_t* park = u + uq_words;
-  uint8_t* redo = (uint8_t*)(park + h2c_park_words(n));
+  uint32_t* h = (uint32_t*)L.h_pts.p;
+  uint32_t* sg = (uint32_t*)L.sig_pts.p;
+  uint32_t *const u = tmp.u, *const q = tmp.q, *const park = tmp.park;
+  uint8_t* const redo = tmp.redo;
   // membership of the signature: checked by the lines kernel (eng_pairing_locked sig_subgroup)
   auto decode = [&](hipStream_t sd) {
     with_src(m, [&](const auto& ms) {
@@ -1275,8 +1249,9 @@ int g2_lane_hash_locked(dgpu_ctx* c, const lane_bufs& L, size_t n, const msg_src
   };
   const bool cof_engine = consts && n <= c->cof_engine_max;
   const unsigned cof_blocks = grid_for(n, ENG_ROUNDS_PER_BLOCK);
-  if (cof_engine && ((rc = c->cof_tmp.ensure((size_t)COF_PLANES * FP_WORDS * n * 4)) ||
-                     (rc = L.lines->ensure((size_t)cof_blocks * ENG_LINE_STEPS * FP_LIMBS * ENG_WAVE_WORDS * 4))))
+  cof_tmp_layout cof{};
+  if (cof_engine && ((rc = carve(c->cof_tmp, &cof, n)) ||
+                     (rc = L.lines.ensure(eng_blk_words(cof_blocks, ENG_LINE_STEPS) * 4))))
     return rc;  // allocated before the fork: a failure here leaves nothing on the side stream
   side_join join(s_dec, s, c->lane_ev[1]);
   if (s_dec) {  // first in the second stream's queue: it runs beside the whole hash chain
@@ -1294,13 +1269,10 @@ int g2_lane_hash_locked(dgpu_ctx* c, const lane_bufs& L, size_t n, const msg_src
   HIP_TRY(launch_sswu(n, u, q, s));
   if (cof_engine) {
     const unsigned blocks = cof_blocks;
-    uint32_t* w = (uint32_t*)c->cof_tmp.p;
-    uint32_t* pa = w + (size_t)G2J_WORDS * n;
-    uint32_t* psia = pa + (size_t)G2A_WORDS * n;
-    uint32_t* t1 = psia + (size_t)G2A_WORDS * n;
-    uint32_t* t0a = t1 + (size_t)12 * FP_WORDS * n;
-    uint32_t* t2 = t0a + (size_t)G2A_WORDS * n;
-    uint32_t* lines = (uint32_t*)L.lines->p;
+    // (the k_cof_* kernels take the planes' base and address them by COF_* themselves)
+    uint32_t *const w = cof.pj, *const pa = cof.pa, *const psia = cof.psia, *const t1 = cof.t1, *const t0a = cof.t0a,
+                    *const t2 = cof.t2;
+    uint32_t* lines = (uint32_t*)L.lines.p;
     hipLaunchKernelGGL(k_cof_prep, dim3(grid_for(n, B)), dim3(B), 0, s, n, (const uint32_t*)q, w);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_eng_lines, dim3(blocks), dim3(ENG_BLOCK), 0, s, n, (size_t)0, n,
@@ -1324,18 +1296,18 @@ int g2_lane_hash_locked(dgpu_ctx* c, const lane_bufs& L, size_t n, const msg_src
                        consts, lines, (uint8_t*)nullptr, t2);
     HIP_TRY(hipGetLastError());
     if (side) HIP_TRY(hipStreamWaitEvent(s, c->cof_ev[1], 0));
-    hipLaunchKernelGGL(k_cof_final, dim3(grid_for(n, B)), dim3(B), 0, s, n, (const uint32_t*)w, h, (uint32_t*)L.h_z->p);
+    hipLaunchKernelGGL(k_cof_final, dim3(grid_for(n, B)), dim3(B), 0, s, n, (const uint32_t*)w, h, (uint32_t*)L.h_z.p);
   } else {
     hipLaunchKernelGGL(k_h2c_finish, dim3(grid_for(n, B)), dim3(B), 0, s, n, (const uint32_t*)q, park, redo, h,
-                       (uint32_t*)L.h_z->p);
+                       (uint32_t*)L.h_z.p);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_h2c_finish_redo, dim3(grid_for(n, B)), dim3(B), 0, s, n, (const uint8_t*)redo, park, h,
-                       (uint32_t*)L.h_z->p);
+                       (uint32_t*)L.h_z.p);
   }
   HIP_TRY(hipGetLastError());
   mark(c, s, "h_affine");
   hipLaunchKernelGGL(k_g2_batch_affine, dim3(grid_for((n + 15) / 16, B)), dim3(B), 0, s, n, h,
-                     (const uint32_t*)L.h_z->p, (uint32_t*)L.h_pre->p);
+                     (const uint32_t*)L.h_z.p, (uint32_t*)L.h_pre.p);
   HIP_TRY(hipGetLastError());
   if (s_dec) {
     HIP_TRY(hipStreamWaitEvent(s, c->lane_ev[1], 0));  // the decode (queued first on s_dec)
@@ -1415,13 +1387,11 @@ int verify_status_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a
   c->rlc_pending = false;
   if (a.mode == DGPU_MODE_RLC && n >= c->rlc_min) {
     // root first, by bucket MSM; the tree of leaves only when it fails
-    const int jw = rlc_geom_of(sig_on_g1(a.scheme)).jw;
     if ((rc = stager_wait_all(stg, s)) || (rc = rlc_points_locked(c, a, s))) return rc;
-    if ((rc = c->rlc_root.ensure(2 * jw * 4))) return rc;
-    uint32_t* root = (uint32_t*)c->rlc_root.p;
-    if ((rc = rlc_root_msm_locked(c, a, s, root))) return rc;
+    rlc_root_layout root;
+    if ((rc = rlc_root_msm_locked(c, a, s, c->rlc_root, &root))) return rc;
     std::vector<uint8_t> fail;
-    if ((rc = rlc_check_locked(c, key, std::vector<uint32_t>{0}, 1, root, root + jw, s, &fail))) return rc;
+    if ((rc = rlc_check_locked(c, key, std::vector<uint32_t>{0}, 1, root.P, root.S, s, &fail))) return rc;
     if (!fail[0] || a.n == 1) {
       if (fail[0]) {  // one round: its leaf is the root
         hipLaunchKernelGGL(k_rlc_mark, dim3(1), dim3(64), 0, s, (size_t)1, (const uint32_t*)c->rlc_idx.p,
@@ -1434,10 +1404,7 @@ int verify_status_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a
   }
   if (sig_on_g1(a.scheme)) return (rc = stager_wait_all(stg, s)) ? rc : verify_g1_locked(c, key, a, st, s);
   const uint32_t* consts = (const uint32_t*)key->consts.p;
-  const lane_bufs L0{&c->h_pts, &c->sig_pts, &c->h_z,     &c->h_pre, &c->h_tmp,
-                     &c->eng_lines, &c->eng_f, &c->eng_n1, &c->eng_kb};
-  const lane_bufs L1{&c->l2_h_pts, &c->l2_sig_pts, &c->l2_h_z, &c->l2_h_pre, &c->l2_h_tmp,
-                     &c->l2_lines, &c->l2_f,      &c->l2_n1, &c->l2_kb};
+  lane_scratch &L0 = c->lane[0], &L1 = c->lane[1];
   // Two lanes (streams) on the two halves of the batch once it spans more
   // than one engine chunk; lane 1 starts when lane 0's hash/decode kernels
   // are done, so its register-bound hash runs beside lane 0's LDS-bound
@@ -1453,13 +1420,13 @@ int verify_status_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a
     return rc;
   const bool sub = !c->decode_subgroup;
   // one slice of the batch on one lane's buffers
-  auto slice_job = [&](const lane_bufs& L, size_t cnt, uint8_t* sst) {
+  auto slice_job = [&](lane_scratch& L, size_t cnt, uint8_t* sst) {
     return pairing_job{.consts = consts,
                        .n = cnt,
-                       .h = (const uint32_t*)L.h_pts->p,
-                       .sg = (const uint32_t*)L.sig_pts->p,
+                       .h = (const uint32_t*)L.h_pts.p,
+                       .sg = (const uint32_t*)L.sig_pts.p,
                        .st = sst,
-                       .lanes = &L,
+                       .lane = &L,
                        .sig_subgroup = sub};
   };
   if (!two) return eng_pairing_locked(c, slice_job(L0, n, st), s);
@@ -1470,7 +1437,7 @@ int verify_status_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a
   // the remaining slices alternate between the lanes (stream order keeps each
   // lane's buffers in use by one slice at a time), so a slice's hash runs
   // beside the other lane's engine chunks (DGPU_LANE_SLICES, default 2)
-  const lane_bufs* LL[2] = {&L0, &L1};
+  lane_scratch* LL[2] = {&L0, &L1};
   hipStream_t ss[2] = {s, s2};
   size_t k = 1;
   for (size_t off = n0; off < n; off += n0, ++k) {
@@ -1864,7 +1831,7 @@ int verify_host_pageable_locked(dgpu_ctx* c, const key_entry* key, verify_args a
 size_t size_engine_chunk(int lanes) {
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return ENG_CHUNK;
-  const size_t fit = free_b / 2 / ((size_t)std::max(lanes, 1) * ENG_BYTES_PER_ROUND);
+  const size_t fit = free_b / 2 / ((size_t)std::max(lanes, 1) * eng_bytes_per_round());
   return std::max(ENG_CHUNK_MIN, std::min(ENG_CHUNK, fit));
 }
 
@@ -2181,10 +2148,9 @@ int dgpu_rlc_root_device(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t pk_l
     if ((rc = c->status.ensure(n))) return rc;
     c->n_ev = 0;
     c->ev_overflow = false;
-    if ((rc = rlc_points_locked(c, a, s)) || (rc = c->msm_root.ensure(2 * (size_t)G.jw * 4)) ||
-        (rc = rlc_root_msm_locked(c, a, s, (uint32_t*)c->msm_root.p)))
-      return rc;
-    HIP_TRY(hipMemcpyAsync(d_root, c->msm_root.p, 2 * (size_t)G.jw * 4, hipMemcpyDeviceToDevice, s));
+    rlc_root_layout root;
+    if ((rc = rlc_points_locked(c, a, s)) || (rc = rlc_root_msm_locked(c, a, s, c->msm_root, &root))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_root, root.P, layout_bytes<rlc_root_layout>(G.jw), hipMemcpyDeviceToDevice, s));
   }
   c->rlc_args = a;
   memcpy(c->rlc_pk, pk, pk_len);
@@ -2208,21 +2174,21 @@ int dgpu_rlc_finish_device(dgpu_ctx* c, size_t n_roots, const uint8_t* d_roots, 
   hipStream_t s = caller_stream(stream);
   stream_order ord(c, s);
   const rlc_geom G = rlc_geom_of(sig_on_g1(a.scheme));
-  if ((rc = c->rlc_root.ensure(2 * (size_t)G.jw * 4))) return rc;
-  uint32_t* sum = (uint32_t*)c->rlc_root.p;
+  rlc_root_layout sum, shard;  // (the shard's root: dgpu_rlc_root_device left it in msm_root)
+  if ((rc = carve(c->rlc_root, &sum, G.jw)) || (rc = carve(c->msm_root, &shard, G.jw))) return rc;
   mark(c, s, "rlc_root_sum");
   if (G.g1)
-    hipLaunchKernelGGL(k_rlc_sum_roots<G1Ops>, dim3(1), dim3(64), 0, s, (int)n_roots, (const uint32_t*)d_roots, sum,
-                       sum + G.jw);
+    hipLaunchKernelGGL(k_rlc_sum_roots<G1Ops>, dim3(1), dim3(64), 0, s, (int)n_roots, (const uint32_t*)d_roots, sum.P,
+                       sum.S);
   else
-    hipLaunchKernelGGL(k_rlc_sum_roots<G2Ops>, dim3(1), dim3(64), 0, s, (int)n_roots, (const uint32_t*)d_roots, sum,
-                       sum + G.jw);
+    hipLaunchKernelGGL(k_rlc_sum_roots<G2Ops>, dim3(1), dim3(64), 0, s, (int)n_roots, (const uint32_t*)d_roots, sum.P,
+                       sum.S);
   HIP_TRY(hipGetLastError());
   std::vector<uint8_t> fail;
-  if ((rc = rlc_check_locked(c, k, std::vector<uint32_t>{0}, 1, sum, sum + G.jw, s, &fail))) return rc;
+  if ((rc = rlc_check_locked(c, k, std::vector<uint32_t>{0}, 1, sum.P, sum.S, s, &fail))) return rc;
   if (a.n == 0) return DGPU_OK;
   // this shard's verdicts, its own root first unless it is the node's (one root)
-  if (fail[0] && (rc = rlc_resolve_locked(c, k, a, s, (const uint32_t*)c->msm_root.p, n_roots == 1))) return rc;
+  if (fail[0] && (rc = rlc_resolve_locked(c, k, a, s, shard, n_roots == 1))) return rc;
   const uint8_t* st = (const uint8_t*)c->status.p;
   mark(c, s, "pack_verdicts");
   hipLaunchKernelGGL(k_pack_verdicts, dim3(grid_for((a.n + 7) / 8, 256)), dim3(256), 0, s, a.n, st, d_bits);
@@ -2430,10 +2396,11 @@ int dgpu_decode_g1_points(dgpu_ctx* c, size_t n, const uint8_t* in48, int* rc_ou
   hipStream_t s = c->stream;
   stream_order ord(c, s);
   int rc;
-  if ((rc = c->in_msgs.ensure(n * 48)) || (rc = c->misc.ensure(n * (4 + 96)))) return rc;
+  g1_points_misc M;
+  if ((rc = c->in_msgs.ensure(n * 48)) || (rc = carve(c->misc, &M, n))) return rc;
   HIP_TRY(hipMemcpyAsync(c->in_msgs.p, in48, n * 48, hipMemcpyHostToDevice, s));
-  int* d_rc = (int*)c->misc.p;
-  uint8_t* d_xy = (uint8_t*)c->misc.p + n * 4;
+  int* const d_rc = M.rc;
+  uint8_t* const d_xy = M.xy;
   hipLaunchKernelGGL(k_decode_g1_points, dim3(grid_for(n, 64)), dim3(64), 0, s, n, (const uint8_t*)c->in_msgs.p, d_rc,
                      d_xy);
   HIP_TRY(hipGetLastError());
@@ -2461,7 +2428,7 @@ int dgpu_decode_signatures(dgpu_ctx* c, int scheme, size_t n, const uint8_t* sig
   stream_order ord(c, s);
   int rc;
   if ((rc = c->in_sigs.ensure(n * sig_stride + 1)) || (rc = c->in_sig_len.ensure(n * 4)) ||
-      (rc = c->sig_pts.ensure(n * nfp * FP_WORDS * 4)) || (rc = c->status.ensure(n)) ||
+      (rc = c->lane[0].sig_pts.ensure(n * nfp * FP_WORDS * 4)) || (rc = c->status.ensure(n)) ||
       (rc = c->misc.ensure(n * nfp * 48)))
     return rc;
   if (sig_stride) HIP_TRY(hipMemcpyAsync(c->in_sigs.p, sigs, n * sig_stride, hipMemcpyHostToDevice, s));
@@ -2469,7 +2436,7 @@ int dgpu_decode_signatures(dgpu_ctx* c, int scheme, size_t n, const uint8_t* sig
   const msg_src m = beacon_src(nullptr, nullptr, 0, nullptr, false);  // no message part: never a bad record
   const uint8_t* d_sigs = (const uint8_t*)c->in_sigs.p;
   const uint32_t* d_len = (const uint32_t*)c->in_sig_len.p;
-  uint32_t* pts = (uint32_t*)c->sig_pts.p;
+  uint32_t* pts = (uint32_t*)c->lane[0].sig_pts.p;
   uint8_t* st = (uint8_t*)c->status.p;
   if (g1)
     hipLaunchKernelGGL(k_decode_g1_sigs<msg_src>, dim3(grid_for(n, 256)), dim3(256), 0, s, n, d_sigs, sig_stride, d_len, m, pts,
@@ -2501,12 +2468,11 @@ int dgpu_decode_pubkey(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t len, u
   hipStream_t s = c->stream;
   stream_order ord(c, s);
   int rc;
-  if ((rc = c->misc.ensure(4096))) return rc;
-  uint8_t* aux = (uint8_t*)c->misc.p;
-  uint8_t* d_in = aux;                      // 96 B
-  uint32_t* d_pt = (uint32_t*)(aux + 128);  // stride-1 affine point (<= 224 B)
-  int* d_rc = (int*)(aux + 512);
-  uint8_t* d_xy = aux + 1024;               // <= 192 B
+  pubkey_misc M;
+  if ((rc = carve(c->misc, &M))) return rc;
+  uint8_t *const d_in = M.in, *const d_xy = M.xy;
+  uint32_t* const d_pt = M.pt;
+  int* const d_rc = M.rc;
   HIP_TRY(hipMemcpyAsync(d_in, pk, want, hipMemcpyHostToDevice, s));
   if (g2key)
     hipLaunchKernelGGL(k_decode_g2_pk, dim3(1), dim3(64), 0, s, (const uint8_t*)d_in, d_pt, d_rc);

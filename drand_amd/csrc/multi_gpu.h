@@ -253,15 +253,17 @@ int dgpu_verify_multi(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_le
                           D > 1 ? splitmix_host(rlc_seed ^ (0x5EEDull * (uint64_t)(k + 1))) : rlc_seed};
     if ((rc = check_args(c, keys[k], args[k]))) return rc;
     multi_bufs& b = m->buf[k];
+    // (the roots: sized for either group's)
     if ((rc = b.bits.ensure(per / 8)) || (rc = b.reasons.ensure(per)) || (rc = b.all_bits.ensure(D * per / 8)) ||
-        (rc = b.all_reasons.ensure(D * per)) || (rc = b.root.ensure(2 * G2J_WORDS * 4)) ||
-        (rc = b.all_roots.ensure((size_t)D * 2 * G2J_WORDS * 4)))
+        (rc = b.all_reasons.ensure(D * per)) || (rc = b.root.ensure(layout_bytes<rlc_root_layout>(G2J_WORDS))) ||
+        (rc = b.all_roots.ensure((size_t)D * layout_bytes<rlc_root_layout>(G2J_WORDS))))
       return rc;
     HIP_TRY(hipStreamWaitEvent(c->stream, c->done, 0));
   }
   const bool rlc = mode == DGPU_MODE_RLC;
   const bool g1 = sig_on_g1(scheme);
-  const int jw = g1 ? G1J_WORDS : G2J_WORDS;  // root: P, S (stride-1 Jacobian of the signature group)
+  const int jw = g1 ? G1J_WORDS : G2J_WORDS;  // root: rlc_root_layout (P, S: stride-1 Jacobian of the signature group)
+  const size_t root_bytes = layout_bytes<rlc_root_layout>(jw);
   // phase 1: stage the shard (the records of the device's shard through its
   // context's pinned ring, overlapped with the verification) and verify it
   // per round (or compute its RLC root)
@@ -276,10 +278,8 @@ int dgpu_verify_multi(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_le
     c->ev_overflow = false;
     if (rlc) {  // the shard's points and its root by bucket MSM (the leaves wait for a failing root)
       c->rlc_pending = false;  // overwrites the points a pending per-rank root (dgpu_rlc_root_device) kept
-      if ((r = stage_all_host_locked(c, a, s)) || (r = rlc_points_locked(c, a, s)) ||
-          (r = c->msm_root.ensure(2 * (size_t)jw * 4)))
-        return r;
-      return rlc_root_msm_locked(c, a, s, (uint32_t*)c->msm_root.p);
+      if ((r = stage_all_host_locked(c, a, s)) || (r = rlc_points_locked(c, a, s))) return r;
+      return rlc_root_msm_locked(c, a, s, c->msm_root);
     }
     // the shard's records through the context's pinned ring, slice by slice
     // beside the verification (verify_status_host_locked)
@@ -297,12 +297,12 @@ int dgpu_verify_multi(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_le
       for (int k = 0; k < D; ++k) {
         dgpu_ctx* c = m->ctx[k];
         HIP_TRY(hipSetDevice(c->device));
-        uint32_t* root = (uint32_t*)m->buf[k].root.p;
+        const rlc_root_layout root = layout_at<rlc_root_layout>(m->buf[k].root.p, jw);  // (ensured above)
         if (args[k].n == 0) {
-          HIP_TRY(hipMemcpyAsync(root, inf_words, (size_t)jw * 4, hipMemcpyHostToDevice, c->stream));
-          HIP_TRY(hipMemcpyAsync(root + jw, inf_words, (size_t)jw * 4, hipMemcpyHostToDevice, c->stream));
+          HIP_TRY(hipMemcpyAsync(root.P, inf_words, (size_t)jw * 4, hipMemcpyHostToDevice, c->stream));
+          HIP_TRY(hipMemcpyAsync(root.S, inf_words, (size_t)jw * 4, hipMemcpyHostToDevice, c->stream));
         } else {
-          HIP_TRY(hipMemcpyAsync(root, c->msm_root.p, 2 * (size_t)jw * 4, hipMemcpyDeviceToDevice, c->stream));
+          HIP_TRY(hipMemcpyAsync(root.P, c->msm_root.p, root_bytes, hipMemcpyDeviceToDevice, c->stream));
         }
       }
       std::vector<const void*> src(D);
@@ -311,20 +311,20 @@ int dgpu_verify_multi(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_le
         src[k] = m->buf[k].root.p;
         dst[k] = m->buf[k].all_roots.p;
       }
-      if ((rc = multi_all_gather(m, src, dst, 2 * (size_t)jw * 4))) return rc;
+      if ((rc = multi_all_gather(m, src, dst, root_bytes))) return rc;
       dgpu_ctx* c0 = m->ctx[0];
       HIP_TRY(hipSetDevice(c0->device));
-      if ((rc = c0->rlc_root.ensure(2 * (size_t)jw * 4))) return rc;
-      uint32_t* sum = (uint32_t*)c0->rlc_root.p;
+      rlc_root_layout sum;
+      if ((rc = carve(c0->rlc_root, &sum, jw))) return rc;
       if (g1)
         hipLaunchKernelGGL(k_rlc_sum_roots<G1Ops>, dim3(1), dim3(64), 0, c0->stream, D,
-                           (const uint32_t*)m->buf[0].all_roots.p, sum, sum + jw);
+                           (const uint32_t*)m->buf[0].all_roots.p, sum.P, sum.S);
       else
         hipLaunchKernelGGL(k_rlc_sum_roots<G2Ops>, dim3(1), dim3(64), 0, c0->stream, D,
-                           (const uint32_t*)m->buf[0].all_roots.p, sum, sum + jw);
+                           (const uint32_t*)m->buf[0].all_roots.p, sum.P, sum.S);
       HIP_TRY(hipGetLastError());
       std::vector<uint8_t> fail;
-      if ((rc = rlc_check_locked(c0, keys[0], std::vector<uint32_t>{0}, 1, sum, sum + jw, c0->stream, &fail)))
+      if ((rc = rlc_check_locked(c0, keys[0], std::vector<uint32_t>{0}, 1, sum.P, sum.S, c0->stream, &fail)))
         return rc;
       all_ok = !fail[0];
     }
@@ -334,7 +334,9 @@ int dgpu_verify_multi(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_le
       if (cnt == 0) return DGPU_OK;
       int r;
       // this shard's verdicts, its own root first (D = 1: that root is the node's, known failing)
-      if (!all_ok && (r = rlc_resolve_locked(c, keys[k], args[k], c->stream, (const uint32_t*)c->msm_root.p, D == 1)))
+      rlc_root_layout shard;  // (phase 1 left the shard's root in msm_root)
+      if (!all_ok && ((r = carve(c->msm_root, &shard, jw)) ||
+                      (r = rlc_resolve_locked(c, keys[k], args[k], c->stream, shard, D == 1))))
         return r;
       return pack_shard_locked(c, cnt, (uint8_t*)m->buf[k].bits.p, (uint8_t*)m->buf[k].reasons.p, c->stream);
     });

@@ -18,13 +18,12 @@
 //   n1     [limb][i]
 #pragma once
 #include "engine.cuh"
+#include "engine_layout.cuh"  // eng_blk_off, kb_off, the cofactor planes: index functions and extents
 #include "kernels.cuh"
 
 namespace dgpu {
 
-constexpr int ENG_BLOCK = 64;                                  // one wave: 5 rounds
-constexpr int ENG_ROUNDS_PER_BLOCK = ENG_GROUPS_PER_WAVE;
-constexpr int ENG_LINE_STEPS = 68;
+constexpr int ENG_BLOCK = 64;                                  // one wave: ENG_ROUNDS_PER_BLOCK rounds
 
 // block constant region, host-built (capi.hip: eng_consts_for)
 struct eng_const_block {
@@ -66,14 +65,7 @@ __device__ __forceinline__ fp ld_soa(const uint32_t* base, size_t stride, size_t
   return a;
 }
 
-// Wave-blocked layout of the line and f buffers: block b (rounds 5b..5b+4)
-// owns planes [b][plane][limb][60] with word g*12 + e (group g, export e), so
-// every limb access of a wave is one contiguous 240-byte segment (a
-// round-fastest SoA would scatter the 60 lanes over 12 planes, 20 bytes each).
-constexpr int ENG_WAVE_WORDS = ENG_GROUPS_PER_WAVE * 12;
-__device__ __forceinline__ size_t eng_blk_off(size_t blk, int planes, int plane, int g, int e) {
-  return (blk * planes + plane) * FP_LIMBS * ENG_WAVE_WORDS + g * 12 + e;
-}
+// Accessors of the wave-blocked line and f buffers (engine_layout.cuh eng_blk_off)
 __device__ __forceinline__ eng_lane eng_lane_id(size_t cnt) { return eng_lane_id(cnt, blockIdx.x); }
 __device__ __forceinline__ void st_blk(uint32_t* base, size_t off, const fp& a) {
 #pragma unroll
@@ -259,8 +251,7 @@ __global__ void __launch_bounds__(ENG_BLOCK, 3) k_eng_lines(size_t n, size_t r0,
 // below 2^64 + 1 -- a hash output is not (every point the ladder meets is
 // then a nonzero multiple of a large-order point); the additions here are
 // the complete g2_add.
-// Scratch planes (stride n): pj [6] | pa [4] | psia [4] | t1 [12] | t0a [4] | t2 [12] | u [6]
-constexpr int COF_PLANES = 6 + 4 + 4 + 12 + 4 + 12 + 6;
+// Scratch planes (stride n; engine_layout.cuh COF_*): pj [6] | pa [4] | psia [4] | t1 [12] | t0a [4] | t2 [12] | u [6]
 __device__ __forceinline__ g2j cof_homog_to_jac(const uint32_t* t, size_t n, size_t i, int pr) {
   const uint32_t* b = t + (size_t)pr * 6 * FP_LIMBS * n;
   const fp2 X{ld_soa(b, n, i), ld_soa(b + FP_LIMBS * n, n, i)};
@@ -274,39 +265,40 @@ __global__ void __launch_bounds__(256) k_cof_prep(size_t n, const uint32_t* __re
   const g2j P = g2_add(ld_g2j(q, n, i), ld_g2j(q + G2J_WORDS * n, n, i));
   st_g2j(w, n, i, P);
   const g2a a = g2_to_affine(P);
-  st_g2a(w + G2J_WORDS * n, n, i, a);
+  st_g2a(w + COF_PA * n, n, i, a);
   const g2j s = g2_psi(g2_from_affine(a));  // Z = conj(1) = 1: still affine
-  st_g2a(w + (G2J_WORDS + G2A_WORDS) * n, n, i, g2a{s.x, s.y});
+  st_g2a(w + COF_PSIA * n, n, i, g2a{s.x, s.y});
 }
 __global__ void __launch_bounds__(256) k_cof_mid(size_t n, uint32_t* __restrict__ w) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const uint32_t* t1 = w + (G2J_WORDS + 2 * G2A_WORDS) * n;
+  const uint32_t* t1 = w + COF_T1 * n;
   const fp2 zi = fp2_inv(fp2{ld_soa(t1 + 4 * FP_LIMBS * n, n, i), ld_soa(t1 + 5 * FP_LIMBS * n, n, i)});
   const fp2 X{ld_soa(t1, n, i), ld_soa(t1 + FP_LIMBS * n, n, i)};
   const fp2 Y{ld_soa(t1 + 2 * FP_LIMBS * n, n, i), ld_soa(t1 + 3 * FP_LIMBS * n, n, i)};
-  st_g2a(w + (G2J_WORDS + 2 * G2A_WORDS + 12 * FP_WORDS) * n, n, i, g2a{fp2_mul(X, zi), fp2_mul(Y, zi)});
+  st_g2a(w + COF_T0A * n, n, i, g2a{fp2_mul(X, zi), fp2_mul(Y, zi)});
 }
 // U = T0 - P - T1 - psi(P) + psi^2(2P): everything but [x^2]P, from the
 // first pass alone -- it runs on a second stream beside the second pass
 __global__ void __launch_bounds__(256) k_cof_partial(size_t n, uint32_t* __restrict__ w) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const uint32_t* t1 = w + (G2J_WORDS + 2 * G2A_WORDS) * n;
+  const uint32_t* t1 = w + COF_T1 * n;
   const g2j P = ld_g2j(w, n, i);
   g2j u = g2_add(cof_homog_to_jac(t1, n, i, 0), g2_neg(P));                       // -[x]P - P
   u = g2_add(u, g2_neg(cof_homog_to_jac(t1, n, i, 1)));                            // + [x]psi(P)
   u = g2_add(u, g2_neg(g2_psi(P)));
   u = g2_add(u, g2_psi2(g2_dbl(P)));
-  st_g2j(w + (G2J_WORDS + 3 * G2A_WORDS + 24 * FP_WORDS) * n, n, i, u);
+  st_g2j(w + COF_U * n, n, i, u);
 }
 // h_eff P = [x^2]P + U
 __global__ void __launch_bounds__(256) k_cof_final(size_t n, const uint32_t* __restrict__ w, uint32_t* __restrict__ h_out,
                                                    uint32_t* __restrict__ z_out) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const uint32_t* t2 = w + (G2J_WORDS + 3 * G2A_WORDS + 12 * FP_WORDS) * n;
-  const g2j h = g2_add(cof_homog_to_jac(t2, n, i, 0), ld_g2j(t2 + 12 * FP_WORDS * n, n, i));
+  const uint32_t* t2 = w + COF_T2 * n;  // u follows t2
+  static_assert(COF_U == COF_T2 + COF_T_WORDS, "k_cof_final reads u behind t2");
+  const g2j h = g2_add(cof_homog_to_jac(t2, n, i, 0), ld_g2j(t2 + COF_T_WORDS * n, n, i));
   st_g2a(h_out, n, i, g2a{h.x, h.y});
   st_fp(z_out, n, i, h.z.c0);
   st_fp(z_out + FP_WORDS * n, n, i, h.z.c1);
@@ -434,14 +426,7 @@ __global__ void __launch_bounds__(ENG_BLOCK, 3) k_eng_fe(size_t cnt, size_t r0, 
 // k_eng_fe_seg(e); finally k_eng_fe_fb re-runs the listed blocks with a
 // flagged item (f1 = 0 at a stored value: practically never) on prog_fe.
 //
-// State planes (gen_engine.py PL_*: t, t2, the exponentiation input m, the
-// six stored m^(2^s)) in fbuf's wave-blocked layout with ENG_KB_PLANES planes:
-// [block of 5 rounds][plane][limb][g * 12 + component].
-__device__ __forceinline__ size_t kb_off(size_t i, int plane, int comp) {
-  const size_t blk = i / ENG_ROUNDS_PER_BLOCK;
-  const int g = (int)(i - blk * ENG_ROUNDS_PER_BLOCK);
-  return (blk * ENG_KB_PLANES + plane) * FP_LIMBS * ENG_WAVE_WORDS + g * 12 + comp;
-}
+// State planes: engine_layout.cuh kb_off.
 // Fp2 components (comp, comp + 1; comp even) of round i's plane: one dwordx2
 // per limb (8-byte aligned: g * 48 + comp * 4 bytes).  The per-thread
 // kernels' accesses; 4-byte loads of each component let a wave's loads of one

@@ -37,6 +37,8 @@ constexpr int RECOVER_MAX_T = 32;
 // coefficient r_j of the batched check
 constexpr int RECOVER_SLOTS = 5;
 
+#ifndef DG_NO_KERNELS  // (a host-only test program takes the sizes above alone)
+
 // recovery class of a round (k_recover_cand; REC_MORE flags a decodable
 // partial beyond the candidates)
 enum : uint8_t { REC_RLC = 0, REC_FAIL = 1, REC_EXACT = 2, REC_MORE = 0x10 };
@@ -718,5 +720,7 @@ __global__ void __launch_bounds__(256) k_scatter_rounds(size_t nx, const uint32_
     for (int b = 0; b < 96; ++b) out96[r * 96 + b] = x_out[k * 96 + b];
   }
 }
+
+#endif  // DG_NO_KERNELS
 
 }  // namespace dgpu

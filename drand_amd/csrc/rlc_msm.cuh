@@ -125,6 +125,8 @@ constexpr size_t MSM_KEYS = (size_t)MSM_MW * MSM_BUCKETS;
 constexpr int MSM_RUN = DG_MSM_RUN;
 constexpr int MSM_RUNS = MSM_BUCKETS / MSM_RUN;   // runs per (MSM, window)
 
+#ifndef DG_NO_KERNELS  // (a host-only test program takes the sizes above alone)
+
 // R (affine SoA in r_aff, (0, 0) = identity) and sig (affine SoA) -> AoS
 // [R | sig][i]; flags[i]: bit 0 R usable, bit 1 sig usable (status ST_OK and
 // not the identity; the leaves kernel skips the same points).
@@ -588,5 +590,7 @@ __global__ void k_rlc_sum_roots(int ndev, const uint32_t* __restrict__ roots, ui
   for (int d = 1; d < ndev; ++d) acc = Gr::add(acc, M::ld_jac(roots + (size_t)d * 2 * M::JAC + w * M::JAC, 1, 0));
   M::st_jac(w ? s_out : p_out, 1, 0, acc);
 }
+
+#endif  // DG_NO_KERNELS
 
 }  // namespace dgpu

@@ -25,10 +25,12 @@ int decode_commits_locked(dgpu_ctx* c, bool g2, int t, const uint8_t* commits, D
   const size_t cb = g2 ? 96 : 48;
   hipStream_t s = c->stream;
   int rc;
-  if ((rc = c->misc.ensure(t * cb + t * 4)) || (rc = dst->ensure((size_t)t * (g2 ? (size_t)G2A_WORDS : 2 * FP_LIMBS) * 4)))
+  commits_misc M;
+  if ((rc = carve(c->misc, &M, (size_t)t, cb)) ||
+      (rc = dst->ensure((size_t)t * (g2 ? (size_t)G2A_WORDS : 2 * FP_LIMBS) * 4)))
     return rc;
-  uint8_t* d_in = (uint8_t*)c->misc.p;
-  int* d_rc = (int*)(d_in + t * cb);
+  uint8_t* const d_in = M.in;
+  int* const d_rc = M.rc;
   HIP_TRY(hipMemcpyAsync(d_in, commits, (size_t)t * cb, hipMemcpyHostToDevice, s));
   if (g2)
     hipLaunchKernelGGL(k_decode_commits_g2, dim3(grid_for(t, 64)), dim3(64), 0, s, t, d_in, (uint32_t*)dst->p, d_rc);
@@ -188,28 +190,32 @@ int recover_begin_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_msgs, si
   const bool g1 = c->grp_g1;
   const size_t key_words = g1 ? (size_t)G2A_WORDS : 2 * FP_LIMBS;
   int rc;
+  lane_scratch& L = c->lane[0];
+  rec_sel_layout sel;
+  rec_part_layout part;
+  static_assert(REC_G1J_WORDS == G1J_WORDS, "one G1 Jacobian SoA");
   if ((rc = c->rec_hidx.ensure(items * 4)) || (rc = c->rec_pk.ensure(items * key_words * 4)) ||
       (rc = c->rec_idx.ensure(items * 4)) || (rc = c->rec_lam.ensure(n_rounds * RECOVER_MAX_T * RECOVER_SLOTS * 8)) ||
       (rc = c->rec_pts.ensure(n_rounds * G2A_WORDS * 4)) || (rc = c->rec_vpk.ensure(n_rounds * key_words * 4)) ||
       (rc = c->rec_st.ensure(n_rounds)) || (rc = c->rec_cls.ensure(n_rounds)) ||
-      (rc = c->h_pts.ensure(n_rounds * G2A_WORDS * 4)) || (rc = c->sig_pts.ensure(items * G2A_WORDS * 4)) ||
-      (rc = c->status.ensure(items)) || (rc = c->rec_sel.ensure(n_rounds * RECOVER_MAX_T * 2 * 4)) ||
-      (rc = c->rec_part.ensure(n_rounds * 5 * G2J_WORDS * 4)))
+      (rc = L.h_pts.ensure(n_rounds * G2A_WORDS * 4)) || (rc = L.sig_pts.ensure(items * G2A_WORDS * 4)) ||
+      (rc = c->status.ensure(items)) || (rc = carve(c->rec_sel, &sel, n_rounds)) ||
+      (rc = carve(c->rec_part, &part, n_rounds, g1 ? G1J_WORDS : G2J_WORDS)))
     return rc;
   recover_walk& w = *out;
   w.n_rounds = n_rounds, w.m = m, w.items = items;
   w.t = c->grp_t;
   w.g1 = g1;
-  w.h = (uint32_t*)c->h_pts.p;
-  w.sg = (uint32_t*)c->sig_pts.p;
+  w.h = (uint32_t*)L.h_pts.p;
+  w.sg = (uint32_t*)L.sig_pts.p;
   w.st = (uint8_t*)c->status.p;
   w.hidx = (uint32_t*)c->rec_hidx.p;
   w.keys = (uint32_t*)c->rec_pk.p;
   w.idx = (uint32_t*)c->rec_idx.p;
-  w.sel = (uint32_t*)c->rec_sel.p;
-  w.xs = w.sel + n_rounds * RECOVER_MAX_T;
+  w.sel = sel.sel;
+  w.xs = sel.xs;
   w.dig = (uint64_t*)c->rec_lam.p;
-  w.part = (uint32_t*)c->rec_part.p;
+  w.part = part.slice[0];  // (the kernels take the slices' base)
   w.rpts = (uint32_t*)c->rec_pts.p;
   w.rpk = (uint32_t*)c->rec_vpk.p;
   w.rst = (uint8_t*)c->rec_st.p;

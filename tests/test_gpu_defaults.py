@@ -161,3 +161,38 @@ def test_small_calls_latency_paths(cof_max, fe_max, n):
     with _default_ctx({"DGPU_COF_ENGINE_MAX": cof_max, "DGPU_FE_GS_MAX": fe_max}) as ctx:
         per = _verify(ctx, _lib.SCHEME_CHAINED, c, _lib.MODE_PER_ROUND)
     assert np.array_equal(per == 0, expect)
+
+
+@pytest.fixture(scope="module")
+def default_and_suite_ctx():
+    with _default_ctx() as dflt:
+        suite = open_ctx({})  # the suite's settings (conftest.py): k_h2c_finish and the Karabina FE
+        try:
+            yield dflt, suite
+        finally:
+            suite.close()
+
+
+@pytest.mark.parametrize("n", [1, 6, 64, 65])
+def test_cofactor_engine_scratch_around_blocks(default_and_suite_ctx, n):
+    """Small per-round calls at the shipped thresholds clear the hash's cofactor
+    on the engine ladder, whose scratch (cof_tmp's planes and the ladder's line
+    buffer) is sized by the call: n around the 5-round engine block and the
+    64-round wave.  Items cycled from the chained fixture, valid and corrupted
+    alike: verdicts and reasons equal the fixture's and those of a context at
+    the suite's settings (k_h2c_finish)."""
+    from drand_amd import _lib
+    from drand_amd.chain import Beacon, pack_beacons
+    from drand_amd.synth import Chain
+    g = load_golden("chain_chained_s1.json")
+    items = [(r["prev"], r["round"], r["sig"], 0) for r in g["rounds"]]
+    items += [(c["prev"], c["round"], c["sig"], c["reason"]) for c in g["corrupted"]]
+    pick = [items[(n + i) % len(items)] for i in range(n)]
+    rounds, sigs, sig_len, prev, prev_len = pack_beacons([Beacon(bytes.fromhex(p), r, bytes.fromhex(s))
+                                                          for p, r, s, _ in pick])
+    c = Chain(_lib.SCHEME_CHAINED, bytes.fromhex(g["pk"]), rounds, sigs, sig_len, prev, prev_len, None)
+    dflt, suite = default_and_suite_ctx
+    got = _verify(dflt, _lib.SCHEME_CHAINED, c, _lib.MODE_PER_ROUND)
+    ref = _verify(suite, _lib.SCHEME_CHAINED, c, _lib.MODE_PER_ROUND)
+    assert got.tolist() == [it[3] for it in pick]
+    assert got.tolist() == ref.tolist()
