@@ -81,6 +81,10 @@ SYMBOLS = [
     ("dgpu_verify_segment_device", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t, _c.c_uint64, _c.c_size_t, _P,
                                               _c.c_size_t, _P, _P, _c.c_size_t, _c.c_int, _c.c_uint64, _P, _P, _P,
                                               _P]),
+    ("dgpu_verify_segment_shard_device", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t, _c.c_uint64, _c.c_size_t, _P,
+                                                    _c.c_size_t, _P, _P, _P, _c.c_int, _c.c_uint64, _P, _P, _P, _P]),
+    ("dgpu_rlc_root_segment_device", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t, _c.c_uint64, _c.c_size_t, _P,
+                                                _c.c_size_t, _P, _P, _c.c_size_t, _P, _P, _c.c_uint64, _P, _P]),
     ("dgpu_rlc_root_bytes", _c.c_int, [_c.c_int]),
     ("dgpu_rlc_root_device", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t, _c.c_size_t, _P, _P, _c.c_size_t, _P, _P,
                                         _c.c_size_t, _P, _c.c_uint64, _P, _P]),
@@ -97,6 +101,8 @@ SYMBOLS = [
     ("dgpu_multi_context", _c.c_int, [_P, _c.c_int, _c.POINTER(_P)]),
     ("dgpu_verify_multi", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t, _c.c_size_t, _P, _P, _c.c_size_t, _P, _P,
                                      _c.c_size_t, _P, _c.c_int, _c.c_uint64, _P, _P]),
+    ("dgpu_verify_segment_multi", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t, _c.c_uint64, _c.c_size_t, _P, _c.c_size_t,
+                                             _P, _P, _c.c_size_t, _c.c_int, _c.c_uint64, _P, _P, _P]),
     ("dgpu_multi_set_group", _c.c_int, [_P, _c.c_int, _c.c_int, _P]),
     ("dgpu_multi_set_group_scheme", _c.c_int, [_P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_size_t]),
     ("dgpu_recover_multi", _c.c_int, [_P, _c.c_size_t, _P, _c.c_size_t, _P, _c.c_size_t, _P, _P, _P, _P]),

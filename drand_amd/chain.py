@@ -113,6 +113,40 @@ def rlc_seed_for(mode, rlc_seed):
     return 0 if rlc_seed is None else int(rlc_seed)
 
 
+def verify_segment_with(call, lib, code, first_round, sigs, prev_sig, pubkey, mode, rlc_seed, randomness, sig_len):
+    """The packing and result checks of a linked-segment call, shared by
+    Verifier.verify_segment and multi.MultiVerifier.verify_segment: `call` is
+    the entry point with its handle and scheme bound, taking the arguments
+    from pk on (dgpu_verify_segment, dgpu_verify_segment_multi)."""
+    width = 48 if code in (_lib.SCHEME_UNCHAINED_G1, _lib.SCHEME_G1_RFC9380) else 96
+    if isinstance(sigs, np.ndarray):
+        if sig_len is None:
+            raise ValueError("a signature array needs sig_len")
+        buf = np.ascontiguousarray(sigs, dtype=np.uint8)
+        lens = np.ascontiguousarray(sig_len, dtype=np.uint32)
+        if buf.ndim != 2 or lens.shape != (buf.shape[0],):
+            raise ValueError("sigs must be (n, stride) and sig_len (n,)")
+    else:
+        buf, lens = _pack_msgs([bytes(s or b"") for s in sigs])
+    if buf.shape[1] < width:
+        buf = np.pad(buf, ((0, 0), (0, width - buf.shape[1])))
+    n = buf.shape[0]
+    rand = np.zeros((n, 32), dtype=np.uint8) if randomness else None
+    if n == 0:
+        return np.zeros(0, dtype=np.uint8), rand
+    seed = np.frombuffer(bytes(prev_sig or b""), dtype=np.uint8).copy()
+    bits = np.zeros((n + 7) // 8, dtype=np.uint8)
+    reason = np.zeros(n, dtype=np.uint8)
+    pk = np.frombuffer(bytes(pubkey), dtype=np.uint8).copy()
+    _lib.check(call(_lib.ptr(pk), pk.size, int(first_round), n, _lib.ptr(buf), buf.shape[1], _lib.ptr(lens),
+                    _lib.ptr(seed) if seed.size else None, seed.size, mode, rlc_seed_for(mode, rlc_seed),
+                    _lib.ptr(bits), _lib.ptr(reason), None if rand is None else _lib.ptr(rand)), lib)
+    valid = np.unpackbits(bits, bitorder="little")[:n].astype(bool)
+    if not np.array_equal(valid, reason == _lib.REASON_OK):
+        raise _lib.DrandGPUError(_lib.DGPU_EINVAL, "verdict bitmap and reasons disagree")
+    return reason, rand
+
+
 class Verifier:
     """chain.Verifier (chain/verify.go:13-20): stateless apart from the scheme;
     safe for concurrent use (the GPU context serializes).  The public key is
@@ -191,35 +225,10 @@ class Verifier:
         verify_records returns them, and the (n, 32) uint8 array of
         SHA-256(sigs[i]) for the rounds that verify (zeros for the others;
         client/verify.go:207), or None when randomness is False."""
-        width = 48 if self._code in (_lib.SCHEME_UNCHAINED_G1, _lib.SCHEME_G1_RFC9380) else 96
-        if isinstance(sigs, np.ndarray):
-            if sig_len is None:
-                raise ValueError("a signature array needs sig_len")
-            buf = np.ascontiguousarray(sigs, dtype=np.uint8)
-            lens = np.ascontiguousarray(sig_len, dtype=np.uint32)
-            if buf.ndim != 2 or lens.shape != (buf.shape[0],):
-                raise ValueError("sigs must be (n, stride) and sig_len (n,)")
-        else:
-            buf, lens = _pack_msgs([bytes(s or b"") for s in sigs])
-        if buf.shape[1] < width:
-            buf = np.pad(buf, ((0, 0), (0, width - buf.shape[1])))
-        n = buf.shape[0]
-        rand = np.zeros((n, 32), dtype=np.uint8) if randomness else None
-        if n == 0:
-            return np.zeros(0, dtype=np.uint8), rand
-        seed = np.frombuffer(bytes(prev_sig or b""), dtype=np.uint8).copy()
-        bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-        reason = np.zeros(n, dtype=np.uint8)
-        pk = np.frombuffer(bytes(pubkey), dtype=np.uint8).copy()
-        _lib.check(self.ctx.lib.dgpu_verify_segment(self.ctx.handle, self._code, _lib.ptr(pk), pk.size, int(first_round),
-                                                    n, _lib.ptr(buf), buf.shape[1], _lib.ptr(lens),
-                                                    _lib.ptr(seed) if seed.size else None, seed.size, mode,
-                                                    rlc_seed_for(mode, rlc_seed), _lib.ptr(bits), _lib.ptr(reason),
-                                                    None if rand is None else _lib.ptr(rand)), self.ctx.lib)
-        valid = np.unpackbits(bits, bitorder="little")[:n].astype(bool)
-        if not np.array_equal(valid, reason == _lib.REASON_OK):
-            raise _lib.DrandGPUError(_lib.DGPU_EINVAL, "verdict bitmap and reasons disagree")
-        return reason, rand
+        lib = self.ctx.lib
+        return verify_segment_with(lambda *a: lib.dgpu_verify_segment(self.ctx.handle, self._code, *a), lib,
+                                   self._code, first_round, sigs, prev_sig, pubkey, mode, rlc_seed, randomness,
+                                   sig_len)
 
     def verify_beacon(self, b: Beacon, pubkey: bytes):
         """chain/verify.go:38-45: raises VerifyError (the reference's non-nil

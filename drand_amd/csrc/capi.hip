@@ -171,11 +171,21 @@ struct key_entry {
   uint64_t stamp = 0;
 };
 
+// A message source as the host holds it: any of the three device types
+// (kernels.cuh), selected by `linked` (SRC_*).  SRC_RECORDS: its msg_src part
+// is the source; SRC_LINKED: its msg_src_linked part; SRC_HALO: with_src
+// builds the msg_src_halo from the msg_src part, first_round, g0 and the two
+// halo pointers (host memory until stage_prepare_locked, device after).
+struct msg_src_host : msg_src_linked {
+  const uint8_t* halo;
+  const uint32_t* halo_len;
+};
+
 // Signature group and message source of one verify call.
 struct verify_args {
   int scheme;
   size_t n;
-  msg_src_linked m;  // (linked = 0: an explicit or raw source, its msg_src part)
+  msg_src_host m;
   const uint8_t* sigs;
   size_t sig_stride;
   const uint32_t* sig_len;
@@ -183,9 +193,9 @@ struct verify_args {
   uint64_t seed;
 };
 
-msg_src_linked beacon_src(const uint64_t* rounds, const uint8_t* prev, size_t prev_stride, const uint32_t* prev_len,
-                          bool chained) {
-  msg_src_linked m{};
+msg_src_host beacon_src(const uint64_t* rounds, const uint8_t* prev, size_t prev_stride, const uint32_t* prev_len,
+                        bool chained) {
+  msg_src_host m{};
   m.rounds = rounds;
   m.chained = chained ? 1 : 0;
   m.prev = chained ? prev : nullptr;
@@ -198,10 +208,10 @@ msg_src_linked beacon_src(const uint64_t* rounds, const uint8_t* prev, size_t pr
 // signature = the seed (copied into the source) for g = 0, else signature
 // g - 1 of the call's signature array.  seed_len <= 96 (checked by the entry
 // points).
-msg_src_linked linked_src(uint64_t first_round, const uint8_t* sigs, size_t sig_stride, const uint32_t* sig_len,
-                          const uint8_t* seed, size_t seed_len, bool chained) {
-  msg_src_linked m{};
-  m.linked = 1;
+msg_src_host linked_src(uint64_t first_round, const uint8_t* sigs, size_t sig_stride, const uint32_t* sig_len,
+                        const uint8_t* seed, size_t seed_len, bool chained) {
+  msg_src_host m{};
+  m.linked = SRC_LINKED;
   m.first_round = first_round;
   m.chained = chained ? 1 : 0;
   if (chained) {
@@ -214,8 +224,27 @@ msg_src_linked linked_src(uint64_t first_round, const uint8_t* sigs, size_t sig_
   return m;
 }
 
-msg_src_linked raw_src(const uint8_t* msgs, size_t stride, const uint32_t* len) {
-  msg_src_linked m{};
+// One shard of a linked segment (kernels.cuh msg_src_halo): first_round is the
+// shard's own first round, and item 0's previous signature is the record at
+// halo / halo_len (never read by an unchained source).
+msg_src_host halo_src(uint64_t first_round, const uint8_t* sigs, size_t sig_stride, const uint32_t* sig_len,
+                      const uint8_t* halo, const uint32_t* halo_len, bool chained) {
+  msg_src_host m{};
+  m.linked = SRC_HALO;
+  m.first_round = first_round;
+  m.chained = chained ? 1 : 0;
+  if (chained) {
+    m.prev = sigs;
+    m.prev_stride = sig_stride;
+    m.prev_len = sig_len;
+    m.halo = halo;
+    m.halo_len = halo_len;
+  }
+  return m;
+}
+
+msg_src_host raw_src(const uint8_t* msgs, size_t stride, const uint32_t* len) {
+  msg_src_host m{};
   m.msgs = msgs;
   m.msg_stride = stride;
   m.msg_len = len;
@@ -223,10 +252,19 @@ msg_src_linked raw_src(const uint8_t* msgs, size_t stride, const uint32_t* len) 
 }
 
 // f(source) with the source as the type its kernels are instantiated for:
-// the linked form, or the msg_src part of any other.
+// the halo form, the linked form, or the msg_src part of any other.
 template <class F>
-auto with_src(const msg_src_linked& m, F&& f) {
-  return m.linked ? f(m) : f(static_cast<const msg_src&>(m));
+auto with_src(const msg_src_host& m, F&& f) {
+  if (m.linked == SRC_HALO) {
+    msg_src_halo h{};
+    static_cast<msg_src&>(h) = m;
+    h.first_round = m.first_round;
+    h.g0 = m.g0;
+    h.halo = m.halo;
+    h.halo_len = m.halo_len;
+    return f(static_cast<const msg_src_halo&>(h));
+  }
+  return m.linked ? f(static_cast<const msg_src_linked&>(m)) : f(static_cast<const msg_src&>(m));
 }
 // the kernel template K for the source type of `src` (inside with_src)
 #define SRC_KERNEL(K, src) K<std::decay_t<decltype(src)>>
@@ -324,6 +362,7 @@ struct dgpu_ctx {
   bool stage_pageable = false;   // A/B build, DGPU_STAGE=pageable: the round-5 whole-batch pageable copy
   // staging for host-pointer entry points
   DevBuf in_rounds, in_sigs, in_sig_len, in_prev, in_prev_len, in_msgs, in_msg_len, out_bits, out_reason, out_rand, misc;
+  DevBuf in_halo, in_halo_len;  // a staged shard's halo (dgpu_verify_segment_multi): one record of the stride, its length
   // optional per-stage HIP-event timing of the last verify call (event pool;
   // durations are summed per stage name: chunked stages repeat)
   bool profile = false;
@@ -1220,7 +1259,7 @@ int stager_wait_all(host_stager* stg, hipStream_t s);
 // consts (the key's engine constants; optional): calls of at most
 // cof_engine_max rounds clear the cofactor on the engine ladder
 // (pairing_engine.cuh k_cof_*) instead of k_h2c_finish.
-int g2_lane_hash_locked(dgpu_ctx* c, lane_scratch& L, size_t n, const msg_src_linked& m, const uint8_t* sigs,
+int g2_lane_hash_locked(dgpu_ctx* c, lane_scratch& L, size_t n, const msg_src_host& m, const uint8_t* sigs,
                         size_t sig_stride, const uint32_t* sig_len, uint8_t* st, hipStream_t s,
                         hipStream_t s_dec = nullptr, const uint32_t* consts = nullptr, host_stager* stg = nullptr,
                         size_t slice = 0) {
@@ -1323,8 +1362,8 @@ int g2_lane_hash_locked(dgpu_ctx* c, lane_scratch& L, size_t n, const msg_src_li
 // msg_src of items [off, off + cnt) of m.  The linked form keeps its base
 // pointers (the slice's first item reads the record before the slice) and
 // carries the offset.
-msg_src_linked src_slice(const msg_src_linked& m, size_t off) {
-  msg_src_linked r = m;
+msg_src_host src_slice(const msg_src_host& m, size_t off) {
+  msg_src_host r = m;
   if (m.linked) {
     r.g0 = m.g0 + off;
   } else if (m.msgs) {
@@ -1495,7 +1534,7 @@ int stage_inputs_locked(dgpu_ctx* c, verify_args& a, hipStream_t s) {
   HIP_TRY(hipMemcpyAsync(c->in_sig_len.p, a.sig_len, n * 4, hipMemcpyHostToDevice, s));
   a.sigs = (const uint8_t*)c->in_sigs.p;
   a.sig_len = (const uint32_t*)c->in_sig_len.p;
-  msg_src_linked& m = a.m;
+  msg_src_host& m = a.m;
   if (m.linked) {  // the records are the signature arrays
     if (m.chained) m.prev = a.sigs, m.prev_len = a.sig_len;
     return DGPU_OK;
@@ -1631,9 +1670,16 @@ struct host_stager {
   // the message arrays of items [a, b) (checked against their stride), then
   // its signature arrays; an event after each part
   int stage_slice(const verify_args& dev, size_t k, size_t a, size_t b) {
-    const msg_src_linked& m = host.m;
+    const msg_src_host& m = host.m;
     const size_t n = b - a;
     int r;
+    // A shard's halo (one record of the stride and its length, not counted in
+    // `bytes`) ahead of everything else of the call on the in-order copy
+    // stream: every event a kernel waits for covers it.
+    if (k == 0 && m.linked == SRC_HALO && m.chained &&
+        ((r = ring_copy_locked(c, (uint8_t*)dev.m.halo, m.halo, host.sig_stride)) ||
+         (r = ring_copy_locked(c, (uint32_t*)dev.m.halo_len, m.halo_len, 4))))
+      return r;
     if (m.linked) {
       // no message part: the slice's digests read its signatures (wait_part)
     } else if (m.msgs) {
@@ -1724,9 +1770,14 @@ int stage_prepare_locked(dgpu_ctx* c, verify_args& a) {
   if ((rc = c->in_sigs.ensure(n * a.sig_stride)) || (rc = c->in_sig_len.ensure(n * 4))) return rc;
   a.sigs = (const uint8_t*)c->in_sigs.p;
   a.sig_len = (const uint32_t*)c->in_sig_len.p;
-  msg_src_linked& m = a.m;
+  msg_src_host& m = a.m;
   if (m.linked) {  // the records are the signature arrays: no rounds, no second copy of the signatures
     if (m.chained) m.prev = a.sigs, m.prev_len = a.sig_len;
+    if (m.linked == SRC_HALO && m.chained) {  // the halo: one record of the stride, and its length
+      if ((rc = c->in_halo.ensure(a.sig_stride)) || (rc = c->in_halo_len.ensure(4))) return rc;
+      m.halo = (const uint8_t*)c->in_halo.p;
+      m.halo_len = (const uint32_t*)c->in_halo_len.p;
+    }
     return DGPU_OK;
   }
   if (m.msgs) {
@@ -2116,25 +2167,55 @@ int dgpu_verify_segment_device(dgpu_ctx* c, int scheme, const uint8_t* pk, size_
   return verify_device_locked(c, k, a, d_bits, d_reason, s, d_randomness32);
 }
 
+// The arguments of the halo form (a shard of a linked segment).
+static int check_shard_args(int scheme, uint64_t first_round, size_t n, const uint8_t* d_halo,
+                            const uint32_t* d_halo_len) {
+  if (n && first_round + (uint64_t)(n - 1) < first_round)
+    return set_err(DGPU_EINVAL, "rounds %llu + %zu overflow", (unsigned long long)first_round, n);
+  if (scheme == DGPU_SCHEME_CHAINED && n && (!d_halo || !d_halo_len))
+    return set_err(DGPU_EINVAL, "a chained shard needs its halo (d_halo, d_halo_len)");
+  return DGPU_OK;
+}
+
+int dgpu_verify_segment_shard_device(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t pk_len, uint64_t first_round,
+                                     size_t n, const uint8_t* d_sigs, size_t sig_stride, const uint32_t* d_sig_len,
+                                     const uint8_t* d_halo, const uint32_t* d_halo_len, int mode, uint64_t rlc_seed,
+                                     uint8_t* d_bits, uint8_t* d_reason, uint8_t* d_randomness32, void* stream) {
+  if (!c) return set_err(DGPU_EINVAL, "null ctx");
+  int rc = check_shard_args(scheme, first_round, n, d_halo, d_halo_len);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  key_entry* k = nullptr;
+  if ((rc = get_key_locked(c, scheme, pk, pk_len, &k))) return rc;
+  hipStream_t s = caller_stream(stream);
+  stream_order ord(c, s);
+  // the halo is read by the kernels, in stream order: the host never looks at it
+  const verify_args a{scheme, n,
+                      halo_src(first_round, d_sigs, sig_stride, d_sig_len, d_halo, d_halo_len,
+                               scheme == DGPU_SCHEME_CHAINED),
+                      d_sigs, sig_stride, d_sig_len, mode, rlc_seed};
+  return verify_device_locked(c, k, a, d_bits, d_reason, s, d_randomness32);
+}
+
 int dgpu_rlc_root_bytes(int scheme) {
   if (!scheme_known(scheme)) return set_err(DGPU_EINVAL, "bad scheme %d", scheme);
   return 2 * rlc_geom_of(sig_on_g1(scheme)).jw * 4;
 }
 
-int dgpu_rlc_root_device(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t pk_len, size_t n,
-                         const uint64_t* d_rounds, const uint8_t* d_sigs, size_t sig_stride, const uint32_t* d_sig_len,
-                         const uint8_t* d_prev, size_t prev_stride, const uint32_t* d_prev_len, uint64_t rlc_seed,
-                         uint8_t* d_root, void* stream) {
-  if (!c || !d_root) return set_err(DGPU_EINVAL, "null argument");
-  std::lock_guard<std::mutex> lk(c->mu);
+// Step 1 of the per-rank RLC protocol for the device-resident shard `a`
+// (any message source): its root to d_root, the shard kept pending on the
+// context for dgpu_rlc_finish_device.
+static int rlc_root_pending_locked(dgpu_ctx* c, const verify_args& a, const uint8_t* pk, size_t pk_len,
+                                   uint8_t* d_root, void* stream) {
+  const int scheme = a.scheme;
+  const size_t n = a.n;
   HIP_TRY(hipSetDevice(c->device));
   key_entry* k = nullptr;
   int rc = get_key_locked(c, scheme, pk, pk_len, &k);
   if (rc) return rc;
   hipStream_t s = caller_stream(stream);
   stream_order ord(c, s);
-  const verify_args a{scheme, n, beacon_src(d_rounds, d_prev, prev_stride, d_prev_len, scheme == DGPU_SCHEME_CHAINED),
-                      d_sigs, sig_stride, d_sig_len, DGPU_MODE_RLC, rlc_seed};
   if ((rc = check_args(c, k, a))) return rc;
   c->rlc_pending = false;
   const rlc_geom G = rlc_geom_of(sig_on_g1(scheme));
@@ -2157,6 +2238,36 @@ int dgpu_rlc_root_device(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t pk_l
   c->rlc_pk_len = pk_len;
   c->rlc_pending = true;
   return DGPU_OK;
+}
+
+int dgpu_rlc_root_device(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t pk_len, size_t n,
+                         const uint64_t* d_rounds, const uint8_t* d_sigs, size_t sig_stride, const uint32_t* d_sig_len,
+                         const uint8_t* d_prev, size_t prev_stride, const uint32_t* d_prev_len, uint64_t rlc_seed,
+                         uint8_t* d_root, void* stream) {
+  if (!c || !d_root) return set_err(DGPU_EINVAL, "null argument");
+  std::lock_guard<std::mutex> lk(c->mu);
+  const verify_args a{scheme, n, beacon_src(d_rounds, d_prev, prev_stride, d_prev_len, scheme == DGPU_SCHEME_CHAINED),
+                      d_sigs, sig_stride, d_sig_len, DGPU_MODE_RLC, rlc_seed};
+  return rlc_root_pending_locked(c, a, pk, pk_len, d_root, stream);
+}
+
+int dgpu_rlc_root_segment_device(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t pk_len, uint64_t first_round,
+                                 size_t n, const uint8_t* d_sigs, size_t sig_stride, const uint32_t* d_sig_len,
+                                 const uint8_t* seed_prev, size_t seed_prev_len, const uint8_t* d_halo,
+                                 const uint32_t* d_halo_len, uint64_t rlc_seed, uint8_t* d_root, void* stream) {
+  if (!c || !d_root) return set_err(DGPU_EINVAL, "null argument");
+  const bool chained = scheme == DGPU_SCHEME_CHAINED;
+  int rc = d_halo ? check_shard_args(scheme, first_round, n, d_halo, d_halo_len)
+                  : check_segment_args(scheme, first_round, n, seed_prev, seed_prev_len);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  // (the seed form carries the seed by value, the halo form the two device
+  // pointers: the pending source keeps either until the finish step)
+  const verify_args a{scheme, n,
+                      d_halo ? halo_src(first_round, d_sigs, sig_stride, d_sig_len, d_halo, d_halo_len, chained)
+                             : linked_src(first_round, d_sigs, sig_stride, d_sig_len, seed_prev, seed_prev_len, chained),
+                      d_sigs, sig_stride, d_sig_len, DGPU_MODE_RLC, rlc_seed};
+  return rlc_root_pending_locked(c, a, pk, pk_len, d_root, stream);
 }
 
 int dgpu_rlc_finish_device(dgpu_ctx* c, size_t n_roots, const uint8_t* d_roots, uint8_t* d_bits, uint8_t* d_reason,

@@ -113,15 +113,39 @@ struct msg_src {
 // msg_src the seed's SHA-256 stream cost the explicit-record kernels 96 bytes
 // of scratch (k_h2c_field) and spills in the two G1 hash kernels
 // (profiles/r08/segment_resource_usage.txt); as instantiated for msg_src they
-// are the kernels they were.  The host holds every source as a
-// msg_src_linked (linked = 0: its msg_src part is the source).
+// are the kernels they were.  The host holds every source as one type
+// (capi.hip msg_src_host) and `linked` tells which device type it is.
 struct msg_src_linked : msg_src {
-  int linked;         // host-side selector of the instantiation; the device type is always linked
+  int linked;         // host-side selector of the instantiation (SRC_*); the device type is always linked
   uint32_t seed_len;  // <= 96
   uint64_t first_round;
   size_t g0;
   uint32_t seed[24];  // 96 bytes, byte k in bits 8 (k % 4) of word k / 4
 };
+
+// One shard of a linked segment (dgpu_verify_segment_shard_device, the later
+// shards of dgpu_verify_segment_multi): the linked form whose item 0 takes its
+// previous signature from a one-record *halo* in device memory -- the
+// neighbouring shard's last record, wherever a copy or a collective put it --
+// read through pointers when the kernel runs, so it is ordered by the stream
+// and nothing of it is known to the host at the launch.  The halo is a record
+// like any other of the array: min(*halo_len, prev_stride) bytes at `halo`,
+// and *halo_len > prev_stride makes item 0 a bad record, exactly as record
+// g - 1's length does for item g.  first_round is the shard's own first
+// round, prev / prev_len the shard's own signature arrays.  An unchained
+// source never touches the halo pointers (they may be null).  No seed by
+// value: the kernels instantiated for it carry the explicit form's arguments
+// and no SHA-256 stream over kernel-argument words
+// (profiles/r11/halo_resource_usage.txt).
+struct msg_src_halo : msg_src {
+  uint64_t first_round;
+  size_t g0;
+  const uint8_t* halo;
+  const uint32_t* halo_len;
+};
+
+// msg_src_linked::linked on the host: which instantiation a source selects
+enum : int { SRC_RECORDS = 0, SRC_LINKED = 1, SRC_HALO = 2 };
 
 DG_FN uint32_t clamp_len(uint32_t len, size_t stride) {
   return (size_t)len > stride ? (uint32_t)stride : len;
@@ -130,13 +154,31 @@ DG_FN uint32_t clamp_len(uint32_t len, size_t stride) {
 // Round number of item i of a beacon source; whether its previous signature
 // is the linked form's seed; the index of the record that holds its previous
 // signature otherwise (i itself, or in the linked form the signature before
-// it, global item g - 1).
+// it, global item g - 1); that record's bytes and its length as stored (not
+// clamped) -- in the halo form the halo's for global item 0.
 DG_FN uint64_t msg_round(const msg_src& m, size_t i) { return m.rounds[i]; }
 DG_FN uint64_t msg_round(const msg_src_linked& m, size_t i) { return m.first_round + (m.g0 + i); }
+DG_FN uint64_t msg_round(const msg_src_halo& m, size_t i) { return m.first_round + (m.g0 + i); }
 DG_FN bool msg_prev_is_seed(const msg_src&, size_t) { return false; }
 DG_FN bool msg_prev_is_seed(const msg_src_linked& m, size_t i) { return m.g0 + i == 0; }
 DG_FN size_t msg_prev_index(const msg_src&, size_t i) { return i; }
 DG_FN size_t msg_prev_index(const msg_src_linked& m, size_t i) { return m.g0 + i - 1; }
+template <class Src>
+DG_FN const uint8_t* msg_prev_ptr(const Src& m, size_t i) {
+  return m.prev + msg_prev_index(m, i) * m.prev_stride;
+}
+template <class Src>
+DG_FN uint32_t msg_prev_len(const Src& m, size_t i) {
+  return m.prev_len[msg_prev_index(m, i)];
+}
+DG_FN const uint8_t* msg_prev_ptr(const msg_src_halo& m, size_t i) {
+  const size_t g = m.g0 + i;
+  return g == 0 ? m.halo : m.prev + (g - 1) * m.prev_stride;
+}
+DG_FN uint32_t msg_prev_len(const msg_src_halo& m, size_t i) {
+  const size_t g = m.g0 + i;
+  return *(g == 0 ? m.halo_len : m.prev_len + (g - 1));
+}
 
 // SHA-256(seed || BE64(round)): the digest of the linked form's first item.
 // The seed word is picked by selects over constant indices, not by an indexed
@@ -159,7 +201,7 @@ template <class Src>
 DG_FN bool msg_bad_record(const Src& m, size_t i) {
   if (m.msgs) return (size_t)m.msg_len[i] > m.msg_stride;
   if (!m.chained || msg_prev_is_seed(m, i)) return false;
-  return (size_t)m.prev_len[msg_prev_index(m, i)] > m.prev_stride;
+  return (size_t)msg_prev_len(m, i) > m.prev_stride;
 }
 
 // drand digest of a beacon record (32 bytes as 8 big-endian words)
@@ -170,9 +212,8 @@ DG_FN void msg_digest(const Src& m, size_t i, uint32_t msg[8]) {
     msg_seed_digest(m, round, msg);
     return;
   }
-  const size_t j = m.chained ? msg_prev_index(m, i) : 0;
-  const uint32_t plen = m.chained ? clamp_len(m.prev_len[j], m.prev_stride) : 0u;
-  drand_digest(msg, m.chained ? m.prev + j * m.prev_stride : nullptr, plen, round);
+  const uint32_t plen = m.chained ? clamp_len(msg_prev_len(m, i), m.prev_stride) : 0u;
+  drand_digest(msg, m.chained ? msg_prev_ptr(m, i) : nullptr, plen, round);
 }
 
 // expand_message_xmd of item i's message under DST G1DST with ELL 32-byte blocks

@@ -20,6 +20,13 @@
 // RCCL is loaded at dgpu_multi_open (dlopen), so the single-GPU library has
 // no link-time dependency on it.
 //
+// dgpu_verify_segment_multi is the same call over a linked segment (the
+// signatures alone, client/verify.go:118-178): there the first round of shard
+// k > 0 hashes the last record of shard k - 1, so that one record travels with
+// the shard as its halo (kernels.cuh msg_src_halo), staged from the caller's
+// own arrays ahead of the shard; everything else is one function
+// (multi_verify) over a per-shard message source.
+//
 // Test mode: with DGPU_MULTI_ALLOW_SAME_DEVICE=1 in the environment a handle
 // may list one device several times (devs = {0, 0, 0}: one context each, own
 // streams and buffers) and its all-gathers are in-library device copies
@@ -221,16 +228,38 @@ int pack_shard_locked(dgpu_ctx* c, size_t cnt, uint8_t* d_bits, uint8_t* d_reaso
 
 }  // namespace
 
-extern "C" {
+namespace {
 
-int dgpu_verify_multi(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_len, size_t n, const uint64_t* rounds,
-                      const uint8_t* sigs, size_t sig_stride, const uint32_t* sig_len, const uint8_t* prev,
-                      size_t prev_stride, const uint32_t* prev_len, int mode, uint64_t rlc_seed,
-                      uint8_t* verdict_bits, uint8_t* reason) {
+// The final statuses of device k's shard -> its verdict bits and reasons in
+// the gather buffers and (rand32: optional, the shard's rows of the caller's
+// array) the verified rounds' randomness, straight from the device to the
+// host as dgpu_recover_multi returns its signatures.  a's signature arrays
+// are the staged device copies.
+int shard_results_locked(dgpu_multi* m, int k, const verify_args& a, uint8_t* rand32) {
+  dgpu_ctx* c = m->ctx[k];
+  hipStream_t s = c->stream;
+  int rc = pack_shard_locked(c, a.n, (uint8_t*)m->buf[k].bits.p, (uint8_t*)m->buf[k].reasons.p, s);
+  if (rc || !rand32 || a.n == 0) return rc;
+  if ((rc = c->out_rand.ensure(a.n * 32))) return rc;
+  hipLaunchKernelGGL(k_randomness, dim3(grid_for(a.n, 256)), dim3(256), 0, s, a.n, a.sigs, a.sig_stride, a.sig_len,
+                     (const uint8_t*)c->status.p, (uint8_t*)c->out_rand.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(rand32, c->out_rand.p, a.n * 32, hipMemcpyDeviceToHost, s));
+  return DGPU_OK;
+}
+
+// The multi-device verify call over host records (dgpu_verify_multi,
+// dgpu_verify_segment_multi): src_of(k, lo, hi) is the message source of
+// shard k = items [lo, hi) of the caller's arrays; everything else -- the
+// shards' signature arrays, per-device seeds, staging through each context's
+// ring, roots, gathers -- is the same for every source.
+template <class SrcOf>
+int multi_verify(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_len, size_t n, const uint8_t* sigs,
+                 size_t sig_stride, const uint32_t* sig_len, int mode, uint64_t rlc_seed, SrcOf&& src_of,
+                 uint8_t* verdict_bits, uint8_t* reason, uint8_t* rand32) {
   if (!m) return set_err(DGPU_EINVAL, "null handle");
   if (n == 0) return DGPU_OK;
   if (!verdict_bits) return set_err(DGPU_EINVAL, "null verdict buffer");
-  const bool chained = scheme == DGPU_SCHEME_CHAINED;
   std::lock_guard<std::mutex> mlk(m->mu);
   std::vector<std::unique_lock<std::mutex>> locks;
   for (dgpu_ctx* c : m->ctx) locks.emplace_back(c->mu);
@@ -239,17 +268,17 @@ int dgpu_verify_multi(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_le
   const size_t per = (((n + (size_t)D - 1) / (size_t)D) + 7) & ~(size_t)7;
   std::vector<key_entry*> keys(D, nullptr);
   std::vector<verify_args> args(D);
+  std::vector<size_t> lo(D);
   int rc;
   for (int k = 0; k < D; ++k) {
     dgpu_ctx* c = m->ctx[k];
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = get_key_locked(c, scheme, pk, pk_len, &keys[k]))) return rc;
-    size_t lo, hi;
-    dgpu_shard_range(n, D, k, &lo, &hi);
+    size_t hi;
+    dgpu_shard_range(n, D, k, &lo[k], &hi);
     // RLC coefficients: an independent seed per device (positions restart at 0)
-    args[k] = verify_args{scheme, hi - lo, beacon_src(rounds + lo, chained ? prev + lo * prev_stride : nullptr,
-                                                      prev_stride, chained ? prev_len + lo : nullptr, chained),
-                          sigs + lo * sig_stride, sig_stride, sig_len + lo, mode,
+    args[k] = verify_args{scheme, hi - lo[k], src_of(k, lo[k], hi), sigs + lo[k] * sig_stride, sig_stride,
+                          sig_len + lo[k], mode,
                           D > 1 ? splitmix_host(rlc_seed ^ (0x5EEDull * (uint64_t)(k + 1))) : rlc_seed};
     if ((rc = check_args(c, keys[k], args[k]))) return rc;
     multi_bufs& b = m->buf[k];
@@ -284,7 +313,7 @@ int dgpu_verify_multi(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_le
     // the shard's records through the context's pinned ring, slice by slice
     // beside the verification (verify_status_host_locked)
     if ((r = verify_status_host_locked(c, keys[k], a, s))) return r;
-    return pack_shard_locked(c, a.n, (uint8_t*)m->buf[k].bits.p, (uint8_t*)m->buf[k].reasons.p, s);
+    return shard_results_locked(m, k, a, rand32 ? rand32 + 32 * lo[k] : nullptr);
   });
   if (rc) return rc;
   if (rlc) {
@@ -338,7 +367,7 @@ int dgpu_verify_multi(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_le
       if (!all_ok && ((r = carve(c->msm_root, &shard, jw)) ||
                       (r = rlc_resolve_locked(c, keys[k], args[k], c->stream, shard, D == 1))))
         return r;
-      return pack_shard_locked(c, cnt, (uint8_t*)m->buf[k].bits.p, (uint8_t*)m->buf[k].reasons.p, c->stream);
+      return shard_results_locked(m, k, args[k], rand32 ? rand32 + 32 * lo[k] : nullptr);
     });
     if (rc) return rc;
   }
@@ -376,6 +405,47 @@ int dgpu_verify_multi(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_le
     HIP_TRY(hipStreamSynchronize(m->ctx[k]->stream));
   }
   return DGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dgpu_verify_multi(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_len, size_t n, const uint64_t* rounds,
+                      const uint8_t* sigs, size_t sig_stride, const uint32_t* sig_len, const uint8_t* prev,
+                      size_t prev_stride, const uint32_t* prev_len, int mode, uint64_t rlc_seed,
+                      uint8_t* verdict_bits, uint8_t* reason) {
+  const bool chained = scheme == DGPU_SCHEME_CHAINED;
+  return multi_verify(
+      m, scheme, pk, pk_len, n, sigs, sig_stride, sig_len, mode, rlc_seed,
+      [&](int, size_t lo, size_t) {
+        return beacon_src(rounds + lo, chained ? prev + lo * prev_stride : nullptr, prev_stride,
+                          chained ? prev_len + lo : nullptr, chained);
+      },
+      verdict_bits, reason, nullptr);
+}
+
+// The linked form over the node: shard 0 is dgpu_verify_segment's source (the
+// caller's seed by value), shard k > 0 the halo form with record lo_k - 1 of
+// the caller's arrays as its halo, staged ahead of the shard's own records
+// (host_stager::stage_slice).
+int dgpu_verify_segment_multi(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_len, uint64_t first_round,
+                              size_t n, const uint8_t* sigs, size_t sig_stride, const uint32_t* sig_len,
+                              const uint8_t* seed_prev, size_t seed_prev_len, int mode, uint64_t rlc_seed,
+                              uint8_t* verdict_bits, uint8_t* reason, uint8_t* randomness32) {
+  int rc = check_segment_args(scheme, first_round, n, seed_prev, seed_prev_len);
+  if (rc) return rc;
+  const bool chained = scheme == DGPU_SCHEME_CHAINED;
+  if (n && (!sigs || !sig_len)) return set_err(DGPU_EINVAL, "bad signature buffers");
+  return multi_verify(
+      m, scheme, pk, pk_len, n, sigs, sig_stride, sig_len, mode, rlc_seed,
+      [&](int, size_t lo, size_t hi) {
+        const uint8_t* s_lo = sigs + lo * sig_stride;
+        if (lo == 0 || lo == hi)  // (an empty shard runs nothing: any source)
+          return linked_src(first_round, s_lo, sig_stride, sig_len + lo, seed_prev, seed_prev_len, chained);
+        return halo_src(first_round + lo, s_lo, sig_stride, sig_len + lo, s_lo - sig_stride, sig_len + lo - 1, chained);
+      },
+      verdict_bits, reason, randomness32);
 }
 
 }  // extern "C"

@@ -102,6 +102,17 @@ def verify_rlc_sharded(ctx, code, pk, n, d_rounds, d_sigs, d_sig_len, d_prev, d_
                                         d_sigs.data_ptr(), sig_stride, d_sig_len.data_ptr(), d_prev.data_ptr(),
                                         prev_stride, d_prev_len.data_ptr(), rank_seed(seed, rank, world),
                                         root.data_ptr(), s))
+    _finish_rlc_sharded(ctx, root, rb, world, d_bits, d_reason, s, lib_stream, cur)
+
+
+def _finish_rlc_sharded(ctx, root, rb, world, d_bits, d_reason, s, lib_stream, cur):
+    """Steps 2-3 of the per-rank RLC protocol: the roots' all-gather (ordered
+    against the library's stream by waits) and dgpu_rlc_finish_device."""
+    import torch
+    import torch.distributed as dist
+    from . import _lib
+    lib = ctx.lib
+    dev = root.device
     if world > 1:
         cur.wait_stream(lib_stream)  # the root is written before the collective reads it
         root.record_stream(cur)
@@ -118,3 +129,110 @@ def verify_rlc_sharded(ctx, code, pk, n, d_rounds, d_sigs, d_sig_len, d_prev, d_
         roots = root
     _lib.check(lib.dgpu_rlc_finish_device(ctx.handle, world, roots.data_ptr(), d_bits.data_ptr(),
                                           None if d_reason is None else d_reason.data_ptr(), s))
+
+
+def halo_len_offset(sig_stride):
+    """Offset of the 32-bit length in a packed halo record: the stride rounded
+    up to a multiple of 4 (sig_stride itself for the 96- and 48-byte strides),
+    so a packed record is sig_stride + 4 bytes."""
+    return (sig_stride + 3) & ~3
+
+
+def exchange_halo(last, n_total, world, rank):
+    """The halo exchange of a linked segment sharded by shard_range: every
+    rank contributes `last`, its shard's last record and that record's length
+    packed as one uint8 tensor (sig_stride bytes, then the little-endian
+    uint32 length at halo_len_offset; zeros from a rank whose shard is empty),
+    in one all-gather.  Returns rank - 1's contribution -- this rank's halo,
+    the previous signature of its first round -- or None where there is none:
+    rank 0 (its first round takes the caller's seed), an empty shard, and
+    world 1 (no collective at all).  Works on whatever tensors the backend
+    gathers: CPU under gloo, device under RCCL."""
+    import torch
+    import torch.distributed as dist
+    if world <= 1:
+        return None
+    out = [torch.empty_like(last) for _ in range(world)]
+    dist.all_gather(out, last)
+    lo, hi = shard_range(n_total, world, rank)
+    if rank == 0 or hi == lo:
+        return None
+    plo, phi = shard_range(n_total, world, rank - 1)
+    # only trailing shards are empty, so a non-empty shard's predecessor holds a record
+    assert phi > plo and phi == lo, (plo, phi, lo, hi)
+    return out[rank - 1]
+
+
+def verify_segment_sharded(ctx, code, pk, first_round, n_total, d_sigs, d_sig_len, seed_prev, mode, seed, d_bits,
+                           stream, world, rank, d_reason=None, d_randomness=None, sig_stride=96):
+    """A linked segment (dgpu_verify_segment's input: first round, one seed,
+    the signatures) sharded across ranks by shard_range, each rank holding its
+    shard's signatures in device memory: d_sigs / d_sig_len are this rank's
+    (n, sig_stride) uint8 and (n,) 32-bit tensors, first_round and seed_prev
+    the whole segment's.  One all-gather hands every rank its predecessor's
+    last record (exchange_halo; a CPU round trip under gloo); rank 0 verifies
+    from the seed, rank k > 0 from that halo, read by the kernels in stream
+    order (dgpu_verify_segment_shard_device).  RLC mode runs the per-rank
+    protocol (dgpu_rlc_root_segment_device, the roots' all-gather,
+    dgpu_rlc_finish_device; `seed` as verify_rlc_sharded's) and returns no
+    randomness.  `stream` and the ordering rules are verify_rlc_sharded's:
+    stream waits, never a device-wide synchronize.  The verdict bits land in
+    d_bits (reasons in d_reason, randomness in d_randomness) in `stream`
+    order.  Measured with two ranks on one GPU only; RCCL with two or more
+    real ranks is unmeasured."""
+    import ctypes
+    import torch
+    from . import _lib
+    lib = ctx.lib
+    rlc = mode == _lib.MODE_RLC
+    if rlc and d_randomness is not None:
+        raise ValueError("the per-rank RLC protocol returns no randomness")
+    lo, hi = shard_range(n_total, world, rank)
+    n = hi - lo
+    dev = d_bits.device
+    s = ctypes.c_void_p(None if stream is None else stream.cuda_stream)
+    lib_stream = torch.cuda.default_stream(dev) if stream is None else stream
+    cur = torch.cuda.current_stream(dev)
+    pkb = pk if hasattr(pk, "ctypes") else np.frombuffer(bytes(pk), dtype=np.uint8).copy()
+    halo = None
+    if world > 1:
+        import torch.distributed as dist
+        off = halo_len_offset(sig_stride)
+        cur.wait_stream(lib_stream)  # the shard's records are written before the exchange reads them
+        last = torch.zeros(off + 4, dtype=torch.uint8, device=dev)
+        if n:
+            last[:sig_stride] = d_sigs.reshape(-1)[(n - 1) * sig_stride:n * sig_stride]
+            last[off:] = d_sig_len[n - 1:n].view(torch.uint8)
+        gloo = dist.get_backend() == "gloo"  # CPU collectives (tests): .cpu() waits on the current stream
+        got = exchange_halo(last.cpu() if gloo else last, n_total, world, rank)
+        if got is not None:
+            halo = got.to(dev)
+            lib_stream.wait_stream(cur)  # the halo is on the device before the library's kernels read it
+            halo.record_stream(lib_stream)
+    seedb = np.frombuffer(bytes(seed_prev or b""), dtype=np.uint8).copy()
+    seed_args = (_lib.ptr(seedb) if seedb.size else None, seedb.size)
+    halo_args = (None, None) if halo is None else (halo.data_ptr(), halo.data_ptr() + halo_len_offset(sig_stride))
+    first = int(first_round) + lo
+    opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    if not rlc:
+        if rank == 0 or n == 0:
+            _lib.check(lib.dgpu_verify_segment_device(ctx.handle, code, _lib.ptr(pkb), pkb.size, first, n,
+                                                      d_sigs.data_ptr(), sig_stride, d_sig_len.data_ptr(), *seed_args,
+                                                      mode, 0, d_bits.data_ptr(), opt(d_reason), opt(d_randomness), s),
+                       lib)
+        else:
+            _lib.check(lib.dgpu_verify_segment_shard_device(ctx.handle, code, _lib.ptr(pkb), pkb.size, first, n,
+                                                            d_sigs.data_ptr(), sig_stride, d_sig_len.data_ptr(),
+                                                            *halo_args, mode, 0, d_bits.data_ptr(), opt(d_reason),
+                                                            opt(d_randomness), s), lib)
+        return
+    rb = lib.dgpu_rlc_root_bytes(code)
+    _lib.check(min(rb, 0))
+    with torch.cuda.stream(lib_stream):  # root allocated in the library's stream order
+        root = torch.empty(rb, dtype=torch.uint8, device=dev)
+    _lib.check(lib.dgpu_rlc_root_segment_device(ctx.handle, code, _lib.ptr(pkb), pkb.size, first, n, d_sigs.data_ptr(),
+                                                sig_stride, d_sig_len.data_ptr(), *seed_args,
+                                                *(halo_args if rank and n else (None, None)),
+                                                rank_seed(seed, rank, world), root.data_ptr(), s), lib)
+    # (the halo tensor stays referenced until the finish step has been enqueued)
+    _finish_rlc_sharded(ctx, root, rb, world, d_bits, d_reason, s, lib_stream, cur)

@@ -10,7 +10,7 @@ drand_amd/dist.py; both shard with the same contiguous rule."""
 import numpy as np
 
 from . import _lib
-from .chain import pack_beacons, rlc_seed_for
+from .chain import pack_beacons, rlc_seed_for, verify_segment_with
 from .scheme import Scheme, scheme_code
 from .threshold import group_scheme_code, pack_partials, sig_bytes, unpack_recovered
 
@@ -48,6 +48,17 @@ class MultiVerifier:
         if not np.array_equal(valid, reason == _lib.REASON_OK):
             raise _lib.DrandGPUError(_lib.DGPU_EINVAL, "verdict bitmap and reasons disagree")
         return reason
+
+    def verify_segment(self, first_round, sigs, prev_sig, pubkey, mode=_lib.MODE_PER_ROUND, rlc_seed=None,
+                       randomness=True, sig_len=None):
+        """chain.Verifier.verify_segment over the handle's GPUs
+        (dgpu_verify_segment_multi): the same arguments, the same
+        (reasons, randomness) result.  The rounds shard contiguously; a later
+        shard's first round takes the record before the shard as its halo."""
+        lib = self.mctx.lib
+        return verify_segment_with(lambda *a: lib.dgpu_verify_segment_multi(self.mctx.handle, self._code, *a), lib,
+                                   self._code, first_round, sigs, prev_sig, pubkey, mode, rlc_seed, randomness,
+                                   sig_len)
 
 
 class MultiThresholdGroup:

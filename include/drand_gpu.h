@@ -62,7 +62,11 @@ extern "C" {
  * points follow the installed group's scheme (their out_sigs96 parameters
  * are now out_sigs, stride 96 or 48 bytes per round).  Also additive:
  * dgpu_verify_segment and dgpu_verify_segment_device, a linked chain segment
- * verified from its signatures alone, with the rounds' randomness. */
+ * verified from its signatures alone, with the rounds' randomness.  Also
+ * additive: linked segments across GPUs -- dgpu_verify_segment_shard_device
+ * (one shard, its first item's previous signature a one-record halo in device
+ * memory), dgpu_rlc_root_segment_device (step 1 of the per-rank RLC protocol
+ * over such a shard) and dgpu_verify_segment_multi. */
 #define DGPU_ABI_VERSION 3
 
 /* scheme IDs (common/scheme/scheme.go:9,12; bls-unchained-on-g1 added by this build) */
@@ -202,6 +206,36 @@ int dgpu_verify_segment_device(dgpu_ctx *ctx, int scheme, const uint8_t *pk, siz
                                const uint8_t *seed_prev, size_t seed_prev_len, int mode, uint64_t rlc_seed,
                                uint8_t *d_verdict_bits, uint8_t *d_reason, uint8_t *d_randomness32, void *stream);
 
+/* One shard of a linked segment, device-resident, asynchronous on `stream`:
+ * as dgpu_verify_segment_device with the seed replaced by a device halo.
+ * first_round is the shard's own first round; the previous signature of its
+ * first item is the one-record halo in device memory -- the neighbouring
+ * shard's last record, wherever a copy or a collective put it: *d_halo_len
+ * bytes at d_halo, a record of stride sig_stride like the shard's own (not
+ * capped at 96 bytes; never read past the stride).  Verdict bits, reasons and
+ * randomness equal dgpu_verify_beacons_device on the records
+ *   rounds[i] = first_round + i          (first_round + n - 1 must not
+ *                                         overflow 64 bits: DGPU_EINVAL)
+ *   prev[0] = halo, prev_len[0] = *d_halo_len
+ *   prev[i] = sigs[i-1], prev_len[i] = sig_len[i-1], prev_stride = sig_stride
+ * under the same key, mode and rlc_seed (randomness as dgpu_verify_segment
+ * defines it), so *d_halo_len > sig_stride is a decode failure of the first
+ * item, exactly what an over-long record does to the item after it inside a
+ * segment.  d_halo and d_halo_len are read by the kernels, in stream order: a
+ * copy or collective the caller enqueued on `stream` before the call is seen,
+ * and the call makes no host synchronisation on their account.  Chained
+ * scheme: a NULL d_halo or d_halo_len with n > 0 is DGPU_EINVAL.  The
+ * unchained and G1-signature schemes never touch the two pointers (they may
+ * be NULL).  n = 0 is a no-op that accepts NULL pointers.  RLC mode below
+ * DGPU_RLC_MIN rounds runs per round, as elsewhere.  Measured on one GPU
+ * only, like every multi-GPU path here: RCCL with two or more real ranks is
+ * unmeasured. */
+int dgpu_verify_segment_shard_device(dgpu_ctx *ctx, int scheme, const uint8_t *pk, size_t pk_len,
+                                     uint64_t first_round, size_t n, const uint8_t *d_sigs, size_t sig_stride,
+                                     const uint32_t *d_sig_len, const uint8_t *d_halo, const uint32_t *d_halo_len,
+                                     int mode, uint64_t rlc_seed, uint8_t *d_verdict_bits, uint8_t *d_reason,
+                                     uint8_t *d_randomness32, void *stream);
+
 /* Per-rank RLC protocol for callers that run one process (or one context)
  * per GPU and exchange data themselves -- the multi-process form of
  * dgpu_verify_multi's RLC mode (chain/beacon/sync_manager.go:188-222 sharded
@@ -228,6 +262,22 @@ int dgpu_rlc_root_device(dgpu_ctx *ctx, int scheme, const uint8_t *pk, size_t pk
                          uint8_t *d_root, void *stream);
 int dgpu_rlc_finish_device(dgpu_ctx *ctx, size_t n_roots, const uint8_t *d_roots, uint8_t *d_verdict_bits,
                            uint8_t *d_reason, void *stream);
+/* Step 1 of the per-rank RLC protocol over a linked shard; steps 2-3 are
+ * unchanged (the all-gather, dgpu_rlc_finish_device).  d_halo != NULL: the
+ * halo form of dgpu_verify_segment_shard_device (seed_prev is ignored);
+ * d_halo == NULL: the host seed by value, as dgpu_verify_segment_device (the
+ * rank that holds the segment's first round).  The pending root keeps the
+ * source, halo pointers included: they stay valid until
+ * dgpu_rlc_finish_device, as d_sigs already must.  Everything else is
+ * dgpu_rlc_root_device's: any other call cancels the pending root, n = 0
+ * yields the identity root, rlc_seed is per rank, and the finish step's
+ * verdicts equal dgpu_verify_segment_shard_device's on the shard.  The
+ * protocol returns no randomness (a walk needs it for the one round it
+ * returns).  RCCL with two or more real ranks is unmeasured. */
+int dgpu_rlc_root_segment_device(dgpu_ctx *ctx, int scheme, const uint8_t *pk, size_t pk_len, uint64_t first_round,
+                                 size_t n, const uint8_t *d_sigs, size_t sig_stride, const uint32_t *d_sig_len,
+                                 const uint8_t *seed_prev, size_t seed_prev_len, const uint8_t *d_halo,
+                                 const uint32_t *d_halo_len, uint64_t rlc_seed, uint8_t *d_root, void *stream);
 
 /* Batch key.Scheme.VerifyRecovered(pk, msg, sig) (= bls.Verify (R); call
  * sites chain/verify.go:44, chain/beacon/chain.go:165; AuthScheme
@@ -295,7 +345,7 @@ int dgpu_synchronize(dgpu_ctx *ctx);
 int dgpu_set_profiling(dgpu_ctx *ctx, int enable);
 /* Host-record staging of the last call on the context that took host records
  * (dgpu_verify_beacons, dgpu_verify_batch, dgpu_verify_recovered, a shard of
- * dgpu_verify_multi): the records go through a library-owned pinned ring
+ * dgpu_verify_multi or dgpu_verify_segment_multi): the records go through a library-owned pinned ring
  * (two 16 MiB slots per context, filled by host threads, DMA'd on the
  * context's copy stream) slice by slice, each slice's kernels starting when
  * its records have arrived.  device_ms = the staging's span on the copy
@@ -471,6 +521,27 @@ int dgpu_verify_multi(dgpu_multi *m, int scheme, const uint8_t *pk, size_t pk_le
                       const uint8_t *sigs, size_t sig_stride, const uint32_t *sig_len, const uint8_t *prev,
                       size_t prev_stride, const uint32_t *prev_len, int mode, uint64_t rlc_seed,
                       uint8_t *verdict_bits, uint8_t *reason);
+
+/* dgpu_verify_segment over the devices of a multi handle: arguments and
+ * results exactly as dgpu_verify_segment on one context (verdict bits,
+ * reasons and randomness, bit for bit, in both modes).  The shards follow
+ * dgpu_shard_range.  Shard 0 takes the caller's seed, by value; shard k > 0
+ * takes record lo_k - 1 of the caller's arrays as its halo
+ * (dgpu_verify_segment_shard_device): the library stages that record and its
+ * length into a small per-context buffer ahead of the shard's own records.
+ * Each shard's signatures go through its context's pinned ring once --
+ * n_k x (sig_stride + 4) bytes, which is what dgpu_staging_stats reports for
+ * the context; the halo's sig_stride + 4 bytes are staged beside them and are
+ * not counted in that figure.  Modes, per-device RLC seeds, the root
+ * all-gather and single check, the per-shard descent and the bitmap / reason
+ * gathers are dgpu_verify_multi's (the same code).  The randomness is
+ * computed per shard once the shard's statuses are final and goes from each
+ * device straight to randomness32 + 32 lo_k.  RCCL with two or more real
+ * ranks is unmeasured. */
+int dgpu_verify_segment_multi(dgpu_multi *m, int scheme, const uint8_t *pk, size_t pk_len, uint64_t first_round,
+                              size_t n, const uint8_t *sigs, size_t sig_stride, const uint32_t *sig_len,
+                              const uint8_t *seed_prev, size_t seed_prev_len, int mode, uint64_t rlc_seed,
+                              uint8_t *verdict_bits, uint8_t *reason, uint8_t *randomness32);
 
 /* dgpu_set_group on every device of the handle (the aggregator's group,
  * chain/beacon/chain.go:158-168 -> key.Scheme.Recover). */
