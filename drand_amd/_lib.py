@@ -76,6 +76,10 @@ SYMBOLS = [
                                        _c.c_size_t, _P, _c.c_int, _c.c_uint64, _P, _P]),
     ("dgpu_verify_beacons_device", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t, _c.c_size_t, _P, _P, _c.c_size_t, _P,
                                               _P, _c.c_size_t, _P, _c.c_int, _c.c_uint64, _P, _P, _P]),
+    ("dgpu_decode_rows_device", _c.c_int, [_P, _c.c_size_t, _P, _c.c_size_t, _P, _P, _P, _P, _c.c_size_t, _P, _P,
+                                           _c.c_size_t, _P, _P, _P]),
+    ("dgpu_verify_rows", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t, _c.c_size_t, _P, _P, _P, _c.c_size_t, _c.c_size_t,
+                                    _c.c_int, _c.c_uint64, _P, _P, _P, _P]),
     ("dgpu_verify_segment", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t, _c.c_uint64, _c.c_size_t, _P, _c.c_size_t, _P,
                                        _P, _c.c_size_t, _c.c_int, _c.c_uint64, _P, _P, _P]),
     ("dgpu_verify_segment_device", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t, _c.c_uint64, _c.c_size_t, _P,

@@ -214,6 +214,36 @@ class Verifier:
             raise _lib.DrandGPUError(_lib.DGPU_EINVAL, "verdict bitmap and reasons disagree")
         return reason
 
+    def verify_rows(self, pubkey, buf, off, ln, mode=_lib.MODE_PER_ROUND, rlc_seed=None, sig_stride=96,
+                    prev_stride=96):
+        """Stored rows (Beacon.Marshal's bytes; row i = buf[off[i]:off[i] +
+        ln[i]], as ingest.window_rows scans them), decoded and verified on the
+        GPU (dgpu_verify_rows).  Returns (reasons, row_ok, rounds): the
+        DGPU_REASON_* code per row, whether the row was canonical (the
+        others -- reason DGPU_REASON_DECODE -- are the caller's to decode
+        with sync.beacon_unmarshal), and each canonical row's Round."""
+        n = len(off)
+        reason = np.zeros(n, dtype=np.uint8)
+        ok = np.zeros(n, dtype=np.uint8)
+        rounds = np.zeros(n, dtype=np.uint64)
+        if n == 0:
+            return reason, ok.astype(bool), rounds
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        ln = np.ascontiguousarray(ln, dtype=np.uint32)
+        if int((off + ln).max()) > buf.size:
+            raise ValueError("a row leaves the buffer")
+        bits = np.zeros((n + 7) // 8, dtype=np.uint8)
+        pk = np.frombuffer(bytes(pubkey), dtype=np.uint8).copy()
+        lib = self.ctx.lib
+        _lib.check(lib.dgpu_verify_rows(self.ctx.handle, self._code, _lib.ptr(pk), pk.size, n, _lib.ptr(buf),
+                                        _lib.ptr(off), _lib.ptr(ln), sig_stride, prev_stride, mode,
+                                        rlc_seed_for(mode, rlc_seed), _lib.ptr(rounds), _lib.ptr(ok), _lib.ptr(bits),
+                                        _lib.ptr(reason)), lib)
+        valid = np.unpackbits(bits, bitorder="little")[:n].astype(bool)
+        if not np.array_equal(valid, reason == _lib.REASON_OK):
+            raise _lib.DrandGPUError(_lib.DGPU_EINVAL, "verdict bitmap and reasons disagree")
+        return reason, ok.astype(bool), rounds
+
     def verify_segment(self, first_round, sigs, prev_sig, pubkey, mode=_lib.MODE_PER_ROUND, rlc_seed=None,
                        randomness=True, sig_len=None):
         """A linked run of rounds known by its signatures alone

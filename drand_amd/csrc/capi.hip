@@ -30,6 +30,7 @@
 #include "g1sig.cuh"
 #include "rlc_msm.cuh"
 #include "recover_g1.cuh"
+#include "ingest_row.cuh"
 #include "scratch_layouts.h"
 
 using namespace dgpu;
@@ -362,6 +363,7 @@ struct dgpu_ctx {
   bool stage_pageable = false;   // A/B build, DGPU_STAGE=pageable: the round-5 whole-batch pageable copy
   // staging for host-pointer entry points
   DevBuf in_rounds, in_sigs, in_sig_len, in_prev, in_prev_len, in_msgs, in_msg_len, out_bits, out_reason, out_rand, misc;
+  DevBuf in_rows, in_row_ok;    // dgpu_verify_rows: the packed stored rows with their positions and lengths; the decoder's ok flags
   DevBuf in_halo, in_halo_len;  // a staged shard's halo (dgpu_verify_segment_multi): one record of the stride, its length
   // optional per-stage HIP-event timing of the last verify call (event pool;
   // durations are summed per stage name: chunked stages repeat)
@@ -1599,6 +1601,74 @@ int ring_copy_locked(dgpu_ctx* c, void* dst, const void* src, size_t bytes) {
   return DGPU_OK;
 }
 
+// The stored rows of a dgpu_verify_rows call.  The caller's rows (row i =
+// len[i] bytes at base + off[i]) are staged packed back to back: slen[i] is
+// the staged length (len[i], or 0 for a row longer than any canonical row at
+// the strides: it is non-canonical whatever it holds and is not staged),
+// pos[i] row i's position in the packed run (pos[n] = the run's bytes).  The
+// device side: the packed run and the two arrays (in_rows), and the record
+// arrays k_ingest_rows writes -- the context's in_* buffers, the verify
+// call's inputs.
+struct rows_src {
+  const uint8_t* base;
+  const uint64_t* off;
+  const uint32_t* len;
+  std::vector<uint32_t> slen;
+  std::vector<uint64_t> pos;
+  ingest_rows_layout dev;
+  uint64_t* d_rounds;
+  uint8_t *d_sigs, *d_prev, *d_ok;
+  uint32_t *d_sig_len, *d_prev_len;
+  size_t sig_stride, prev_stride;
+};
+
+// The ring bytes of rows [a, b) of a rows_src: the packed rows, then (on an
+// 8-byte boundary) their positions and their lengths.
+inline size_t rows_piece_bytes(const rows_src& R, size_t a, size_t b) {
+  return (((size_t)(R.pos[b] - R.pos[a]) + 7) & ~(size_t)7) + (b - a) * 12;
+}
+
+// Rows [a, b) of a rows_src, on the copy stream: cut by bytes into pieces of
+// whole rows, each piece the longest run whose ring bytes (rows_piece_bytes)
+// fit one slot; the pool's threads gather a piece's rows into the slot, its
+// three parts are DMA'd to in_rows, and k_ingest_rows decodes the piece into
+// its rows of the record arrays right behind its DMA.
+int ring_rows_locked(dgpu_ctx* c, const rows_src& R, size_t a, size_t b) {
+  while (a < b) {
+    size_t e = a + 1;  // (one row always fits: checked by the entry point)
+    {  // the last e in (a, b] with rows_piece_bytes(a, e) <= the slot: the bytes grow with e
+      size_t lo = a + 1, hi = b;
+      while (lo < hi) {
+        const size_t mid = lo + (hi - lo + 1) / 2;
+        if (rows_piece_bytes(R, a, mid) <= STAGE_SLOT_BYTES) lo = mid;
+        else hi = mid - 1;
+      }
+      e = lo;
+    }
+    const size_t m = e - a, pb = (size_t)(R.pos[e] - R.pos[a]), at_off = (pb + 7) & ~(size_t)7, at_len = at_off + m * 8;
+    const int k = c->ring_next;
+    c->ring_next ^= 1;
+    if (c->ring_busy[k]) HIP_TRY(hipEventSynchronize(c->ring_ev[k]));  // its previous DMA has read the slot
+    uint8_t* slot = (uint8_t*)c->ring[k];
+    host_copy_pool().gather(slot, R.base, R.off + a, R.slen.data() + a, R.pos.data() + a, m);
+    memcpy(slot + at_off, R.pos.data() + a, m * 8);
+    memcpy(slot + at_len, R.slen.data() + a, m * 4);
+    if (pb) HIP_TRY(hipMemcpyAsync(R.dev.bytes + R.pos[a], slot, pb, hipMemcpyHostToDevice, c->stream_copy));
+    HIP_TRY(hipMemcpyAsync(R.dev.off + a, slot + at_off, m * 8, hipMemcpyHostToDevice, c->stream_copy));
+    HIP_TRY(hipMemcpyAsync(R.dev.len + a, slot + at_len, m * 4, hipMemcpyHostToDevice, c->stream_copy));
+    HIP_TRY(hipEventRecord(c->ring_ev[k], c->stream_copy));
+    c->ring_busy[k] = true;
+    // the piece's rows lie in [0, pos[e]) of the packed run: nothing behind it is on the device yet
+    hipLaunchKernelGGL(k_ingest_rows, dim3(grid_for(m, INGEST_ROWS_PER_WAVE)), dim3(INGEST_ROWS_PER_WAVE), 0,
+                       c->stream_copy, m, (const uint8_t*)R.dev.bytes, (size_t)R.pos[e], (const uint64_t*)R.dev.off + a,
+                       (const uint32_t*)R.dev.len + a, R.d_rounds + a, R.d_sigs + a * R.sig_stride, R.sig_stride,
+                       R.d_sig_len + a, R.d_prev + a * R.prev_stride, R.prev_stride, R.d_prev_len + a, R.d_ok + a);
+    HIP_TRY(hipGetLastError());
+    a = e;
+  }
+  return DGPU_OK;
+}
+
 int ring_ensure_locked(dgpu_ctx* c) {
   for (int k = 0; k < 2; ++k) {
     if (c->ring[k]) continue;
@@ -1626,6 +1696,7 @@ int ring_ensure_locked(dgpu_ctx* c) {
 struct host_stager {
   dgpu_ctx* c;
   verify_args host;               // the caller's pointers
+  const rows_src* rows = nullptr;  // dgpu_verify_rows: the records are decoded on the device from these stored rows
   std::vector<size_t> lo;         // slice k = [lo[k], lo[k + 1])
   std::vector<hipEvent_t> ev_msg, ev_sig;
   std::thread th;
@@ -1673,6 +1744,21 @@ struct host_stager {
     const msg_src_host& m = host.m;
     const size_t n = b - a;
     int r;
+    if (rows) {
+      // Stored rows: the slice's rows and their decode, then both events -- the
+      // records of slice k exist once its k_ingest_rows launches have run.
+      // Staged bytes: the staged rows and 12 bytes (position, length) per row.
+      if ((r = ring_rows_locked(c, *rows, a, b))) return r;
+      bytes += (size_t)(rows->pos[b] - rows->pos[a]) + n * 12;
+      HIP_TRY(hipEventRecord(ev_msg[k], c->stream_copy));
+      {
+        std::lock_guard<std::mutex> lk(mu);
+        staged_msg = k + 1;
+      }
+      cv.notify_all();
+      HIP_TRY(hipEventRecord(ev_sig[k], c->stream_copy));
+      return DGPU_OK;
+    }
     // A shard's halo (one record of the stride and its length, not counted in
     // `bytes`) ahead of everything else of the call on the in-order copy
     // stream: every event a kernel waits for covers it.
@@ -1799,10 +1885,27 @@ int stage_prepare_locked(dgpu_ctx* c, verify_args& a) {
 // verify_status_locked over host records, overlapping their staging with the
 // verification: the slices are the per-round G2 path's lane slices
 // (lane_slice_len), one slice for every other pipeline.
-int verify_status_host_locked(dgpu_ctx* c, const key_entry* key, verify_args& a, hipStream_t s) {
+// rows (dgpu_verify_rows): a's records are decoded on the device from these
+// stored rows, slice by slice behind their DMA; a's pointers become the
+// record arrays the decoder writes.
+int verify_status_host_locked(dgpu_ctx* c, const key_entry* key, verify_args& a, hipStream_t s,
+                              rows_src* rows = nullptr) {
   host_stager stg(c, a);
   int rc;
   if ((rc = stage_prepare_locked(c, a))) return rc;
+  if (rows) {
+    // the decoder writes every row's previous signature, whatever the scheme reads
+    if ((rc = c->in_prev.ensure(a.n * rows->prev_stride + 1)) || (rc = c->in_prev_len.ensure(a.n * 4)) ||
+        (rc = c->in_row_ok.ensure(a.n)) || (rc = carve(c->in_rows, &rows->dev, (size_t)rows->pos[a.n], a.n)))
+      return rc;
+    rows->d_rounds = (uint64_t*)c->in_rounds.p;
+    rows->d_sigs = (uint8_t*)c->in_sigs.p;
+    rows->d_sig_len = (uint32_t*)c->in_sig_len.p;
+    rows->d_prev = (uint8_t*)c->in_prev.p;
+    rows->d_prev_len = (uint32_t*)c->in_prev_len.p;
+    rows->d_ok = (uint8_t*)c->in_row_ok.p;
+    stg.rows = rows;
+  }
   // the copy stream (device buffers, ring slots) after the previous call's work
   HIP_TRY(hipStreamWaitEvent(c->stream_copy, c->done, 0));
   const size_t n0 = lane_slice_len(c, a);
@@ -1875,6 +1978,47 @@ int verify_host_pageable_locked(dgpu_ctx* c, const key_entry* key, verify_args a
   HIP_TRY(hipMemcpyAsync(verdict_bits, c->out_bits.p, (a.n + 7) / 8, hipMemcpyDeviceToHost, s));
   if (reason) HIP_TRY(hipMemcpyAsync(reason, c->out_reason.p, a.n, hipMemcpyDeviceToHost, s));
   if (rand32) HIP_TRY(hipMemcpyAsync(rand32, c->out_rand.p, a.n * 32, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return DGPU_OK;
+}
+
+// dgpu_verify_rows: verify_host_locked with the records decoded on the device
+// from the caller's stored rows; the decoder's ok flags and rounds come back
+// with the verdicts.
+int verify_rows_locked(dgpu_ctx* c, const key_entry* key, verify_args a, const uint8_t* base, const uint64_t* row_off,
+                       const uint32_t* row_len, size_t prev_stride, uint64_t* rounds_out, uint8_t* row_ok,
+                       uint8_t* verdict_bits, uint8_t* reason) {
+  verify_args a0 = a;  // scheme, mode and key before anything else (n = 0 checks no buffers)
+  a0.n = 0;
+  int rc = check_args(c, key, a0);
+  if (rc || a.n == 0) return rc;
+  if (!base || !row_off || !row_len || !row_ok || !verdict_bits) return set_err(DGPU_EINVAL, "null row or output buffer");
+  if (a.sig_stride < (sig_on_g1(a.scheme) ? 48u : 96u)) return set_err(DGPU_EINVAL, "bad signature stride");
+  const size_t max_len = ingest_row_max_len(a.sig_stride, prev_stride);
+  if (a.sig_stride > STAGE_SLOT_BYTES || prev_stride > STAGE_SLOT_BYTES || max_len + 16 > STAGE_SLOT_BYTES)
+    return set_err(DGPU_EINVAL, "strides too large for the staging ring");
+  rows_src R{};
+  R.base = base, R.off = row_off, R.len = row_len;
+  R.sig_stride = a.sig_stride, R.prev_stride = prev_stride;
+  R.slen.resize(a.n);
+  R.pos.resize(a.n + 1);
+  uint64_t at = 0;
+  for (size_t i = 0; i < a.n; ++i) {
+    R.slen[i] = row_len[i] <= max_len ? row_len[i] : 0;
+    R.pos[i] = at;
+    at += R.slen[i];
+  }
+  R.pos[a.n] = at;
+  hipStream_t s = c->stream;
+  stream_order ord(c, s);
+  if ((rc = c->out_bits.ensure((a.n + 7) / 8)) || (rc = c->out_reason.ensure(a.n))) return rc;
+  if ((rc = verify_status_host_locked(c, key, a, s, &R)) ||
+      (rc = pack_results_locked(c, a, (uint8_t*)c->out_bits.p, nullptr, s)))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(verdict_bits, c->out_bits.p, (a.n + 7) / 8, hipMemcpyDeviceToHost, s));
+  if (reason) HIP_TRY(hipMemcpyAsync(reason, c->status.p, a.n, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(row_ok, R.d_ok, a.n, hipMemcpyDeviceToHost, s));
+  if (rounds_out) HIP_TRY(hipMemcpyAsync(rounds_out, R.d_rounds, a.n * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return DGPU_OK;
 }
@@ -2115,6 +2259,42 @@ int dgpu_verify_beacons_device(dgpu_ctx* c, int scheme, const uint8_t* pk, size_
   const verify_args a{scheme, n, beacon_src(d_rounds, d_prev, prev_stride, d_prev_len, scheme == DGPU_SCHEME_CHAINED),
                       d_sigs, sig_stride, d_sig_len, mode, rlc_seed};
   return verify_device_locked(c, k, a, d_bits, d_reason, s);
+}
+
+int dgpu_decode_rows_device(dgpu_ctx* c, size_t n, const uint8_t* d_rows, size_t rows_bytes, const uint64_t* d_row_off,
+                            const uint32_t* d_row_len, uint64_t* d_rounds, uint8_t* d_sigs, size_t sig_stride,
+                            uint32_t* d_sig_len, uint8_t* d_prev, size_t prev_stride, uint32_t* d_prev_len, uint8_t* d_ok,
+                            void* stream) {
+  if (!c) return set_err(DGPU_EINVAL, "null ctx");
+  if (n == 0) return DGPU_OK;
+  if (!d_row_off || !d_row_len || !d_rounds || !d_sigs || !d_sig_len || !d_prev_len || !d_ok ||
+      (!d_rows && rows_bytes) || (!d_prev && prev_stride))
+    return set_err(DGPU_EINVAL, "null row or record buffer");
+  if (n > (size_t)0x7fffffff * INGEST_ROWS_PER_WAVE) return set_err(DGPU_EINVAL, "too many rows");
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = caller_stream(stream);
+  stream_order ord(c, s);
+  hipLaunchKernelGGL(k_ingest_rows, dim3(grid_for(n, INGEST_ROWS_PER_WAVE)), dim3(INGEST_ROWS_PER_WAVE), 0, s, n, d_rows,
+                     rows_bytes, d_row_off, d_row_len, d_rounds, d_sigs, sig_stride, d_sig_len, d_prev, prev_stride,
+                     d_prev_len, d_ok);
+  HIP_TRY(hipGetLastError());
+  return DGPU_OK;
+}
+
+int dgpu_verify_rows(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t pk_len, size_t n, const uint8_t* base,
+                     const uint64_t* row_off, const uint32_t* row_len, size_t sig_stride, size_t prev_stride, int mode,
+                     uint64_t rlc_seed, uint64_t* rounds_out, uint8_t* row_ok, uint8_t* verdict_bits, uint8_t* reason) {
+  if (!c) return set_err(DGPU_EINVAL, "null ctx");
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  key_entry* k = nullptr;
+  int rc = get_key_locked(c, scheme, pk, pk_len, &k);
+  if (rc) return rc;
+  // (the record pointers are the context's buffers once the call is staged)
+  const verify_args a{scheme, n, beacon_src(nullptr, nullptr, prev_stride, nullptr, scheme == DGPU_SCHEME_CHAINED),
+                      nullptr, sig_stride, nullptr, mode, rlc_seed};
+  return verify_rows_locked(c, k, a, base, row_off, row_len, prev_stride, rounds_out, row_ok, verdict_bits, reason);
 }
 
 // The arguments of the two segment entry points that no other call has.

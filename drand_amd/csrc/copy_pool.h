@@ -1,5 +1,6 @@
 // Host memcpy on a few pooled threads (pageable -> pinned runs at host memory
-// bandwidth only when several cores copy).  Host-only C++17, no HIP: capi.hip
+// bandwidth only when several cores copy), and the gather of scattered rows
+// into one packed run on the same threads.  Host-only C++17, no HIP: capi.hip
 // fills the staging ring's pinned slots through it, and
 // tests/copy_pool_check.cpp builds it alone under the host sanitizers.
 #pragma once
@@ -69,6 +70,39 @@ class copy_pool {
     std::unique_lock<std::mutex> lk(b.mu);
     b.cv.wait(lk, [&] { return b.left == 0; });
   }
+  // Gather: row i (len[i] bytes at base + off[i], i < n) -> dst + (pos[i] -
+  // pos[0]), the rows split across the pool in runs of equal byte share;
+  // returns when every row is copied.  pos is ascending with pos[i + 1] >=
+  // pos[i] + len[i] (the packed positions of the rows: a prefix sum of len),
+  // so the runs write disjoint ranges of dst.
+  void gather(void* dst, const uint8_t* base, const uint64_t* off, const uint32_t* len, const uint64_t* pos, size_t n) {
+    if (!n) return;
+    const size_t bytes = (size_t)(pos[n - 1] - pos[0]) + len[n - 1];
+    const size_t parts = std::min(th_.size(), bytes / COPY_POOL_MIN_PART + (bytes % COPY_POOL_MIN_PART != 0));
+    if (parts <= 1) {
+      gather_rows((uint8_t*)dst, base, off, len, pos, pos[0], 0, n);
+      return;
+    }
+    batch b;
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      // run p ends at the first row whose packed position reaches share p + 1
+      size_t lo = 0;
+      for (size_t p = 0; p < parts && lo < n; ++p) {
+        const uint64_t until = pos[0] + (uint64_t)(bytes / parts) * (p + 1);
+        const size_t hi = p + 1 == parts ? n : (size_t)(std::lower_bound(pos + lo, pos + n, until) - pos);
+        if (hi == lo) continue;
+        task t{(uint8_t*)dst, base, hi - lo, &b};
+        t.off = off + lo, t.len = len + lo, t.pos = pos + lo, t.pos0 = pos[0];
+        q_.push_back(t);
+        ++b.left;
+        lo = hi;
+      }
+    }
+    cv_.notify_all();
+    std::unique_lock<std::mutex> lk(b.mu);
+    b.cv.wait(lk, [&] { return b.left == 0; });
+  }
 
  private:
   struct batch {
@@ -81,7 +115,17 @@ class copy_pool {
     const uint8_t* s;
     size_t n;
     batch* b;
+    // a gather task (off != nullptr): n rows, d / s the bases of gather()
+    const uint64_t* off = nullptr;
+    const uint32_t* len = nullptr;
+    const uint64_t* pos = nullptr;
+    uint64_t pos0 = 0;
   };
+  static void gather_rows(uint8_t* dst, const uint8_t* base, const uint64_t* off, const uint32_t* len,
+                          const uint64_t* pos, uint64_t pos0, size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; ++i)
+      if (len[i]) memcpy(dst + (pos[i] - pos0), base + off[i], len[i]);
+  }
   void work() {
     for (;;) {
       task t;
@@ -92,7 +136,8 @@ class copy_pool {
         t = q_.front();
         q_.pop_front();
       }
-      memcpy(t.d, t.s, t.n);
+      if (t.off) gather_rows(t.d, t.s, t.off, t.len, t.pos, t.pos0, 0, t.n);
+      else memcpy(t.d, t.s, t.n);
       std::lock_guard<std::mutex> lk(t.b->mu);
       if (--t.b->left == 0) t.b->cv.notify_all();
     }

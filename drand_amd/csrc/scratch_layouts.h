@@ -226,6 +226,22 @@ struct commits_misc {
   }
 };
 
+// ---------------------------------------------------------------- row ingest
+// in_rows (dgpu_verify_rows): a call's stored rows packed back to back, then
+// each row's position in that run and its length -- k_ingest_rows' inputs.
+// The packed run starts on a 16-byte line (the kernel's 16-byte loads are
+// aligned by address, whatever a row's position).
+struct ingest_rows_layout {
+  uint8_t* bytes;  // [packed_bytes]
+  uint64_t* off;   // [n]
+  uint32_t* len;   // [n]
+  void fill(carver& c, size_t packed_bytes, size_t n) {
+    bytes = c.take<uint8_t>(packed_bytes, 16);
+    off = c.take<uint64_t>(n);
+    len = c.take<uint32_t>(n);
+  }
+};
+
 // ---------------------------------------------------------------- recovery
 // rec_sel: the t selected items of a round, then their indices
 struct rec_sel_layout {

@@ -133,6 +133,23 @@ def decode(buf, off, ln, raw=None, sig_stride=96, prev_stride=96):
     return rounds, sigs, sig_len, prev, prev_len, ok.astype(bool)
 
 
+class Rows:
+    """One window of stored rows, undecoded: `keys` (the rows' rounds by key,
+    ascending), and row i = buf[off[i]:off[i] + len[i]]."""
+
+    __slots__ = ("lo", "hi", "keys", "off", "len", "buf")
+
+    def __init__(self, lo, hi, keys, off, ln, buf):
+        self.lo, self.hi, self.keys, self.off, self.len, self.buf = lo, hi, keys, off, ln, buf
+
+
+def window_rows(store, lo, hi):
+    """The rows of rounds [lo, hi) of a BoltStore, scan only: what
+    Verifier.verify_rows decodes on the GPU (dgpu_verify_rows)."""
+    rr, off, ln, buf = store.scan_offsets(lo, hi)
+    return Rows(lo, hi, rr, np.ascontiguousarray(off, dtype=np.uint64), np.ascontiguousarray(ln, dtype=np.uint32), buf)
+
+
 def window_records(store, lo, hi):
     """Records of rounds [lo, hi) of a BoltStore (native scan + decode)."""
     rr, off, ln, buf = store.scan_offsets(lo, hi)

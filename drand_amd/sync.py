@@ -129,15 +129,25 @@ class MemoryStore:
         return beacon_unmarshal(v)
 
 
-def check_past_beacons(store, verifier, pubkey, up_to, cb=None, window=1 << 16, cancelled=None, mode=0):
+def check_past_beacons(store, verifier, pubkey, up_to, cb=None, window=1 << 16, cancelled=None, mode=0,
+                       decode="host"):
     """SyncManager.CheckPastBeacons (chain/beacon/sync_manager.go:171-232).
 
     `verifier` is a drand_amd.chain.Verifier (GPU); `pubkey` the group key
-    bytes.  Returns the ascending list of faulty rounds, or None."""
+    bytes.  Returns the ascending list of faulty rounds, or None.
+    decode="device" (a BoltStore and a verifier with verify_rows): the
+    windows' rows are decoded on the GPU (_check_past_records); the result
+    and the callbacks are those of decode="host"."""
+    if decode not in ("host", "device"):
+        raise ValueError(f"decode must be 'host' or 'device', not {decode!r}")
     last = store.last()
     if last.round < up_to:
         up_to = last.round
     n = store.len()
+    if decode == "device":
+        if not (hasattr(store, "scan_offsets") and hasattr(verifier, "verify_rows")):
+            raise ValueError("decode='device' needs a BoltStore and a verifier with verify_rows")
+        return _check_past_records(store, verifier, pubkey, up_to, n, cb, window, cancelled, mode, device=True)
     if hasattr(store, "scan_offsets") and hasattr(verifier, "verify_records"):
         return _check_past_records(store, verifier, pubkey, up_to, n, cb, window, cancelled, mode)
     faulty = []
@@ -183,7 +193,36 @@ def check_past_beacons(store, verifier, pubkey, up_to, cb=None, window=1 << 16, 
     return faulty or None
 
 
-def _check_past_records(store, verifier, pubkey, up_to, n, cb, window, cancelled, mode):
+def _verify_window_rows(verifier, pubkey, rows, mode):
+    """One window of stored rows (ingest.Rows) through Verifier.verify_rows:
+    (bad, index, rounds, reasons) as the host path has them -- the window
+    positions that are missing or do not unmarshal, and for every decodable
+    row its position, its stored Round and its DGPU_REASON_* code.  The rows
+    the device decoder leaves (not canonical) go through beacon_unmarshal, as
+    the native host decoder's do, and the decodable ones are verified in one
+    explicit-record call."""
+    import numpy as np
+    reasons, ok, rounds = verifier.verify_rows(pubkey, rows.buf, rows.off, rows.len, mode)
+    pos = (rows.keys - np.uint64(rows.lo)).astype(np.int64)
+    present = np.zeros(rows.hi - rows.lo, dtype=bool)
+    present[pos] = True
+    bad = ~present
+    left, beacons = [], []
+    for i in np.nonzero(~ok)[0].tolist():
+        try:
+            beacons.append(beacon_unmarshal(bytes(rows.buf[rows.off[i]:rows.off[i] + rows.len[i]])))
+            left.append(i)
+        except ValueError:
+            bad[pos[i]] = True
+    keep = ok.copy()
+    if left:
+        keep[left] = True
+        rounds[left] = [b.round for b in beacons]
+        reasons[left] = verifier.verify_reasons(beacons, pubkey, mode)
+    return np.nonzero(bad)[0], pos[keep], rounds[keep], reasons[keep]
+
+
+def _check_past_records(store, verifier, pubkey, up_to, n, cb, window, cancelled, mode, device=False):
     """CheckPastBeacons over a BoltStore with the native ingest
     (drand_amd/ingest.py): each window's rows are walked and decoded into
     fixed-stride records off the Python heap -- the next window's while the
@@ -191,10 +230,13 @@ def _check_past_records(store, verifier, pubkey, up_to, n, cb, window, cancelled
     replayed with the loop's exact rules: rounds visited 1 .. min(Len-1,
     upTo); a missing or undecodable row faults its round i, a failed
     verification the stored beacon's Round; callbacks and cancellation per
-    visited round when given."""
+    visited round when given.  device=True: a window is scanned only
+    (ingest.window_rows) and its rows are decoded on the GPU
+    (_verify_window_rows); everything after is the same replay."""
     import numpy as np
     from concurrent.futures import ThreadPoolExecutor
-    from .ingest import window_records
+    from .ingest import window_records, window_rows
+    fetch = window_rows if device else window_records
     # visited rounds: [1, end) -- round 1 always (the loop tests i >= upTo only
     # after checking round i, sync_manager.go:188-221), so up_to = 0 checks it too
     end = min(n, max(up_to, 1) + 1)
@@ -203,22 +245,26 @@ def _check_past_records(store, verifier, pubkey, up_to, n, cb, window, cancelled
     bounds = [(lo, min(end, lo + window)) for lo in range(1, end, window)]
     faulty = []
     with ThreadPoolExecutor(1) as ex:
-        nxt = ex.submit(window_records, store, *bounds[0])
+        nxt = ex.submit(fetch, store, *bounds[0])
         for k in range(len(bounds)):
             rec = nxt.result()
             if k + 1 < len(bounds):
-                nxt = ex.submit(window_records, store, *bounds[k + 1])
-            reasons = verifier.verify_records(pubkey, rec.rounds, rec.sigs, rec.sig_len, rec.prev, rec.prev_len,
-                                              mode) if len(rec.rounds) else np.zeros(0, dtype=np.uint8)
+                nxt = ex.submit(fetch, store, *bounds[k + 1])
+            if device:
+                bad, index, rounds, reasons = _verify_window_rows(verifier, pubkey, rec, mode)
+            else:
+                bad, index, rounds = rec.bad, rec.index, rec.rounds
+                reasons = verifier.verify_records(pubkey, rec.rounds, rec.sigs, rec.sig_len, rec.prev, rec.prev_len,
+                                                  mode) if len(rec.rounds) else np.zeros(0, dtype=np.uint8)
             # the faulty value of every visited round of the window, in order
             size = rec.hi - rec.lo
             val = np.zeros(size, dtype=np.uint64)
             hit = np.zeros(size, dtype=bool)
-            hit[rec.bad] = True
-            val[rec.bad] = rec.lo + rec.bad.astype(np.uint64)
+            hit[bad] = True
+            val[bad] = rec.lo + bad.astype(np.uint64)
             fail = reasons != 0
-            hit[rec.index[fail]] = True
-            val[rec.index[fail]] = rec.rounds[fail]
+            hit[index[fail]] = True
+            val[index[fail]] = rounds[fail]
             if cb is None and cancelled is None:
                 faulty.extend(val[hit].tolist())
                 continue

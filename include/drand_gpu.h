@@ -168,6 +168,53 @@ int dgpu_verify_beacons_device(dgpu_ctx *ctx, int scheme, const uint8_t *pk, siz
                                const uint32_t *d_prev_len, int mode, uint64_t rlc_seed, uint8_t *d_verdict_bits,
                                uint8_t *d_reason, void *stream);
 
+/* Stored beacon rows -> fixed-stride records, on the device (check-chain
+ * ingest: the rows of the bolt beacon store as Beacon.Marshal wrote them,
+ * chain/beacon.go:34-37).  Row i is d_row_len[i] bytes at d_rows +
+ * d_row_off[i] inside the device buffer [d_rows, d_rows + rows_bytes); nothing
+ * outside that buffer is read, whatever its alignment, and a row whose range
+ * leaves it is not read and gets ok = 0.  The contract is the host decoder's
+ * (dgpu_ingest_decode of include/drand_ingest.h), byte for byte.  Canonical
+ * form only:
+ *   {"PreviousSig":<hex or null>,"Round":<uint64>,"Signature":<hex or null>}
+ * in Go's field order with no whitespace; a field is null or a quoted
+ * even-length hex string of either letter case holding at most its stride in
+ * bytes; Round is 1-20 digits with no leading zero that fit 64 bits; the
+ * closing brace is the row's last byte.  A canonical row: d_ok[i] = 1,
+ * d_rounds[i], d_sig_len[i] bytes at d_sigs + i*sig_stride and d_prev_len[i]
+ * bytes at d_prev + i*prev_stride, each zero-padded to its stride.  Any other
+ * row: d_ok[i] = 0, round 0, both lengths 0, both records zeroed -- an
+ * ordinary decode failure for the verify calls; the caller passes such rows
+ * to its full hexjson decoder.  No field is written past its stride.  The
+ * outputs must not overlap the rows or each other.  Asynchronous on `stream`
+ * (as dgpu_verify_beacons_device); n = 0 is a no-op that accepts NULL
+ * pointers. */
+int dgpu_decode_rows_device(dgpu_ctx *ctx, size_t n, const uint8_t *d_rows, size_t rows_bytes,
+                            const uint64_t *d_row_off, const uint32_t *d_row_len, uint64_t *d_rounds, uint8_t *d_sigs,
+                            size_t sig_stride, uint32_t *d_sig_len, uint8_t *d_prev, size_t prev_stride,
+                            uint32_t *d_prev_len, uint8_t *d_ok, void *stream);
+
+/* dgpu_verify_beacons over stored rows in host memory: row i is row_len[i]
+ * bytes at base + row_off[i], exactly what dgpu_ingest_scan emits over the
+ * mapped store.  The rows are decoded on the device: row_ok (n bytes) and
+ * rounds_out (optional, n values) equal the host decoder's ok and rounds at
+ * these strides, and verdict_bits and reason equal dgpu_verify_beacons on the
+ * arrays the host decoder writes, under the same key, mode and rlc_seed (a
+ * row with row_ok = 0 is a zeroed record: reason DGPU_REASON_DECODE; the
+ * caller passes it to its full hexjson decoder).  A row longer than any
+ * canonical row at the strides, 64 + 2 (sig_stride + prev_stride) bytes, is
+ * not canonical and is not staged.  The rows go through the pinned ring of
+ * dgpu_staging_stats packed back to back, cut by bytes into pieces of whole
+ * rows (a piece is the longest run of rows whose packed bytes, rounded up to
+ * 8, plus 12 bytes per row fit a 16 MiB slot); each piece is decoded on the
+ * copy stream behind its DMA, and a slice's hash waits for that slice's
+ * decode alone.  Staged bytes (dgpu_staging_stats):
+ *   sum of row_len[i] over the rows within 64 + 2 (sig_stride + prev_stride)
+ *   + 12 n   (each row's position and length). */
+int dgpu_verify_rows(dgpu_ctx *ctx, int scheme, const uint8_t *pk, size_t pk_len, size_t n, const uint8_t *base,
+                     const uint64_t *row_off, const uint32_t *row_len, size_t sig_stride, size_t prev_stride, int mode,
+                     uint64_t rlc_seed, uint64_t *rounds_out, uint8_t *row_ok, uint8_t *verdict_bits, uint8_t *reason);
+
 /* A linked chain segment verified from its signatures alone: the walk from a
  * point of trust, client/verify.go:118-178, which builds each beacon as
  * {PreviousSig: the signature before it, Round, Signature} and (line 207)
@@ -345,7 +392,8 @@ int dgpu_synchronize(dgpu_ctx *ctx);
 int dgpu_set_profiling(dgpu_ctx *ctx, int enable);
 /* Host-record staging of the last call on the context that took host records
  * (dgpu_verify_beacons, dgpu_verify_batch, dgpu_verify_recovered, a shard of
- * dgpu_verify_multi or dgpu_verify_segment_multi): the records go through a library-owned pinned ring
+ * dgpu_verify_multi or dgpu_verify_segment_multi) or stored rows
+ * (dgpu_verify_rows: its bytes are stated there): the records go through a library-owned pinned ring
  * (two 16 MiB slots per context, filled by host threads, DMA'd on the
  * context's copy stream) slice by slice, each slice's kernels starting when
  * its records have arrived.  device_ms = the staging's span on the copy
