@@ -80,6 +80,11 @@ SYMBOLS = [
                                            _c.c_size_t, _P, _P, _P]),
     ("dgpu_verify_rows", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t, _c.c_size_t, _P, _P, _P, _c.c_size_t, _c.c_size_t,
                                     _c.c_int, _c.c_uint64, _P, _P, _P, _P]),
+    ("dgpu_faulty_rounds_device", _c.c_int, [_P, _c.c_uint64, _c.c_size_t, _c.c_size_t, _P, _P, _P, _P, _P, _P,
+                                             _c.c_size_t, _P, _c.c_size_t, _P, _P]),
+    ("dgpu_check_rows", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t, _c.c_size_t, _P, _P, _P, _P, _c.c_size_t,
+                                   _c.c_size_t, _c.c_int, _c.c_uint64, _c.c_uint64, _c.c_size_t, _P, _P, _c.c_size_t,
+                                   _P, _P, _c.c_size_t, _P, _P]),
     ("dgpu_verify_segment", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t, _c.c_uint64, _c.c_size_t, _P, _c.c_size_t, _P,
                                        _P, _c.c_size_t, _c.c_int, _c.c_uint64, _P, _P, _P]),
     ("dgpu_verify_segment_device", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t, _c.c_uint64, _c.c_size_t, _P,
@@ -107,6 +112,9 @@ SYMBOLS = [
                                      _c.c_size_t, _P, _c.c_int, _c.c_uint64, _P, _P]),
     ("dgpu_verify_segment_multi", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t, _c.c_uint64, _c.c_size_t, _P, _c.c_size_t,
                                              _P, _P, _c.c_size_t, _c.c_int, _c.c_uint64, _P, _P, _P]),
+    ("dgpu_check_rows_multi", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t, _c.c_size_t, _P, _P, _P, _P, _c.c_size_t,
+                                         _c.c_size_t, _c.c_int, _c.c_uint64, _c.c_uint64, _c.c_size_t, _P, _P,
+                                         _c.c_size_t, _P, _P, _c.c_size_t, _P, _P]),
     ("dgpu_multi_set_group", _c.c_int, [_P, _c.c_int, _c.c_int, _P]),
     ("dgpu_multi_set_group_scheme", _c.c_int, [_P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_size_t]),
     ("dgpu_recover_multi", _c.c_int, [_P, _c.c_size_t, _P, _c.c_size_t, _P, _c.c_size_t, _P, _P, _P, _P]),

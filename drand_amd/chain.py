@@ -147,6 +147,37 @@ def verify_segment_with(call, lib, code, first_round, sigs, prev_sig, pubkey, mo
     return reason, rand
 
 
+def check_rows_with(call, lib, pubkey, rows, first, count, mode, rlc_seed, sig_stride=96, prev_stride=96,
+                    reasons=False):
+    """The packing of a dgpu_check_rows call, shared by Verifier.check_rows
+    and multi.MultiVerifier.check_rows: `call` is the entry point with its
+    handle and scheme bound, taking the arguments from pk on.  The lists are
+    given room for every position and every row (untouched pages of an empty
+    array cost nothing; the library copies back the entries there are)."""
+    n = len(rows.off)
+    first, count = int(first), int(count)
+    off = np.ascontiguousarray(rows.off, dtype=np.uint64)
+    ln = np.ascontiguousarray(rows.len, dtype=np.uint32)
+    keys = np.ascontiguousarray(rows.keys, dtype=np.uint64)
+    if len(ln) != n or len(keys) != n:
+        raise ValueError("rows.keys, rows.off and rows.len differ in length")
+    if n and int((off + ln).max()) > rows.buf.size:
+        raise ValueError("a row leaves the buffer")
+    pos = np.empty(count, dtype=np.uint64)
+    val = np.empty(count, dtype=np.uint64)
+    left = np.empty(n, dtype=np.uint64)
+    nf, nl = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint64)
+    reason = np.zeros(n, dtype=np.uint8) if reasons else None
+    pk = np.frombuffer(bytes(pubkey), dtype=np.uint8).copy()
+    _lib.check(call(_lib.ptr(pk), pk.size, n, _lib.ptr(rows.buf) if n else None, _lib.ptr(off) if n else None,
+                    _lib.ptr(ln) if n else None, _lib.ptr(keys) if n else None, sig_stride, prev_stride, mode,
+                    rlc_seed_for(mode, rlc_seed), first, count, _lib.ptr(pos) if count else None,
+                    _lib.ptr(val) if count else None, count, _lib.ptr(nf), _lib.ptr(left) if n else None, n,
+                    _lib.ptr(nl), _lib.ptr(reason) if reasons and n else None), lib)
+    out = pos[:int(nf[0])].copy(), val[:int(nf[0])].copy(), left[:int(nl[0])].copy()
+    return out + (reason,) if reasons else out
+
+
 class Verifier:
     """chain.Verifier (chain/verify.go:13-20): stateless apart from the scheme;
     safe for concurrent use (the GPU context serializes).  The public key is
@@ -243,6 +274,21 @@ class Verifier:
         if not np.array_equal(valid, reason == _lib.REASON_OK):
             raise _lib.DrandGPUError(_lib.DGPU_EINVAL, "verdict bitmap and reasons disagree")
         return reason, ok.astype(bool), rounds
+
+    def check_rows(self, pubkey, rows, first, count, mode=_lib.MODE_PER_ROUND, rlc_seed=None, sig_stride=96,
+                   prev_stride=96, reasons=False):
+        """One window of the bulk chain check in one call (dgpu_check_rows):
+        `rows` is an ingest.Rows (keys, off, len, buf), the loop visits rounds
+        first .. first + count - 1.  The rows are decoded and verified on the
+        GPU and the faulty list is built there.  Returns (faulty_pos,
+        faulty_val, left_rows): the positions (round - first) and values of
+        the faulty entries in ascending position, and the indices of the rows
+        that are not canonical -- the caller's to decode with
+        sync.beacon_unmarshal and merge.  reasons=True appends the
+        DGPU_REASON_* code per row."""
+        lib = self.ctx.lib
+        return check_rows_with(lambda *a: lib.dgpu_check_rows(self.ctx.handle, self._code, *a), lib, pubkey, rows,
+                               first, count, mode, rlc_seed, sig_stride, prev_stride, reasons)
 
     def verify_segment(self, first_round, sigs, prev_sig, pubkey, mode=_lib.MODE_PER_ROUND, rlc_seed=None,
                        randomness=True, sig_len=None):

@@ -31,6 +31,7 @@
 #include "rlc_msm.cuh"
 #include "recover_g1.cuh"
 #include "ingest_row.cuh"
+#include "check_rows.cuh"
 #include "scratch_layouts.h"
 
 using namespace dgpu;
@@ -364,6 +365,8 @@ struct dgpu_ctx {
   // staging for host-pointer entry points
   DevBuf in_rounds, in_sigs, in_sig_len, in_prev, in_prev_len, in_msgs, in_msg_len, out_bits, out_reason, out_rand, misc;
   DevBuf in_rows, in_row_ok;    // dgpu_verify_rows: the packed stored rows with their positions and lengths; the decoder's ok flags
+  DevBuf in_keys;               // dgpu_check_rows: the rows' keys, staged beside the rows
+  DevBuf chk, chk_out;          // the faulty list's scratch (check_rows_layout) and dgpu_check_rows' device lists
   DevBuf in_halo, in_halo_len;  // a staged shard's halo (dgpu_verify_segment_multi): one record of the stride, its length
   // optional per-stage HIP-event timing of the last verify call (event pool;
   // durations are summed per stage name: chunked stages repeat)
@@ -1620,6 +1623,10 @@ struct rows_src {
   uint8_t *d_sigs, *d_prev, *d_ok;
   uint32_t *d_sig_len, *d_prev_len;
   size_t sig_stride, prev_stride;
+  // dgpu_check_rows: the rows' keys (host), staged slice by slice behind the
+  // slice's rows into d_keys; nullptr for dgpu_verify_rows
+  const uint64_t* keys;
+  uint64_t* d_keys;
 };
 
 // The ring bytes of rows [a, b) of a rows_src: the packed rows, then (on an
@@ -1748,8 +1755,13 @@ struct host_stager {
       // Stored rows: the slice's rows and their decode, then both events -- the
       // records of slice k exist once its k_ingest_rows launches have run.
       // Staged bytes: the staged rows and 12 bytes (position, length) per row.
+      // dgpu_check_rows: the slice's keys behind them, 8 bytes per row.
       if ((r = ring_rows_locked(c, *rows, a, b))) return r;
       bytes += (size_t)(rows->pos[b] - rows->pos[a]) + n * 12;
+      if (rows->keys) {
+        if ((r = ring_copy_locked(c, rows->d_keys + a, rows->keys + a, n * 8))) return r;
+        bytes += n * 8;
+      }
       HIP_TRY(hipEventRecord(ev_msg[k], c->stream_copy));
       {
         std::lock_guard<std::mutex> lk(mu);
@@ -1882,6 +1894,25 @@ int stage_prepare_locked(dgpu_ctx* c, verify_args& a) {
   return DGPU_OK;
 }
 
+// The device side of a rows_src behind stage_prepare_locked: the packed rows
+// and the record arrays the decoder writes (the context's in_* buffers).
+int rows_prepare_locked(dgpu_ctx* c, const verify_args& a, rows_src* rows) {
+  int rc;
+  // the decoder writes every row's previous signature, whatever the scheme reads
+  if ((rc = c->in_prev.ensure(a.n * rows->prev_stride + 1)) || (rc = c->in_prev_len.ensure(a.n * 4)) ||
+      (rc = c->in_row_ok.ensure(a.n)) || (rc = carve(c->in_rows, &rows->dev, (size_t)rows->pos[a.n], a.n)))
+    return rc;
+  if (rows->keys && (rc = c->in_keys.ensure(a.n * 8))) return rc;
+  rows->d_rounds = (uint64_t*)c->in_rounds.p;
+  rows->d_sigs = (uint8_t*)c->in_sigs.p;
+  rows->d_sig_len = (uint32_t*)c->in_sig_len.p;
+  rows->d_prev = (uint8_t*)c->in_prev.p;
+  rows->d_prev_len = (uint32_t*)c->in_prev_len.p;
+  rows->d_ok = (uint8_t*)c->in_row_ok.p;
+  rows->d_keys = rows->keys ? (uint64_t*)c->in_keys.p : nullptr;
+  return DGPU_OK;
+}
+
 // verify_status_locked over host records, overlapping their staging with the
 // verification: the slices are the per-round G2 path's lane slices
 // (lane_slice_len), one slice for every other pipeline.
@@ -1894,16 +1925,7 @@ int verify_status_host_locked(dgpu_ctx* c, const key_entry* key, verify_args& a,
   int rc;
   if ((rc = stage_prepare_locked(c, a))) return rc;
   if (rows) {
-    // the decoder writes every row's previous signature, whatever the scheme reads
-    if ((rc = c->in_prev.ensure(a.n * rows->prev_stride + 1)) || (rc = c->in_prev_len.ensure(a.n * 4)) ||
-        (rc = c->in_row_ok.ensure(a.n)) || (rc = carve(c->in_rows, &rows->dev, (size_t)rows->pos[a.n], a.n)))
-      return rc;
-    rows->d_rounds = (uint64_t*)c->in_rounds.p;
-    rows->d_sigs = (uint8_t*)c->in_sigs.p;
-    rows->d_sig_len = (uint32_t*)c->in_sig_len.p;
-    rows->d_prev = (uint8_t*)c->in_prev.p;
-    rows->d_prev_len = (uint32_t*)c->in_prev_len.p;
-    rows->d_ok = (uint8_t*)c->in_row_ok.p;
+    if ((rc = rows_prepare_locked(c, a, rows))) return rc;
     stg.rows = rows;
   }
   // the copy stream (device buffers, ring slots) after the previous call's work
@@ -1923,10 +1945,15 @@ int verify_status_host_locked(dgpu_ctx* c, const key_entry* key, verify_args& a,
 
 // Every record of a host call on the device before anything else runs on s
 // (the RLC root's points need the whole shard): one slice through the ring.
-int stage_all_host_locked(dgpu_ctx* c, verify_args& a, hipStream_t s) {
+// rows: as verify_status_host_locked.
+int stage_all_host_locked(dgpu_ctx* c, verify_args& a, hipStream_t s, rows_src* rows = nullptr) {
   host_stager stg(c, a);
   int rc;
   if ((rc = stage_prepare_locked(c, a))) return rc;
+  if (rows) {
+    if ((rc = rows_prepare_locked(c, a, rows))) return rc;
+    stg.rows = rows;
+  }
   HIP_TRY(hipStreamWaitEvent(c->stream_copy, c->done, 0));
   stg.lo = {0, a.n};
   if ((rc = stg.make_events(1))) return rc;
@@ -1982,23 +2009,16 @@ int verify_host_pageable_locked(dgpu_ctx* c, const key_entry* key, verify_args a
   return DGPU_OK;
 }
 
-// dgpu_verify_rows: verify_host_locked with the records decoded on the device
-// from the caller's stored rows; the decoder's ok flags and rounds come back
-// with the verdicts.
-int verify_rows_locked(dgpu_ctx* c, const key_entry* key, verify_args a, const uint8_t* base, const uint64_t* row_off,
-                       const uint32_t* row_len, size_t prev_stride, uint64_t* rounds_out, uint8_t* row_ok,
-                       uint8_t* verdict_bits, uint8_t* reason) {
-  verify_args a0 = a;  // scheme, mode and key before anything else (n = 0 checks no buffers)
-  a0.n = 0;
-  int rc = check_args(c, key, a0);
-  if (rc || a.n == 0) return rc;
-  if (!base || !row_off || !row_len || !row_ok || !verdict_bits) return set_err(DGPU_EINVAL, "null row or output buffer");
+// The host side of a rows_src over a.n > 0 rows: the argument checks of the
+// row entry points, the staged lengths and the packed positions.
+int rows_src_init(rows_src& R, const verify_args& a, const uint8_t* base, const uint64_t* row_off,
+                  const uint32_t* row_len, size_t prev_stride, const uint64_t* keys) {
+  if (!base || !row_off || !row_len) return set_err(DGPU_EINVAL, "null row or output buffer");
   if (a.sig_stride < (sig_on_g1(a.scheme) ? 48u : 96u)) return set_err(DGPU_EINVAL, "bad signature stride");
   const size_t max_len = ingest_row_max_len(a.sig_stride, prev_stride);
   if (a.sig_stride > STAGE_SLOT_BYTES || prev_stride > STAGE_SLOT_BYTES || max_len + 16 > STAGE_SLOT_BYTES)
     return set_err(DGPU_EINVAL, "strides too large for the staging ring");
-  rows_src R{};
-  R.base = base, R.off = row_off, R.len = row_len;
+  R.base = base, R.off = row_off, R.len = row_len, R.keys = keys;
   R.sig_stride = a.sig_stride, R.prev_stride = prev_stride;
   R.slen.resize(a.n);
   R.pos.resize(a.n + 1);
@@ -2009,6 +2029,22 @@ int verify_rows_locked(dgpu_ctx* c, const key_entry* key, verify_args a, const u
     at += R.slen[i];
   }
   R.pos[a.n] = at;
+  return DGPU_OK;
+}
+
+// dgpu_verify_rows: verify_host_locked with the records decoded on the device
+// from the caller's stored rows; the decoder's ok flags and rounds come back
+// with the verdicts.
+int verify_rows_locked(dgpu_ctx* c, const key_entry* key, verify_args a, const uint8_t* base, const uint64_t* row_off,
+                       const uint32_t* row_len, size_t prev_stride, uint64_t* rounds_out, uint8_t* row_ok,
+                       uint8_t* verdict_bits, uint8_t* reason) {
+  verify_args a0 = a;  // scheme, mode and key before anything else (n = 0 checks no buffers)
+  a0.n = 0;
+  int rc = check_args(c, key, a0);
+  if (rc || a.n == 0) return rc;
+  if (!row_ok || !verdict_bits) return set_err(DGPU_EINVAL, "null row or output buffer");
+  rows_src R{};
+  if ((rc = rows_src_init(R, a, base, row_off, row_len, prev_stride, nullptr))) return rc;
   hipStream_t s = c->stream;
   stream_order ord(c, s);
   if ((rc = c->out_bits.ensure((a.n + 7) / 8)) || (rc = c->out_reason.ensure(a.n))) return rc;
@@ -2021,6 +2057,133 @@ int verify_rows_locked(dgpu_ctx* c, const key_entry* key, verify_args a, const u
   if (rounds_out) HIP_TRY(hipMemcpyAsync(rounds_out, R.d_rounds, a.n * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return DGPU_OK;
+}
+
+// ---------------------------------------------------------------- the faulty list (check_rows.cuh)
+// The arguments every form of the faulty-list stage shares: first + count
+// must not wrap, and the map's and the grid's index widths bound n and count.
+int check_range_args(uint64_t first, size_t count, size_t n) {
+  if ((uint64_t)count > UINT64_MAX - first) return set_err(DGPU_EINVAL, "first + count overflows 64 bits");
+  if (n >= (size_t)CHECK_NO_ROW) return set_err(DGPU_EINVAL, "too many rows");
+  if (count > (size_t)0x7fffffff * CHECK_BLOCK) return set_err(DGPU_EINVAL, "too many visited rounds");
+  return DGPU_OK;
+}
+
+// dgpu_faulty_rounds_device's kernels on s (count > 0; arguments checked).
+int faulty_rounds_locked(dgpu_ctx* c, uint64_t first, size_t count, size_t n, const uint64_t* d_keys,
+                         const uint8_t* d_row_ok, const uint64_t* d_rounds, const uint8_t* d_status,
+                         uint64_t* d_faulty_pos, uint64_t* d_faulty_val, size_t faulty_cap, uint64_t* d_left_rows,
+                         size_t left_cap, uint64_t* d_counts, hipStream_t s) {
+  check_rows_layout L;
+  int rc = carve(c->chk, &L, count);
+  if (rc) return rc;
+  const size_t nblk = check_blocks(count);
+  HIP_TRY(hipMemsetAsync(L.map, 0xFF, count * 4, s));  // CHECK_NO_ROW everywhere
+  if (n)
+    hipLaunchKernelGGL(k_check_map, dim3(grid_for(n, CHECK_BLOCK)), dim3(CHECK_BLOCK), 0, s, first, count, n, d_keys,
+                       L.map);
+  hipLaunchKernelGGL(k_check_classify, dim3((unsigned)nblk), dim3(CHECK_BLOCK), 0, s, first, count, n,
+                     (const uint32_t*)L.map, d_row_ok, d_rounds, d_status, L.flags, L.blk_faulty, L.blk_left);
+  hipLaunchKernelGGL(k_check_scan, dim3(1), dim3(CHECK_BLOCK), 0, s, nblk, L.blk_faulty, L.blk_left, d_counts);
+  hipLaunchKernelGGL(k_check_scatter, dim3((unsigned)nblk), dim3(CHECK_BLOCK), 0, s, first, count, n,
+                     (const uint32_t*)L.map, d_row_ok, d_rounds, d_status, (const uint8_t*)L.flags,
+                     (const uint64_t*)L.blk_faulty, (const uint64_t*)L.blk_left, d_faulty_pos, d_faulty_val, faulty_cap,
+                     d_left_rows, left_cap);
+  HIP_TRY(hipGetLastError());
+  return DGPU_OK;
+}
+
+// The lists of one context on the host: the totals, and the entries below the caps.
+struct check_lists {
+  uint64_t n_faulty = 0, n_left = 0;
+  std::vector<uint64_t> pos, val, left;
+};
+
+// The faulty list of positions [first, first + count) over the n rows the
+// context has just verified (keys at d_keys; the decoder's ok flags and rounds;
+// the final statuses), behind that work on s; the totals come back first, then
+// the entries there are, so the bytes copied follow the faults, not n.
+// Synchronises s.
+int check_lists_locked(dgpu_ctx* c, uint64_t first, size_t count, size_t n, const uint64_t* d_keys,
+                       size_t faulty_cap, size_t left_cap, check_lists& out, hipStream_t s) {
+  out = check_lists{};
+  if (count == 0) return DGPU_OK;
+  faulty_cap = std::min(faulty_cap, count);  // (no more entries than positions, or rows)
+  left_cap = std::min(left_cap, n);
+  check_lists_layout D;
+  int rc = carve(c->chk_out, &D, faulty_cap, left_cap);
+  if (rc) return rc;
+  if ((rc = faulty_rounds_locked(c, first, count, n, d_keys, (const uint8_t*)c->in_row_ok.p,
+                                 (const uint64_t*)c->in_rounds.p, (const uint8_t*)c->status.p, D.faulty_pos,
+                                 D.faulty_val, faulty_cap, D.left_rows, left_cap, D.counts, s)))
+    return rc;
+  uint64_t counts[2];
+  HIP_TRY(hipMemcpyAsync(counts, D.counts, sizeof counts, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  out.n_faulty = counts[0], out.n_left = counts[1];
+  const size_t nf = (size_t)std::min<uint64_t>(counts[0], faulty_cap);
+  const size_t nl = (size_t)std::min<uint64_t>(counts[1], left_cap);
+  out.pos.resize(nf), out.val.resize(nf), out.left.resize(nl);
+  if (nf) {
+    HIP_TRY(hipMemcpyAsync(out.pos.data(), D.faulty_pos, nf * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out.val.data(), D.faulty_val, nf * 8, hipMemcpyDeviceToHost, s));
+  }
+  if (nl) HIP_TRY(hipMemcpyAsync(out.left.data(), D.left_rows, nl * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return DGPU_OK;
+}
+
+// The host-side argument checks of dgpu_check_rows and its _multi form, before
+// any device work.
+int check_rows_args(size_t n, const uint8_t* base, const uint64_t* row_off, const uint32_t* row_len,
+                    const uint64_t* keys, uint64_t first, size_t count, const uint64_t* faulty_pos,
+                    const uint64_t* faulty_val, size_t faulty_cap, const uint64_t* n_faulty, const uint64_t* left_rows,
+                    size_t left_cap, const uint64_t* n_left) {
+  int rc = check_range_args(first, count, n);
+  if (rc) return rc;
+  if (!n_faulty || !n_left) return set_err(DGPU_EINVAL, "null count output");
+  if (n && (!base || !row_off || !row_len || !keys)) return set_err(DGPU_EINVAL, "null row buffer");
+  if ((faulty_cap && (!faulty_pos || !faulty_val)) || (left_cap && !left_rows))
+    return set_err(DGPU_EINVAL, "null list buffer");
+  for (size_t i = 0; i < n; ++i) {
+    if (i && keys[i] <= keys[i - 1]) return set_err(DGPU_EINVAL, "keys[%zu] is not above keys[%zu]", i, i - 1);
+    uint64_t j;
+    if (!check_rows_slot(first, count, keys[i], &j))
+      return set_err(DGPU_EINVAL, "keys[%zu] lies outside [first, first + count)", i);
+  }
+  return DGPU_OK;
+}
+
+// dgpu_check_rows on one context (arguments checked by check_rows_args).
+int check_rows_locked(dgpu_ctx* c, const key_entry* key, verify_args a, const uint8_t* base, const uint64_t* row_off,
+                      const uint32_t* row_len, const uint64_t* keys, size_t prev_stride, uint64_t first, size_t count,
+                      size_t faulty_cap, size_t left_cap, check_lists& out, uint8_t* reason) {
+  verify_args a0 = a;  // scheme, mode and key (n = 0 checks no buffers)
+  a0.n = 0;
+  int rc = check_args(c, key, a0);
+  if (rc) return rc;
+  rows_src R{};
+  if (a.n && (rc = rows_src_init(R, a, base, row_off, row_len, prev_stride, keys))) return rc;
+  hipStream_t s = c->stream;
+  stream_order ord(c, s);
+  if (a.n && (rc = verify_status_host_locked(c, key, a, s, &R))) return rc;
+  if (a.n) mark(c, s);
+  if ((rc = check_lists_locked(c, first, count, a.n, R.d_keys, faulty_cap, left_cap, out, s))) return rc;
+  if (reason && a.n) {
+    HIP_TRY(hipMemcpyAsync(reason, c->status.p, a.n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  return DGPU_OK;
+}
+
+// The lists into the caller's buffers (entries below the caps; the totals always).
+void check_lists_store(const check_lists& L, uint64_t* faulty_pos, uint64_t* faulty_val, size_t faulty_cap,
+                       uint64_t* n_faulty, uint64_t* left_rows, size_t left_cap, uint64_t* n_left) {
+  const size_t nf = std::min(L.pos.size(), faulty_cap), nl = std::min(L.left.size(), left_cap);
+  if (nf) memcpy(faulty_pos, L.pos.data(), nf * 8), memcpy(faulty_val, L.val.data(), nf * 8);
+  if (nl) memcpy(left_rows, L.left.data(), nl * 8);
+  *n_faulty = L.n_faulty;
+  *n_left = L.n_left;
 }
 
 size_t size_engine_chunk(int lanes) {
@@ -2295,6 +2458,48 @@ int dgpu_verify_rows(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t pk_len, 
   const verify_args a{scheme, n, beacon_src(nullptr, nullptr, prev_stride, nullptr, scheme == DGPU_SCHEME_CHAINED),
                       nullptr, sig_stride, nullptr, mode, rlc_seed};
   return verify_rows_locked(c, k, a, base, row_off, row_len, prev_stride, rounds_out, row_ok, verdict_bits, reason);
+}
+
+int dgpu_faulty_rounds_device(dgpu_ctx* c, uint64_t first, size_t count, size_t n, const uint64_t* d_keys,
+                              const uint8_t* d_row_ok, const uint64_t* d_rounds, const uint8_t* d_reason,
+                              uint64_t* d_faulty_pos, uint64_t* d_faulty_val, size_t faulty_cap, uint64_t* d_left_rows,
+                              size_t left_cap, uint64_t* d_counts, void* stream) {
+  if (!c) return set_err(DGPU_EINVAL, "null ctx");
+  if (count == 0) return DGPU_OK;
+  int rc = check_range_args(first, count, n);
+  if (rc) return rc;
+  if (!d_counts || (n && (!d_keys || !d_row_ok || !d_rounds || !d_reason)) ||
+      (faulty_cap && (!d_faulty_pos || !d_faulty_val)) || (left_cap && !d_left_rows))
+    return set_err(DGPU_EINVAL, "null row, list or count buffer");
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = caller_stream(stream);
+  stream_order ord(c, s);
+  return faulty_rounds_locked(c, first, count, n, d_keys, d_row_ok, d_rounds, d_reason, d_faulty_pos, d_faulty_val,
+                              faulty_cap, d_left_rows, left_cap, d_counts, s);
+}
+
+int dgpu_check_rows(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t pk_len, size_t n, const uint8_t* base,
+                    const uint64_t* row_off, const uint32_t* row_len, const uint64_t* keys, size_t sig_stride,
+                    size_t prev_stride, int mode, uint64_t rlc_seed, uint64_t first, size_t count,
+                    uint64_t* faulty_pos, uint64_t* faulty_val, size_t faulty_cap, uint64_t* n_faulty,
+                    uint64_t* left_rows, size_t left_cap, uint64_t* n_left, uint8_t* reason) {
+  if (!c) return set_err(DGPU_EINVAL, "null ctx");
+  int rc = check_rows_args(n, base, row_off, row_len, keys, first, count, faulty_pos, faulty_val, faulty_cap, n_faulty,
+                           left_rows, left_cap, n_left);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipSetDevice(c->device));
+  key_entry* k = nullptr;
+  if ((rc = get_key_locked(c, scheme, pk, pk_len, &k))) return rc;
+  const verify_args a{scheme, n, beacon_src(nullptr, nullptr, prev_stride, nullptr, scheme == DGPU_SCHEME_CHAINED),
+                      nullptr, sig_stride, nullptr, mode, rlc_seed};
+  check_lists L;
+  if ((rc = check_rows_locked(c, k, a, base, row_off, row_len, keys, prev_stride, first, count, faulty_cap, left_cap, L,
+                              reason)))
+    return rc;
+  check_lists_store(L, faulty_pos, faulty_val, faulty_cap, n_faulty, left_rows, left_cap, n_left);
+  return DGPU_OK;
 }
 
 // The arguments of the two segment entry points that no other call has.

@@ -248,18 +248,49 @@ int shard_results_locked(dgpu_multi* m, int k, const verify_args& a, uint8_t* ra
   return DGPU_OK;
 }
 
+// The stored-row form of a multi call (dgpu_check_rows_multi): the caller's
+// rows and keys, each device's rows_src over its shard, the positions
+// [p0[k], p0[k] + pcount[k]) of the visited range device k owns, and the lists
+// each device returns (positions relative to p0[k], rows to the shard).
+struct multi_rows {
+  const uint8_t* base;
+  const uint64_t* off;
+  const uint32_t* len;
+  const uint64_t* keys;
+  size_t prev_stride;
+  uint64_t first;
+  size_t faulty_cap, left_cap;
+  std::vector<rows_src> R;
+  std::vector<uint64_t> p0;
+  std::vector<size_t> pcount;
+  std::vector<check_lists> lists;
+};
+
+// The faulty list of the positions device k owns, once its shard's statuses
+// are final (synchronises the device's stream).
+int shard_lists_locked(dgpu_multi* m, int k, const verify_args& a, multi_rows& mr) {
+  dgpu_ctx* c = m->ctx[k];
+  return check_lists_locked(c, mr.first + mr.p0[k], mr.pcount[k], a.n, mr.R[k].d_keys, mr.faulty_cap, mr.left_cap,
+                            mr.lists[k], c->stream);
+}
+
 // The multi-device verify call over host records (dgpu_verify_multi,
 // dgpu_verify_segment_multi): src_of(k, lo, hi) is the message source of
 // shard k = items [lo, hi) of the caller's arrays; everything else -- the
 // shards' signature arrays, per-device seeds, staging through each context's
 // ring, roots, gathers -- is the same for every source.
+// mr (dgpu_check_rows_multi): the records of every shard are decoded on its
+// device from the caller's stored rows (the row form of both staging
+// functions), the faulty-list stage runs on each device once its shard's
+// statuses are final, and no verdict bitmap is gathered (verdict_bits is NULL;
+// the reasons only when the caller asks for them).
 template <class SrcOf>
 int multi_verify(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_len, size_t n, const uint8_t* sigs,
                  size_t sig_stride, const uint32_t* sig_len, int mode, uint64_t rlc_seed, SrcOf&& src_of,
-                 uint8_t* verdict_bits, uint8_t* reason, uint8_t* rand32) {
+                 uint8_t* verdict_bits, uint8_t* reason, uint8_t* rand32, multi_rows* mr = nullptr) {
   if (!m) return set_err(DGPU_EINVAL, "null handle");
   if (n == 0) return DGPU_OK;
-  if (!verdict_bits) return set_err(DGPU_EINVAL, "null verdict buffer");
+  if (!verdict_bits && !mr) return set_err(DGPU_EINVAL, "null verdict buffer");
   std::lock_guard<std::mutex> mlk(m->mu);
   std::vector<std::unique_lock<std::mutex>> locks;
   for (dgpu_ctx* c : m->ctx) locks.emplace_back(c->mu);
@@ -277,10 +308,19 @@ int multi_verify(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_len, si
     size_t hi;
     dgpu_shard_range(n, D, k, &lo[k], &hi);
     // RLC coefficients: an independent seed per device (positions restart at 0)
-    args[k] = verify_args{scheme, hi - lo[k], src_of(k, lo[k], hi), sigs + lo[k] * sig_stride, sig_stride,
-                          sig_len + lo[k], mode,
+    args[k] = verify_args{scheme, hi - lo[k], src_of(k, lo[k], hi), sigs ? sigs + lo[k] * sig_stride : nullptr,
+                          sig_stride, sig_len ? sig_len + lo[k] : nullptr, mode,
                           D > 1 ? splitmix_host(rlc_seed ^ (0x5EEDull * (uint64_t)(k + 1))) : rlc_seed};
-    if ((rc = check_args(c, keys[k], args[k]))) return rc;
+    if (mr) {  // (the record arrays are the context's buffers: scheme, mode and key alone, then the rows)
+      verify_args a0 = args[k];
+      a0.n = 0;
+      if ((rc = check_args(c, keys[k], a0)) ||
+          (args[k].n && (rc = rows_src_init(mr->R[k], args[k], mr->base, mr->off + lo[k], mr->len + lo[k],
+                                            mr->prev_stride, mr->keys + lo[k]))))
+        return rc;
+    } else if ((rc = check_args(c, keys[k], args[k]))) {
+      return rc;
+    }
     multi_bufs& b = m->buf[k];
     // (the roots: sized for either group's)
     if ((rc = b.bits.ensure(per / 8)) || (rc = b.reasons.ensure(per)) || (rc = b.all_bits.ensure(D * per / 8)) ||
@@ -307,13 +347,15 @@ int multi_verify(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_len, si
     c->ev_overflow = false;
     if (rlc) {  // the shard's points and its root by bucket MSM (the leaves wait for a failing root)
       c->rlc_pending = false;  // overwrites the points a pending per-rank root (dgpu_rlc_root_device) kept
-      if ((r = stage_all_host_locked(c, a, s)) || (r = rlc_points_locked(c, a, s))) return r;
+      if ((r = stage_all_host_locked(c, a, s, mr ? &mr->R[k] : nullptr)) || (r = rlc_points_locked(c, a, s))) return r;
       return rlc_root_msm_locked(c, a, s, c->msm_root);
     }
     // the shard's records through the context's pinned ring, slice by slice
     // beside the verification (verify_status_host_locked)
-    if ((r = verify_status_host_locked(c, keys[k], a, s))) return r;
-    return shard_results_locked(m, k, a, rand32 ? rand32 + 32 * lo[k] : nullptr);
+    if ((r = verify_status_host_locked(c, keys[k], a, s, mr ? &mr->R[k] : nullptr)) ||
+        (r = shard_results_locked(m, k, a, rand32 ? rand32 + 32 * lo[k] : nullptr)))
+      return r;
+    return mr ? shard_lists_locked(m, k, a, *mr) : DGPU_OK;
   });
   if (rc) return rc;
   if (rlc) {
@@ -367,7 +409,8 @@ int multi_verify(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_len, si
       if (!all_ok && ((r = carve(c->msm_root, &shard, jw)) ||
                       (r = rlc_resolve_locked(c, keys[k], args[k], c->stream, shard, D == 1))))
         return r;
-      return shard_results_locked(m, k, args[k], rand32 ? rand32 + 32 * lo[k] : nullptr);
+      if ((r = shard_results_locked(m, k, args[k], rand32 ? rand32 + 32 * lo[k] : nullptr))) return r;
+      return mr ? shard_lists_locked(m, k, args[k], *mr) : DGPU_OK;
     });
     if (rc) return rc;
   }
@@ -388,7 +431,7 @@ int multi_verify(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_len, si
       rsrc[k] = m->buf[k].reasons.p;
       rdst[k] = m->buf[k].all_reasons.p;
     }
-    if ((rc = multi_all_gather(m, src, dst, per / 8))) return rc;
+    if (verdict_bits && (rc = multi_all_gather(m, src, dst, per / 8))) return rc;
     if (reason && (rc = multi_all_gather(m, rsrc, rdst, per))) return rc;
   }
   for (int k = 0; k < D; ++k) {
@@ -397,7 +440,8 @@ int multi_verify(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_len, si
   }
   dgpu_ctx* c0 = m->ctx[0];
   HIP_TRY(hipSetDevice(c0->device));
-  HIP_TRY(hipMemcpyAsync(verdict_bits, m->buf[0].all_bits.p, (n + 7) / 8, hipMemcpyDeviceToHost, c0->stream));
+  if (verdict_bits)
+    HIP_TRY(hipMemcpyAsync(verdict_bits, m->buf[0].all_bits.p, (n + 7) / 8, hipMemcpyDeviceToHost, c0->stream));
   if (reason) HIP_TRY(hipMemcpyAsync(reason, m->buf[0].all_reasons.p, n, hipMemcpyDeviceToHost, c0->stream));
   for (int k = 0; k < D; ++k) {
     HIP_TRY(hipSetDevice(m->ctx[k]->device));
@@ -446,6 +490,55 @@ int dgpu_verify_segment_multi(dgpu_multi* m, int scheme, const uint8_t* pk, size
         return halo_src(first_round + lo, s_lo, sig_stride, sig_len + lo, s_lo - sig_stride, sig_len + lo - 1, chained);
       },
       verdict_bits, reason, randomness32);
+}
+
+// dgpu_check_rows over the node.  The rows shard like every batch here; the
+// visited positions follow the rows: shard 0 owns them from 0, a later
+// non-empty shard k from its first key, the last non-empty shard up to count
+// -- so a run of missing rounds in front of a shard's first key belongs to the
+// shard before it -- and each device builds the list of its own positions.
+// The host concatenates the lists in shard order; no collective carries them.
+int dgpu_check_rows_multi(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_len, size_t n, const uint8_t* base,
+                          const uint64_t* row_off, const uint32_t* row_len, const uint64_t* keys, size_t sig_stride,
+                          size_t prev_stride, int mode, uint64_t rlc_seed, uint64_t first, size_t count,
+                          uint64_t* faulty_pos, uint64_t* faulty_val, size_t faulty_cap, uint64_t* n_faulty,
+                          uint64_t* left_rows, size_t left_cap, uint64_t* n_left, uint8_t* reason) {
+  if (!m) return set_err(DGPU_EINVAL, "null handle");
+  if (n == 0) {  // shard 0 owns every position
+    std::lock_guard<std::mutex> mlk(m->mu);
+    return dgpu_check_rows(m->ctx[0], scheme, pk, pk_len, 0, base, row_off, row_len, keys, sig_stride, prev_stride, mode,
+                           rlc_seed, first, count, faulty_pos, faulty_val, faulty_cap, n_faulty, left_rows, left_cap,
+                           n_left, reason);
+  }
+  int rc = check_rows_args(n, base, row_off, row_len, keys, first, count, faulty_pos, faulty_val, faulty_cap, n_faulty,
+                           left_rows, left_cap, n_left);
+  if (rc) return rc;
+  const int D = m->ndev;
+  multi_rows mr{base, row_off, row_len, keys, prev_stride, first, faulty_cap, left_cap, {}, {}, {}, {}};
+  mr.R.resize(D), mr.p0.assign(D, 0), mr.pcount.assign(D, 0), mr.lists.resize(D);
+  std::vector<size_t> lo(D), hi(D);
+  for (int k = 0; k < D; ++k) dgpu_shard_range(n, D, k, &lo[k], &hi[k]);
+  for (int k = 0; k < D; ++k) {
+    if (lo[k] == hi[k]) continue;  // (the non-empty shards are the first ones)
+    mr.p0[k] = k ? keys[lo[k]] - first : 0;
+    const bool last = k + 1 == D || lo[k + 1] == hi[k + 1];
+    mr.pcount[k] = (size_t)((last ? (uint64_t)count : keys[lo[k + 1]] - first) - mr.p0[k]);
+  }
+  const bool chained = scheme == DGPU_SCHEME_CHAINED;
+  rc = multi_verify(
+      m, scheme, pk, pk_len, n, nullptr, sig_stride, nullptr, mode, rlc_seed,
+      [&](int, size_t, size_t) { return beacon_src(nullptr, nullptr, prev_stride, nullptr, chained); }, nullptr, reason,
+      nullptr, &mr);
+  if (rc) return rc;
+  check_lists all;
+  for (int k = 0; k < D; ++k) {
+    const check_lists& L = mr.lists[k];
+    all.n_faulty += L.n_faulty, all.n_left += L.n_left;
+    for (size_t i = 0; i < L.pos.size(); ++i) all.pos.push_back(L.pos[i] + mr.p0[k]), all.val.push_back(L.val[i]);
+    for (uint64_t r : L.left) all.left.push_back(r + lo[k]);
+  }
+  check_lists_store(all, faulty_pos, faulty_val, faulty_cap, n_faulty, left_rows, left_cap, n_left);
+  return DGPU_OK;
 }
 
 }  // extern "C"

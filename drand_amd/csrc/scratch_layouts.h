@@ -2,8 +2,10 @@
 // (scratch_carve.h: one fill() per buffer gives its size and its pointers).
 // Grouped by the code that owns the buffer; capi.hip's carve() applies them.
 // Host code; it takes the kernels' own sizes and index functions from their
-// headers, which a host-only program includes under DG_NO_KERNELS
-// (tests/scratch_layout_check.hip checks every layout here).
+// headers, which a host-only program includes under DG_NO_KERNELS.
+// Which program checks which layout: tests/scratch_layout_check.hip every
+// layout here except those of the row ingest group; tests/check_rows_check.cpp
+// that group (ingest_rows_layout, check_rows_layout, check_lists_layout).
 //
 // Alignment: a region is aligned to the widest access its kernels make --
 // 16 bytes for k_h2c_finish's park quads, 8 for the wave-blocked planes
@@ -14,6 +16,7 @@
 #include "recover.cuh"
 #include "rlc_msm.cuh"
 #include "scratch_carve.h"
+#include "check_rows.cuh"  // (behind the headers that bring the HIP runtime's function qualifiers)
 
 namespace dgpu {
 
@@ -239,6 +242,31 @@ struct ingest_rows_layout {
     bytes = c.take<uint8_t>(packed_bytes, 16);
     off = c.take<uint64_t>(n);
     len = c.take<uint32_t>(n);
+  }
+};
+
+// chk (dgpu_faulty_rounds_device): the scratch of the faulty list over `count`
+// visited positions -- the two block-count arrays k_check_scan turns into
+// block offsets, the position -> row map, the outcome flags.
+struct check_rows_layout {
+  uint64_t *blk_faulty, *blk_left;  // [check_blocks(count)]
+  uint32_t* map;                    // [count], CHECK_NO_ROW where no row has the key
+  uint8_t* flags;                   // [count], CHECK_*
+  void fill(carver& c, size_t count) {
+    blk_faulty = c.take<uint64_t>(check_blocks(count));
+    blk_left = c.take<uint64_t>(check_blocks(count));
+    map = c.take<uint32_t>(count);
+    flags = c.take<uint8_t>(count);
+  }
+};
+// chk_out (dgpu_check_rows): the two totals, then the lists at their caps
+struct check_lists_layout {
+  uint64_t *counts, *faulty_pos, *faulty_val, *left_rows;
+  void fill(carver& c, size_t faulty_cap, size_t left_cap) {
+    counts = c.take<uint64_t>(2);
+    faulty_pos = c.take<uint64_t>(faulty_cap);
+    faulty_val = c.take<uint64_t>(faulty_cap);
+    left_rows = c.take<uint64_t>(left_cap);
   }
 };
 

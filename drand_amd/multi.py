@@ -10,7 +10,7 @@ drand_amd/dist.py; both shard with the same contiguous rule."""
 import numpy as np
 
 from . import _lib
-from .chain import pack_beacons, rlc_seed_for, verify_segment_with
+from .chain import Verifier, check_rows_with, pack_beacons, rlc_seed_for, verify_segment_with
 from .scheme import Scheme, scheme_code
 from .threshold import group_scheme_code, pack_partials, sig_bytes, unpack_recovered
 
@@ -59,6 +59,57 @@ class MultiVerifier:
         return verify_segment_with(lambda *a: lib.dgpu_verify_segment_multi(self.mctx.handle, self._code, *a), lib,
                                    self._code, first_round, sigs, prev_sig, pubkey, mode, rlc_seed, randomness,
                                    sig_len)
+
+
+    def _shard_verifiers(self):
+        """One chain.Verifier per device of the handle, over the handle's own
+        contexts (dgpu_multi_context; the handle keeps owning them)."""
+        if getattr(self, "_shards", None) is None:
+            import ctypes
+            self._shards = []
+            for k in range(len(self.mctx.devices)):
+                h = ctypes.c_void_p()
+                _lib.check(self.mctx.lib.dgpu_multi_context(self.mctx.handle, k, ctypes.byref(h)), self.mctx.lib)
+                v = Verifier.__new__(Verifier)
+                v.scheme, v._code, v.ctx = self.scheme, self._code, _BorrowedContext(self.mctx.lib, h)
+                self._shards.append(v)
+        return self._shards
+
+    def verify_rows(self, pubkey, buf, off, ln, mode=_lib.MODE_PER_ROUND, rlc_seed=None, sig_stride=96,
+                    prev_stride=96):
+        """chain.Verifier.verify_rows over the handle's GPUs: the same
+        arguments and the same (reasons, row_ok, rounds) result.  The rows
+        shard on the host by dgpu_shard_range and each shard is one
+        dgpu_verify_rows call on its device's context, side by side (RLC
+        mode: each shard checks its own combination)."""
+        from concurrent.futures import ThreadPoolExecutor
+        n = len(off)
+        shards = self._shard_verifiers()
+        cuts = [_lib.shard_range(n, len(shards), k) for k in range(len(shards))]
+        seed = rlc_seed_for(mode, rlc_seed)
+
+        def part(k):
+            lo, hi = cuts[k]
+            return shards[k].verify_rows(pubkey, buf, off[lo:hi], ln[lo:hi], mode, seed, sig_stride, prev_stride)
+        with ThreadPoolExecutor(len(shards)) as ex:
+            parts = list(ex.map(part, range(len(shards))))
+        return tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
+
+    def check_rows(self, pubkey, rows, first, count, mode=_lib.MODE_PER_ROUND, rlc_seed=None, sig_stride=96,
+                   prev_stride=96, reasons=False):
+        """chain.Verifier.check_rows over the handle's GPUs
+        (dgpu_check_rows_multi): the same arguments, the same lists."""
+        lib = self.mctx.lib
+        return check_rows_with(lambda *a: lib.dgpu_check_rows_multi(self.mctx.handle, self._code, *a), lib, pubkey,
+                               rows, first, count, mode, rlc_seed, sig_stride, prev_stride, reasons)
+
+
+class _BorrowedContext:
+    """A context of a dgpu_multi handle as chain.Verifier holds one: the
+    library and the handle, not owned."""
+
+    def __init__(self, lib, handle):
+        self.lib, self.handle = lib, handle
 
 
 class MultiThresholdGroup:

@@ -130,16 +130,25 @@ class MemoryStore:
 
 
 def check_past_beacons(store, verifier, pubkey, up_to, cb=None, window=1 << 16, cancelled=None, mode=0,
-                       decode="host"):
+                       decode="host", replay="host"):
     """SyncManager.CheckPastBeacons (chain/beacon/sync_manager.go:171-232).
 
     `verifier` is a drand_amd.chain.Verifier (GPU); `pubkey` the group key
     bytes.  Returns the ascending list of faulty rounds, or None.
     decode="device" (a BoltStore and a verifier with verify_rows): the
     windows' rows are decoded on the GPU (_check_past_records); the result
-    and the callbacks are those of decode="host"."""
+    and the callbacks are those of decode="host".
+    replay="device" (with decode="device" and a verifier with check_rows):
+    each window is one check_rows call -- the faulty list is built on the GPU
+    behind the verification and only that list comes back
+    (_check_past_rows_device); window=None takes the whole visited range in
+    one call.  The result and the callbacks are the same again."""
     if decode not in ("host", "device"):
         raise ValueError(f"decode must be 'host' or 'device', not {decode!r}")
+    if replay not in ("host", "device"):
+        raise ValueError(f"replay must be 'host' or 'device', not {replay!r}")
+    if replay == "device" and decode != "device":
+        raise ValueError("replay='device' needs decode='device'")
     last = store.last()
     if last.round < up_to:
         up_to = last.round
@@ -147,6 +156,10 @@ def check_past_beacons(store, verifier, pubkey, up_to, cb=None, window=1 << 16, 
     if decode == "device":
         if not (hasattr(store, "scan_offsets") and hasattr(verifier, "verify_rows")):
             raise ValueError("decode='device' needs a BoltStore and a verifier with verify_rows")
+        if replay == "device":
+            if not hasattr(verifier, "check_rows"):
+                raise ValueError("replay='device' needs a verifier with check_rows")
+            return _check_past_rows_device(store, verifier, pubkey, up_to, n, cb, window, cancelled, mode)
         return _check_past_records(store, verifier, pubkey, up_to, n, cb, window, cancelled, mode, device=True)
     if hasattr(store, "scan_offsets") and hasattr(verifier, "verify_records"):
         return _check_past_records(store, verifier, pubkey, up_to, n, cb, window, cancelled, mode)
@@ -275,6 +288,75 @@ def _check_past_records(store, verifier, pubkey, up_to, n, cb, window, cancelled
                     cb(rec.lo + j, up_to)
                 if hit[j]:
                     faulty.append(int(val[j]))
+    return faulty or None
+
+
+def _left_rows_faults(verifier, pubkey, rows, left, mode):
+    """The rows check_rows leaves (not canonical), through the full decoder:
+    (positions, values) of the faults among them, in ascending position -- a
+    row that does not unmarshal faults its own round, one that does is
+    verified (one verify_reasons call for all of them) and a failure faults
+    its stored Round."""
+    pos, val, at, beacons = [], [], [], []
+    for i in left.tolist():
+        j = int(rows.keys[i]) - rows.lo
+        try:
+            beacons.append(beacon_unmarshal(bytes(rows.buf[int(rows.off[i]):int(rows.off[i]) + int(rows.len[i])])))
+            at.append(j)
+        except ValueError:
+            pos.append(j)
+            val.append(rows.lo + j)
+    if beacons:
+        for j, b, r in zip(at, beacons, verifier.verify_reasons(beacons, pubkey, mode)):
+            if int(r) != 0:
+                pos.append(j)
+                val.append(b.round)
+    order = sorted(range(len(pos)), key=pos.__getitem__)
+    return [pos[k] for k in order], [val[k] for k in order]
+
+
+def _check_past_rows_device(store, verifier, pubkey, up_to, n, cb, window, cancelled, mode):
+    """CheckPastBeacons with the loop's bookkeeping on the GPU: per window one
+    Verifier.check_rows call (scan only on the host, as decode="device"),
+    which returns the faulty entries of the canonical rows and of the missing
+    rounds in walk order and the indices of the rows it leaves; those go
+    through _left_rows_faults and are merged in by position.  The visited
+    range, the callbacks and the cancellation point are _check_past_records'."""
+    import numpy as np
+    from concurrent.futures import ThreadPoolExecutor
+    from .ingest import window_rows
+    end = min(n, max(up_to, 1) + 1)
+    if end <= 1:
+        return None
+    if window is None:
+        window = end - 1
+    bounds = [(lo, min(end, lo + window)) for lo in range(1, end, window)]
+    faulty = []
+    with ThreadPoolExecutor(1) as ex:
+        nxt = ex.submit(window_rows, store, *bounds[0])
+        for k in range(len(bounds)):
+            rows = nxt.result()
+            if k + 1 < len(bounds):
+                nxt = ex.submit(window_rows, store, *bounds[k + 1])
+            pos, val, left = verifier.check_rows(pubkey, rows, rows.lo, rows.hi - rows.lo, mode)
+            if len(left):
+                lpos, lval = _left_rows_faults(verifier, pubkey, rows, left, mode)
+                if lpos:  # both lists ascend and no position is in both: a stable merge by position
+                    allpos = np.concatenate([pos, np.asarray(lpos, dtype=np.uint64)])
+                    order = np.argsort(allpos, kind="stable")
+                    pos, val = allpos[order], np.concatenate([val, np.asarray(lval, dtype=np.uint64)])[order]
+            if cb is None and cancelled is None:
+                faulty.extend(val.tolist())
+                continue
+            at = 0
+            for j in range(rows.hi - rows.lo):
+                if cancelled is not None and cancelled():
+                    raise Cancelled()
+                if cb is not None:
+                    cb(rows.lo + j, up_to)
+                if at < len(pos) and int(pos[at]) == j:
+                    faulty.append(int(val[at]))
+                    at += 1
     return faulty or None
 
 

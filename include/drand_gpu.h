@@ -66,7 +66,10 @@ extern "C" {
  * additive: linked segments across GPUs -- dgpu_verify_segment_shard_device
  * (one shard, its first item's previous signature a one-record halo in device
  * memory), dgpu_rlc_root_segment_device (step 1 of the per-rank RLC protocol
- * over such a shard) and dgpu_verify_segment_multi. */
+ * over such a shard) and dgpu_verify_segment_multi.  Also additive: stored rows
+ * (dgpu_decode_rows_device, dgpu_verify_rows) and the check-chain loop's
+ * faulty list built on the device (dgpu_faulty_rounds_device, dgpu_check_rows,
+ * dgpu_check_rows_multi). */
 #define DGPU_ABI_VERSION 3
 
 /* scheme IDs (common/scheme/scheme.go:9,12; bls-unchained-on-g1 added by this build) */
@@ -214,6 +217,70 @@ int dgpu_decode_rows_device(dgpu_ctx *ctx, size_t n, const uint8_t *d_rows, size
 int dgpu_verify_rows(dgpu_ctx *ctx, int scheme, const uint8_t *pk, size_t pk_len, size_t n, const uint8_t *base,
                      const uint64_t *row_off, const uint32_t *row_len, size_t sig_stride, size_t prev_stride, int mode,
                      uint64_t rlc_seed, uint64_t *rounds_out, uint8_t *row_ok, uint8_t *verdict_bits, uint8_t *reason);
+
+/* The faulty list of SyncManager.CheckPastBeacons (chain/beacon/
+ * sync_manager.go:188-222) over one window, built on the device from the
+ * outputs of the row verification.  The loop visits rounds first + j for j in
+ * [0, count) (first + count must not overflow 64 bits: DGPU_EINVAL).  The
+ * window's n rows carry d_keys[r] (the bolt key: the round the loop's Get asks
+ * for, as dgpu_ingest_scan emits it), d_row_ok[r] and d_rounds[r] (the
+ * decoder's outputs, dgpu_decode_rows_device) and d_reason[r] (the row's
+ * DGPU_REASON_* code, 0 = valid).  Position j (one rule, check_rows_outcome of
+ * drand_amd/csrc/check_rows.cuh):
+ *   no row has d_keys[r] == first + j       faulty, value first + j (:202-210)
+ *   the row exists, d_row_ok[r] == 0        left: r is listed in d_left_rows
+ *                                           for the caller's full hexjson
+ *                                           decoder; nothing in the faulty list
+ *   the row exists and is ok, reason != 0   faulty, value d_rounds[r] (:212-214:
+ *                                           the stored Round, not the key)
+ *   otherwise                               nothing
+ * A row whose key lies outside [first, first + count) takes no part.
+ * d_faulty_pos[i] / d_faulty_val[i]: position j and value of the i-th faulty
+ * entry, in ascending position -- the reference's ascending walk; d_left_rows:
+ * the left rows in ascending row index.  The compaction is ordered (flags, a
+ * prefix sum, a scatter): no atomic append, no sort.  d_counts[0], d_counts[1]:
+ * the totals of faulty entries and of left rows, which may exceed the caps;
+ * entries at or beyond a cap are not written and nothing is written past
+ * either buffer.  d_keys must be strictly ascending; with duplicate keys which
+ * row a position takes is unspecified, but no access leaves the given buffers
+ * whatever the keys hold.  n = 0 with count > 0 makes every position faulty;
+ * count = 0 is a no-op that accepts NULL pointers (d_counts is not written).
+ * n < 2^32 - 1.  The scratch (position map, flags, block sums: 5 count + 16
+ * ceil(count / 256) bytes) is the context's.  Asynchronous on `stream` (as
+ * dgpu_verify_beacons_device). */
+int dgpu_faulty_rounds_device(dgpu_ctx *ctx, uint64_t first, size_t count, size_t n, const uint64_t *d_keys,
+                              const uint8_t *d_row_ok, const uint64_t *d_rounds, const uint8_t *d_reason,
+                              uint64_t *d_faulty_pos, uint64_t *d_faulty_val, size_t faulty_cap,
+                              uint64_t *d_left_rows, size_t left_cap, uint64_t *d_counts, void *stream);
+
+/* CheckPastBeacons over one window of stored rows in one call: the rows,
+ * key, strides, mode and seed of dgpu_verify_rows, the rows' keys (n values,
+ * as dgpu_ingest_scan emits them) and the visited range.  Synchronous.  The
+ * rows are decoded and verified exactly as dgpu_verify_rows does, then
+ * dgpu_faulty_rounds_device runs behind that on the same stream over the
+ * decoder's ok flags and rounds and the final statuses.  Contract: faulty_pos,
+ * faulty_val and left_rows (entries below their caps) and *n_faulty, *n_left
+ * (the totals) equal that rule applied to dgpu_verify_rows' row_ok,
+ * rounds_out and reason for the same rows, key, mode and rlc_seed.  The caller
+ * passes each left row to its full hexjson decoder (position keys[r] - first:
+ * an undecodable row faults its own round, a decodable one is verified and a
+ * failure faults its stored Round) and merges by position.  Only the two
+ * lists and their totals are copied back -- 16 bytes, then 16 bytes per
+ * faulty entry and 8 per left row below the caps -- and reason (optional, n
+ * bytes, as dgpu_verify_rows writes it) only when given.  DGPU_EINVAL before
+ * any device work: keys not strictly ascending, a key outside [first, first +
+ * count), first + count overflowing 64 bits, a NULL buffer with a nonzero
+ * size (rows and keys with n > 0, a list with a nonzero cap, n_faulty,
+ * n_left).  n = 0 verifies nothing (the key and scheme are still checked) and
+ * makes every position faulty; count = 0 (hence n = 0) writes two zero
+ * totals.  The keys are staged beside the rows through the same ring, slice
+ * by slice.  Staged bytes (dgpu_staging_stats):
+ *   dgpu_verify_rows' bytes + 8 n   (each row's key). */
+int dgpu_check_rows(dgpu_ctx *ctx, int scheme, const uint8_t *pk, size_t pk_len, size_t n, const uint8_t *base,
+                    const uint64_t *row_off, const uint32_t *row_len, const uint64_t *keys, size_t sig_stride,
+                    size_t prev_stride, int mode, uint64_t rlc_seed, uint64_t first, size_t count,
+                    uint64_t *faulty_pos, uint64_t *faulty_val, size_t faulty_cap, uint64_t *n_faulty,
+                    uint64_t *left_rows, size_t left_cap, uint64_t *n_left, uint8_t *reason);
 
 /* A linked chain segment verified from its signatures alone: the walk from a
  * point of trust, client/verify.go:118-178, which builds each beacon as
@@ -393,7 +460,8 @@ int dgpu_set_profiling(dgpu_ctx *ctx, int enable);
 /* Host-record staging of the last call on the context that took host records
  * (dgpu_verify_beacons, dgpu_verify_batch, dgpu_verify_recovered, a shard of
  * dgpu_verify_multi or dgpu_verify_segment_multi) or stored rows
- * (dgpu_verify_rows: its bytes are stated there): the records go through a library-owned pinned ring
+ * (dgpu_verify_rows, dgpu_check_rows, a shard of dgpu_check_rows_multi: their
+ * bytes are stated there): the records go through a library-owned pinned ring
  * (two 16 MiB slots per context, filled by host threads, DMA'd on the
  * context's copy stream) slice by slice, each slice's kernels starting when
  * its records have arrived.  device_ms = the staging's span on the copy
@@ -590,6 +658,26 @@ int dgpu_verify_segment_multi(dgpu_multi *m, int scheme, const uint8_t *pk, size
                               size_t n, const uint8_t *sigs, size_t sig_stride, const uint32_t *sig_len,
                               const uint8_t *seed_prev, size_t seed_prev_len, int mode, uint64_t rlc_seed,
                               uint8_t *verdict_bits, uint8_t *reason, uint8_t *randomness32);
+
+/* dgpu_check_rows over the devices of a multi handle: the same arguments and
+ * the same results, element for element, in both modes.  The rows shard by
+ * dgpu_shard_range(n, D, k); each shard's rows and keys go through its
+ * context's ring and row decoder (dgpu_staging_stats of that context: the
+ * shard's bytes by dgpu_check_rows' formula).  The RLC phases are
+ * dgpu_verify_multi's unchanged: per-device seeds, the root all-gather, one
+ * check, the per-shard descent.  Each device builds the list of the
+ * positions it owns: shard 0 from position 0, a later non-empty shard k from
+ * keys[lo_k] - first, the last non-empty shard up to count (a run of missing
+ * rounds in front of a shard's first key belongs to the shard before it; with
+ * n = 0 shard 0 owns everything).  The host concatenates the per-device lists
+ * in shard order, left-row indices made global; no collective carries them,
+ * and no verdict bitmap is gathered (the reasons only when `reason` is
+ * given).  RCCL with two or more real ranks is unmeasured. */
+int dgpu_check_rows_multi(dgpu_multi *m, int scheme, const uint8_t *pk, size_t pk_len, size_t n, const uint8_t *base,
+                          const uint64_t *row_off, const uint32_t *row_len, const uint64_t *keys, size_t sig_stride,
+                          size_t prev_stride, int mode, uint64_t rlc_seed, uint64_t first, size_t count,
+                          uint64_t *faulty_pos, uint64_t *faulty_val, size_t faulty_cap, uint64_t *n_faulty,
+                          uint64_t *left_rows, size_t left_cap, uint64_t *n_left, uint8_t *reason);
 
 /* dgpu_set_group on every device of the handle (the aggregator's group,
  * chain/beacon/chain.go:158-168 -> key.Scheme.Recover). */
