@@ -33,6 +33,7 @@
 #include "ingest_row.cuh"
 #include "check_rows.cuh"
 #include "scratch_layouts.h"
+#include "record_arrays.h"
 
 using namespace dgpu;
 
@@ -172,86 +173,6 @@ struct key_entry {
   DevBuf consts, table;
   uint64_t stamp = 0;
 };
-
-// A message source as the host holds it: any of the three device types
-// (kernels.cuh), selected by `linked` (SRC_*).  SRC_RECORDS: its msg_src part
-// is the source; SRC_LINKED: its msg_src_linked part; SRC_HALO: with_src
-// builds the msg_src_halo from the msg_src part, first_round, g0 and the two
-// halo pointers (host memory until stage_prepare_locked, device after).
-struct msg_src_host : msg_src_linked {
-  const uint8_t* halo;
-  const uint32_t* halo_len;
-};
-
-// Signature group and message source of one verify call.
-struct verify_args {
-  int scheme;
-  size_t n;
-  msg_src_host m;
-  const uint8_t* sigs;
-  size_t sig_stride;
-  const uint32_t* sig_len;
-  int mode;
-  uint64_t seed;
-};
-
-msg_src_host beacon_src(const uint64_t* rounds, const uint8_t* prev, size_t prev_stride, const uint32_t* prev_len,
-                        bool chained) {
-  msg_src_host m{};
-  m.rounds = rounds;
-  m.chained = chained ? 1 : 0;
-  m.prev = chained ? prev : nullptr;
-  m.prev_stride = chained ? prev_stride : 0;
-  m.prev_len = chained ? prev_len : nullptr;
-  return m;
-}
-
-// The linked form (kernels.cuh msg_src_linked): round first_round + g, previous
-// signature = the seed (copied into the source) for g = 0, else signature
-// g - 1 of the call's signature array.  seed_len <= 96 (checked by the entry
-// points).
-msg_src_host linked_src(uint64_t first_round, const uint8_t* sigs, size_t sig_stride, const uint32_t* sig_len,
-                        const uint8_t* seed, size_t seed_len, bool chained) {
-  msg_src_host m{};
-  m.linked = SRC_LINKED;
-  m.first_round = first_round;
-  m.chained = chained ? 1 : 0;
-  if (chained) {
-    m.prev = sigs;
-    m.prev_stride = sig_stride;
-    m.prev_len = sig_len;
-    m.seed_len = (uint32_t)seed_len;
-    if (seed_len) memcpy(m.seed, seed, seed_len);
-  }
-  return m;
-}
-
-// One shard of a linked segment (kernels.cuh msg_src_halo): first_round is the
-// shard's own first round, and item 0's previous signature is the record at
-// halo / halo_len (never read by an unchained source).
-msg_src_host halo_src(uint64_t first_round, const uint8_t* sigs, size_t sig_stride, const uint32_t* sig_len,
-                      const uint8_t* halo, const uint32_t* halo_len, bool chained) {
-  msg_src_host m{};
-  m.linked = SRC_HALO;
-  m.first_round = first_round;
-  m.chained = chained ? 1 : 0;
-  if (chained) {
-    m.prev = sigs;
-    m.prev_stride = sig_stride;
-    m.prev_len = sig_len;
-    m.halo = halo;
-    m.halo_len = halo_len;
-  }
-  return m;
-}
-
-msg_src_host raw_src(const uint8_t* msgs, size_t stride, const uint32_t* len) {
-  msg_src_host m{};
-  m.msgs = msgs;
-  m.msg_stride = stride;
-  m.msg_len = len;
-  return m;
-}
 
 // f(source) with the source as the type its kernels are instantiated for:
 // the halo form, the linked form, or the msg_src part of any other.
@@ -1384,6 +1305,50 @@ msg_src_host src_slice(const msg_src_host& m, size_t off) {
   return r;
 }
 
+// The stored rows of a row call (verify_args' m.rows).  The caller's rows
+// (row i = len[i] bytes at base + off[i]) are staged packed back to back:
+// slen[i] is the staged length (len[i], or 0 for a row longer than any
+// canonical row at the strides: it is non-canonical whatever it holds and is
+// not staged), pos[i] row i's position in the packed run (pos[n] = the run's
+// bytes).  The device side (rows_prepare_locked): the packed run and the two
+// arrays (in_rows), and the record arrays k_ingest_rows writes -- the
+// context's in_* buffers, the verify call's inputs.
+struct rows_src {
+  const uint8_t* base;
+  const uint64_t* off;
+  const uint32_t* len;
+  std::vector<uint32_t> slen;
+  std::vector<uint64_t> pos;
+  ingest_rows_layout dev;
+  uint64_t* d_rounds;
+  uint8_t *d_sigs, *d_prev, *d_ok;
+  uint32_t *d_sig_len, *d_prev_len;
+  size_t sig_stride, prev_stride;
+  // dgpu_check_rows: the rows' keys (host), staged slice by slice behind the
+  // slice's rows into d_keys; nullptr for dgpu_verify_rows
+  const uint64_t* keys;
+  uint64_t* d_keys;
+};
+
+// The host side of a rows_src: the caller's arrays and the strides.
+rows_src rows_src_of(const uint8_t* base, const uint64_t* row_off, const uint32_t* row_len, const uint64_t* keys,
+                     size_t sig_stride, size_t prev_stride) {
+  rows_src R{};
+  R.base = base, R.off = row_off, R.len = row_len, R.keys = keys;
+  R.sig_stride = sig_stride, R.prev_stride = prev_stride;
+  return R;
+}
+
+// The argument checks of a row call with rows: the row arrays and the strides.
+int rows_check_args(const rows_src& R, size_t sig_bytes) {
+  if (!R.base || !R.off || !R.len) return set_err(DGPU_EINVAL, "null row or output buffer");
+  if (R.sig_stride < sig_bytes) return set_err(DGPU_EINVAL, "bad signature stride");
+  const size_t max_len = ingest_row_max_len(R.sig_stride, R.prev_stride);
+  if (R.sig_stride > STAGE_SLOT_BYTES || R.prev_stride > STAGE_SLOT_BYTES || max_len + 16 > STAGE_SLOT_BYTES)
+    return set_err(DGPU_EINVAL, "strides too large for the staging ring");
+  return DGPU_OK;
+}
+
 int check_args(const dgpu_ctx* c, const key_entry* key, const verify_args& a) {
   if (!scheme_known(a.scheme)) return set_err(DGPU_EINVAL, "bad scheme %d", a.scheme);
   if (a.mode != DGPU_MODE_PER_ROUND && a.mode != DGPU_MODE_RLC) return set_err(DGPU_EINVAL, "bad mode %d", a.mode);
@@ -1392,6 +1357,7 @@ int check_args(const dgpu_ctx* c, const key_entry* key, const verify_args& a) {
     return set_err(DGPU_ENOKEY, "the public key is on the wrong group for scheme %d", a.scheme);
   if (a.n == 0) return DGPU_OK;
   const size_t sig_bytes = sig_on_g1(a.scheme) ? 48 : 96;
+  if (a.m.rows) return rows_check_args(*a.m.rows, sig_bytes);  // (the record buffers are the context's)
   if (!a.sigs || !a.sig_len || a.sig_stride < sig_bytes) return set_err(DGPU_EINVAL, "bad signature buffers");
   if (a.m.msgs || a.m.msg_len) {
     if (!a.m.msgs || !a.m.msg_len) return set_err(DGPU_EINVAL, "bad message buffers");
@@ -1498,6 +1464,62 @@ int verify_status_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a
   return DGPU_OK;
 }
 
+// ---------------------------------------------------------------- the RLC shard protocol
+// The per-rank entry points and multi_verify run these three steps, the exchange of roots between the first two.
+// Shard root: the shard's points and its root by bucket MSM, left in msm_root
+// and copied to d_root (device; rlc_root_layout); an empty shard's is the identity pair.
+int rlc_shard_root_locked(dgpu_ctx* c, const verify_args& a, uint8_t* d_root, hipStream_t s) {
+  const rlc_geom G = rlc_geom_of(sig_on_g1(a.scheme));
+  if (a.n == 0) {
+    uint32_t inf[G2J_WORDS];
+    rlc_identity_words(G.g1, inf);
+    const rlc_root_layout root = layout_at<rlc_root_layout>(d_root, G.jw);
+    HIP_TRY(hipMemcpyAsync(root.P, inf, (size_t)G.jw * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(root.S, inf, (size_t)G.jw * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));  // the host source goes out of scope
+    return DGPU_OK;
+  }
+  rlc_root_layout root;
+  int rc;
+  if ((rc = c->status.ensure(a.n))) return rc;
+  c->n_ev = 0;
+  c->ev_overflow = false;
+  if ((rc = rlc_points_locked(c, a, s)) || (rc = rlc_root_msm_locked(c, a, s, c->msm_root, &root))) return rc;
+  HIP_TRY(hipMemcpyAsync(d_root, root.P, layout_bytes<rlc_root_layout>(G.jw), hipMemcpyDeviceToDevice, s));
+  return DGPU_OK;
+}
+
+// Node check: the n_roots roots at d_roots summed into the context's rlc_root, one
+// pairing check of the sum.  *fail: the node's batch holds a bad round.  Synchronizes s.
+int rlc_node_check_locked(dgpu_ctx* c, const key_entry* key, size_t n_roots, const uint8_t* d_roots, hipStream_t s,
+                          bool* fail) {
+  rlc_root_layout sum;
+  int rc = carve(c->rlc_root, &sum, rlc_geom_of(key->g2key).jw);
+  if (rc) return rc;
+  mark(c, s, "rlc_root_sum");
+  if (key->g2key)
+    hipLaunchKernelGGL(k_rlc_sum_roots<G1Ops>, dim3(1), dim3(64), 0, s, (int)n_roots, (const uint32_t*)d_roots, sum.P,
+                       sum.S);
+  else
+    hipLaunchKernelGGL(k_rlc_sum_roots<G2Ops>, dim3(1), dim3(64), 0, s, (int)n_roots, (const uint32_t*)d_roots, sum.P,
+                       sum.S);
+  HIP_TRY(hipGetLastError());
+  std::vector<uint8_t> f;
+  if ((rc = rlc_check_locked(c, key, std::vector<uint32_t>{0}, 1, sum.P, sum.S, s, &f))) return rc;
+  *fail = f[0] != 0;
+  return DGPU_OK;
+}
+
+// Shard finish: under a failing node the shard is resolved against its own root in
+// msm_root, checked first unless it is the node's (one root: known to fail).
+int rlc_shard_finish_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a, bool node_failed, size_t n_roots,
+                            hipStream_t s) {
+  if (!node_failed || a.n == 0) return DGPU_OK;
+  rlc_root_layout shard;
+  int rc = carve(c->msm_root, &shard, rlc_geom_of(key->g2key).jw);
+  return rc ? rc : rlc_resolve_locked(c, key, a, s, shard, n_roots == 1);
+}
+
 // The final statuses -> verdict bitmap, then (d_rand: optional, 32 bytes per
 // round) the verified rounds' randomness.  a's signature arrays are device
 // memory.  Closes the call's stage markers.
@@ -1528,43 +1550,48 @@ int verify_device_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a
   return DGPU_OK;
 }
 
-// Stage the host records of a verify call into the context's input buffers;
-// rewrites a's pointers to the device copies.  Records with a length above
-// their stride are rejected here (the host path reports them as EINVAL).
+// The context buffer behind a record array (record_arrays.h REC_*).
+DevBuf& record_buf(dgpu_ctx* c, int buf) {
+  DevBuf* const b[REC_BUFS] = {&c->in_rounds, &c->in_prev,    &c->in_prev_len, &c->in_msgs,    &c->in_msg_len,
+                               &c->in_sigs,   &c->in_sig_len, &c->in_halo,     &c->in_halo_len};
+  return *b[buf];
+}
+
+// The device buffers of the record arrays L of call a; a's pointers become
+// the device copies' (their contents: stage_inputs_locked, host_stager).
+int record_buffers_locked(dgpu_ctx* c, verify_args& a, const record_list& L) {
+  for (const record_array& e : L) {
+    DevBuf& b = record_buf(c, e.buf);
+    int rc = b.ensure((e.part == PART_ONCE ? 1 : a.n) * e.item_bytes + e.pad);
+    if (rc) return rc;
+    record_ptr_set(a, e, b.p);
+  }
+  record_aliases(a);
+  return DGPU_OK;
+}
+
+// A record of items [lo, hi) longer than its stride fails the host call (the device paths flag it per item).
+int record_lengths_check(const record_list& L, int part, size_t lo, size_t hi) {
+  size_t i = 0;
+  const record_array* e = record_bad_length(L, part, lo, hi, &i);
+  return e ? set_err(DGPU_EINVAL, e->len_fmt, i, e->len[i]) : DGPU_OK;
+}
+// ... of one length array of n items (the data tools' entry points)
+int lengths_check(const uint32_t* len, size_t n, size_t stride, const char* fmt) {
+  const size_t i = first_long_item(len, 0, n, stride);
+  return i < n ? set_err(DGPU_EINVAL, fmt, i, len[i]) : DGPU_OK;
+}
+
+// The host records of a verify call into the context's input buffers by whole-batch pageable
+// copies (the A/B build's DGPU_STAGE=pageable); a's pointers become the device copies'.
 int stage_inputs_locked(dgpu_ctx* c, verify_args& a, hipStream_t s) {
-  const size_t n = a.n;
+  const verify_args host = a;
+  const record_list L = record_arrays(host);
   int rc;
-  if ((rc = c->in_sigs.ensure(n * a.sig_stride)) || (rc = c->in_sig_len.ensure(n * 4))) return rc;
-  HIP_TRY(hipMemcpyAsync(c->in_sigs.p, a.sigs, n * a.sig_stride, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(c->in_sig_len.p, a.sig_len, n * 4, hipMemcpyHostToDevice, s));
-  a.sigs = (const uint8_t*)c->in_sigs.p;
-  a.sig_len = (const uint32_t*)c->in_sig_len.p;
-  msg_src_host& m = a.m;
-  if (m.linked) {  // the records are the signature arrays
-    if (m.chained) m.prev = a.sigs, m.prev_len = a.sig_len;
-    return DGPU_OK;
-  }
-  if (m.msgs) {
-    for (size_t i = 0; i < n; ++i)
-      if (m.msg_len[i] > m.msg_stride) return set_err(DGPU_EINVAL, "msg_len[%zu]=%u > msg_stride", i, m.msg_len[i]);
-    if ((rc = c->in_msgs.ensure(n * m.msg_stride + 1)) || (rc = c->in_msg_len.ensure(n * 4))) return rc;
-    if (m.msg_stride) HIP_TRY(hipMemcpyAsync(c->in_msgs.p, m.msgs, n * m.msg_stride, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->in_msg_len.p, m.msg_len, n * 4, hipMemcpyHostToDevice, s));
-    m.msgs = (const uint8_t*)c->in_msgs.p;
-    m.msg_len = (const uint32_t*)c->in_msg_len.p;
-    return DGPU_OK;
-  }
-  if ((rc = c->in_rounds.ensure(n * 8))) return rc;
-  HIP_TRY(hipMemcpyAsync(c->in_rounds.p, m.rounds, n * 8, hipMemcpyHostToDevice, s));
-  m.rounds = (const uint64_t*)c->in_rounds.p;
-  if (m.chained) {
-    for (size_t i = 0; i < n; ++i)
-      if (m.prev_len[i] > m.prev_stride) return set_err(DGPU_EINVAL, "prev_len[%zu]=%u > prev_stride", i, m.prev_len[i]);
-    if ((rc = c->in_prev.ensure(n * m.prev_stride + 1)) || (rc = c->in_prev_len.ensure(n * 4))) return rc;
-    if (m.prev_stride) HIP_TRY(hipMemcpyAsync(c->in_prev.p, m.prev, n * m.prev_stride, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c->in_prev_len.p, m.prev_len, n * 4, hipMemcpyHostToDevice, s));
-    m.prev = (const uint8_t*)c->in_prev.p;
-    m.prev_len = (const uint32_t*)c->in_prev_len.p;
+  if ((rc = record_lengths_check(L, PART_MSG, 0, a.n)) || (rc = record_buffers_locked(c, a, L))) return rc;
+  for (const record_array& e : L) {
+    const size_t bytes = (e.part == PART_ONCE ? 1 : a.n) * e.item_bytes;
+    if (bytes) HIP_TRY(hipMemcpyAsync((void*)record_ptr(a, e), record_ptr(host, e), bytes, hipMemcpyHostToDevice, s));
   }
   return DGPU_OK;
 }
@@ -1603,31 +1630,6 @@ int ring_copy_locked(dgpu_ctx* c, void* dst, const void* src, size_t bytes) {
   }
   return DGPU_OK;
 }
-
-// The stored rows of a dgpu_verify_rows call.  The caller's rows (row i =
-// len[i] bytes at base + off[i]) are staged packed back to back: slen[i] is
-// the staged length (len[i], or 0 for a row longer than any canonical row at
-// the strides: it is non-canonical whatever it holds and is not staged),
-// pos[i] row i's position in the packed run (pos[n] = the run's bytes).  The
-// device side: the packed run and the two arrays (in_rows), and the record
-// arrays k_ingest_rows writes -- the context's in_* buffers, the verify
-// call's inputs.
-struct rows_src {
-  const uint8_t* base;
-  const uint64_t* off;
-  const uint32_t* len;
-  std::vector<uint32_t> slen;
-  std::vector<uint64_t> pos;
-  ingest_rows_layout dev;
-  uint64_t* d_rounds;
-  uint8_t *d_sigs, *d_prev, *d_ok;
-  uint32_t *d_sig_len, *d_prev_len;
-  size_t sig_stride, prev_stride;
-  // dgpu_check_rows: the rows' keys (host), staged slice by slice behind the
-  // slice's rows into d_keys; nullptr for dgpu_verify_rows
-  const uint64_t* keys;
-  uint64_t* d_keys;
-};
 
 // The ring bytes of rows [a, b) of a rows_src: the packed rows, then (on an
 // 8-byte boundary) their positions and their lengths.
@@ -1702,8 +1704,8 @@ int ring_ensure_locked(dgpu_ctx* c) {
 // after the entry point returns.
 struct host_stager {
   dgpu_ctx* c;
-  verify_args host;               // the caller's pointers
-  const rows_src* rows = nullptr;  // dgpu_verify_rows: the records are decoded on the device from these stored rows
+  verify_args host;               // the caller's pointers (m.rows: the records are decoded on the device from them)
+  record_list list;               // the arrays it stages (record_arrays of `host`)
   std::vector<size_t> lo;         // slice k = [lo[k], lo[k + 1])
   std::vector<hipEvent_t> ev_msg, ev_sig;
   std::thread th;
@@ -1717,7 +1719,7 @@ struct host_stager {
   size_t bytes = 0;
   double host_ms = 0.0;                    // the thread's wall time, first memcpy to last DMA enqueued
 
-  host_stager(dgpu_ctx* c_, const verify_args& h) : c(c_), host(h) {}
+  host_stager(dgpu_ctx* c_, const verify_args& h) : c(c_), host(h), list(record_arrays(host)) {}
   ~host_stager() {
     const bool ok = th.joinable();
     cancel = true;
@@ -1745,10 +1747,21 @@ struct host_stager {
     HIP_TRY(hipEventCreate(&t1));
     return DGPU_OK;
   }
-  // the message arrays of items [a, b) (checked against their stride), then
-  // its signature arrays; an event after each part
+  // one part of the list for items [a, b), through the ring (PART_ONCE: the call's one record)
+  int copy_part(const verify_args& dev, int part, size_t a, size_t b) {
+    for (const record_array& e : list) {
+      if (e.part != part) continue;
+      const size_t off = part == PART_ONCE ? 0 : a * e.item_bytes, len = (part == PART_ONCE ? 1 : b - a) * e.item_bytes;
+      int r = ring_copy_locked(c, (uint8_t*)record_ptr(dev, e) + off, record_ptr(host, e) + off, len);
+      if (r) return r;
+    }
+    return DGPU_OK;
+  }
+  // Slice k = items [a, b) on the in-order copy stream: the once-per-call entries ahead of
+  // everything else of the call (a shard's halo: every event a kernel waits for covers it),
+  // the message part (its lengths checked first) and its event, the signature part and its event.
   int stage_slice(const verify_args& dev, size_t k, size_t a, size_t b) {
-    const msg_src_host& m = host.m;
+    const rows_src* rows = host.m.rows;
     const size_t n = b - a;
     int r;
     if (rows) {
@@ -1762,43 +1775,9 @@ struct host_stager {
         if ((r = ring_copy_locked(c, rows->d_keys + a, rows->keys + a, n * 8))) return r;
         bytes += n * 8;
       }
-      HIP_TRY(hipEventRecord(ev_msg[k], c->stream_copy));
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        staged_msg = k + 1;
-      }
-      cv.notify_all();
-      HIP_TRY(hipEventRecord(ev_sig[k], c->stream_copy));
-      return DGPU_OK;
-    }
-    // A shard's halo (one record of the stride and its length, not counted in
-    // `bytes`) ahead of everything else of the call on the in-order copy
-    // stream: every event a kernel waits for covers it.
-    if (k == 0 && m.linked == SRC_HALO && m.chained &&
-        ((r = ring_copy_locked(c, (uint8_t*)dev.m.halo, m.halo, host.sig_stride)) ||
-         (r = ring_copy_locked(c, (uint32_t*)dev.m.halo_len, m.halo_len, 4))))
+    } else if ((r = record_lengths_check(list, PART_MSG, a, b)) || (k == 0 && (r = copy_part(dev, PART_ONCE, a, b))) ||
+               (r = copy_part(dev, PART_MSG, a, b))) {
       return r;
-    if (m.linked) {
-      // no message part: the slice's digests read its signatures (wait_part)
-    } else if (m.msgs) {
-      for (size_t i = a; i < b; ++i)
-        if (m.msg_len[i] > m.msg_stride) return set_err(DGPU_EINVAL, "msg_len[%zu]=%u > msg_stride", i, m.msg_len[i]);
-      if ((r = ring_copy_locked(c, (uint8_t*)dev.m.msgs + a * m.msg_stride, m.msgs + a * m.msg_stride,
-                                n * m.msg_stride)) ||
-          (r = ring_copy_locked(c, (uint32_t*)dev.m.msg_len + a, m.msg_len + a, n * 4)))
-        return r;
-      bytes += n * (m.msg_stride + 4);
-    } else {
-      if (m.chained)
-        for (size_t i = a; i < b; ++i)
-          if (m.prev_len[i] > m.prev_stride)
-            return set_err(DGPU_EINVAL, "prev_len[%zu]=%u > prev_stride", i, m.prev_len[i]);
-      if ((r = ring_copy_locked(c, (uint64_t*)dev.m.rounds + a, m.rounds + a, n * 8))) return r;
-      if (m.chained && ((r = ring_copy_locked(c, (uint8_t*)dev.m.prev + a * m.prev_stride, m.prev + a * m.prev_stride,
-                                              n * m.prev_stride)) ||
-                        (r = ring_copy_locked(c, (uint32_t*)dev.m.prev_len + a, m.prev_len + a, n * 4))))
-        return r;
-      bytes += n * (8 + (m.chained ? m.prev_stride + 4 : 0));
     }
     HIP_TRY(hipEventRecord(ev_msg[k], c->stream_copy));
     {
@@ -1806,11 +1785,8 @@ struct host_stager {
       staged_msg = k + 1;
     }
     cv.notify_all();
-    if ((r = ring_copy_locked(c, (uint8_t*)dev.sigs + a * host.sig_stride, host.sigs + a * host.sig_stride,
-                              n * host.sig_stride)) ||
-        (r = ring_copy_locked(c, (uint32_t*)dev.sig_len + a, host.sig_len + a, n * 4)))
-      return r;
-    bytes += n * (host.sig_stride + 4);
+    if (!rows && (r = copy_part(dev, PART_SIG, a, b))) return r;
+    if (!rows) bytes += n * record_item_bytes(list);
     HIP_TRY(hipEventRecord(ev_sig[k], c->stream_copy));
     return DGPU_OK;
   }
@@ -1862,41 +1838,24 @@ int stager_wait_all(host_stager* stg, hipStream_t s) { return stg ? stg->wait_al
 // The device buffers of a staged call; a's pointers become the device
 // copies' (their contents arrive slice by slice).
 int stage_prepare_locked(dgpu_ctx* c, verify_args& a) {
-  const size_t n = a.n;
-  int rc;
-  if ((rc = ring_ensure_locked(c))) return rc;
-  if ((rc = c->in_sigs.ensure(n * a.sig_stride)) || (rc = c->in_sig_len.ensure(n * 4))) return rc;
-  a.sigs = (const uint8_t*)c->in_sigs.p;
-  a.sig_len = (const uint32_t*)c->in_sig_len.p;
-  msg_src_host& m = a.m;
-  if (m.linked) {  // the records are the signature arrays: no rounds, no second copy of the signatures
-    if (m.chained) m.prev = a.sigs, m.prev_len = a.sig_len;
-    if (m.linked == SRC_HALO && m.chained) {  // the halo: one record of the stride, and its length
-      if ((rc = c->in_halo.ensure(a.sig_stride)) || (rc = c->in_halo_len.ensure(4))) return rc;
-      m.halo = (const uint8_t*)c->in_halo.p;
-      m.halo_len = (const uint32_t*)c->in_halo_len.p;
-    }
-    return DGPU_OK;
-  }
-  if (m.msgs) {
-    if ((rc = c->in_msgs.ensure(n * m.msg_stride + 1)) || (rc = c->in_msg_len.ensure(n * 4))) return rc;
-    m.msgs = (const uint8_t*)c->in_msgs.p;
-    m.msg_len = (const uint32_t*)c->in_msg_len.p;
-    return DGPU_OK;
-  }
-  if ((rc = c->in_rounds.ensure(n * 8))) return rc;
-  m.rounds = (const uint64_t*)c->in_rounds.p;
-  if (m.chained) {
-    if ((rc = c->in_prev.ensure(n * m.prev_stride + 1)) || (rc = c->in_prev_len.ensure(n * 4))) return rc;
-    m.prev = (const uint8_t*)c->in_prev.p;
-    m.prev_len = (const uint32_t*)c->in_prev_len.p;
-  }
-  return DGPU_OK;
+  int rc = ring_ensure_locked(c);
+  return rc ? rc : record_buffers_locked(c, a, record_arrays(a));
 }
 
-// The device side of a rows_src behind stage_prepare_locked: the packed rows
-// and the record arrays the decoder writes (the context's in_* buffers).
-int rows_prepare_locked(dgpu_ctx* c, const verify_args& a, rows_src* rows) {
+// The rest of a row call's rows_src behind stage_prepare_locked: staged lengths, packed positions,
+// the packed rows on the device and the record arrays the decoder writes (the context's in_* buffers).
+int rows_prepare_locked(dgpu_ctx* c, const verify_args& a) {
+  rows_src* rows = a.m.rows;
+  const size_t max_len = ingest_row_max_len(rows->sig_stride, rows->prev_stride);
+  rows->slen.resize(a.n);
+  rows->pos.resize(a.n + 1);
+  uint64_t at = 0;
+  for (size_t i = 0; i < a.n; ++i) {
+    rows->slen[i] = rows->len[i] <= max_len ? rows->len[i] : 0;
+    rows->pos[i] = at;
+    at += rows->slen[i];
+  }
+  rows->pos[a.n] = at;
   int rc;
   // the decoder writes every row's previous signature, whatever the scheme reads
   if ((rc = c->in_prev.ensure(a.n * rows->prev_stride + 1)) || (rc = c->in_prev_len.ensure(a.n * 4)) ||
@@ -1913,28 +1872,29 @@ int rows_prepare_locked(dgpu_ctx* c, const verify_args& a, rows_src* rows) {
   return DGPU_OK;
 }
 
-// verify_status_locked over host records, overlapping their staging with the
-// verification: the slices are the per-round G2 path's lane slices
-// (lane_slice_len), one slice for every other pipeline.
-// rows (dgpu_verify_rows): a's records are decoded on the device from these
-// stored rows, slice by slice behind their DMA; a's pointers become the
-// record arrays the decoder writes.
-int verify_status_host_locked(dgpu_ctx* c, const key_entry* key, verify_args& a, hipStream_t s,
-                              rows_src* rows = nullptr) {
-  host_stager stg(c, a);
+// The front of every staged host call: the device buffers (a's pointers become theirs; a row
+// call's records are decoded into them, slice by slice behind their DMA), the copy stream behind
+// the previous call, slices of slice_len items with their events, and the staging thread running.
+int stager_begin_locked(dgpu_ctx* c, host_stager& stg, verify_args& a, size_t slice_len) {
   int rc;
   if ((rc = stage_prepare_locked(c, a))) return rc;
-  if (rows) {
-    if ((rc = rows_prepare_locked(c, a, rows))) return rc;
-    stg.rows = rows;
-  }
+  if (a.m.rows && (rc = rows_prepare_locked(c, a))) return rc;
   // the copy stream (device buffers, ring slots) after the previous call's work
   HIP_TRY(hipStreamWaitEvent(c->stream_copy, c->done, 0));
-  const size_t n0 = lane_slice_len(c, a);
-  for (size_t off = 0; off < a.n; off += n0) stg.lo.push_back(off);
+  for (size_t off = 0; off < a.n; off += slice_len) stg.lo.push_back(off);
   stg.lo.push_back(a.n);
   if ((rc = stg.make_events(stg.lo.size() - 1))) return rc;
   stg.start(a);
+  return DGPU_OK;
+}
+
+// verify_status_locked over host records, overlapping their staging with the
+// verification: the slices are the per-round G2 path's lane slices
+// (lane_slice_len), one slice for every other pipeline.
+int verify_status_host_locked(dgpu_ctx* c, const key_entry* key, verify_args& a, hipStream_t s) {
+  host_stager stg(c, a);
+  int rc = stager_begin_locked(c, stg, a, lane_slice_len(c, a));
+  if (rc) return rc;
 #ifdef DG_AB_KNOBS
   if (c->test_stage_only) return stg.wait_all(s);  // staging rehearsal: no verification (statuses undefined)
 #endif
@@ -1945,114 +1905,63 @@ int verify_status_host_locked(dgpu_ctx* c, const key_entry* key, verify_args& a,
 
 // Every record of a host call on the device before anything else runs on s
 // (the RLC root's points need the whole shard): one slice through the ring.
-// rows: as verify_status_host_locked.
-int stage_all_host_locked(dgpu_ctx* c, verify_args& a, hipStream_t s, rows_src* rows = nullptr) {
+int stage_all_host_locked(dgpu_ctx* c, verify_args& a, hipStream_t s) {
   host_stager stg(c, a);
+  int rc = stager_begin_locked(c, stg, a, std::max<size_t>(a.n, 1));
+  return rc ? rc : stg.wait_all(s);
+}
+
+// The results of a call whose statuses are final, asynchronous on s: the bitmap packed
+// (pack_results_locked: stage markers closed) into d_bits -- the context's out_bits when NULL --
+// and copied to `bits` (host; optional); the reasons (optional), a copy of the statuses of kind
+// `reason_kind` (to the host, or a device buffer); the randomness (optional, host) through out_rand.
+int results_out_locked(dgpu_ctx* c, const verify_args& a, uint8_t* d_bits, uint8_t* bits, uint8_t* reason,
+                       hipMemcpyKind reason_kind, uint8_t* rand32, hipStream_t s) {
   int rc;
-  if ((rc = stage_prepare_locked(c, a))) return rc;
-  if (rows) {
-    if ((rc = rows_prepare_locked(c, a, rows))) return rc;
-    stg.rows = rows;
+  if (!d_bits) {
+    if ((rc = c->out_bits.ensure((a.n + 7) / 8))) return rc;
+    d_bits = (uint8_t*)c->out_bits.p;
   }
-  HIP_TRY(hipStreamWaitEvent(c->stream_copy, c->done, 0));
-  stg.lo = {0, a.n};
-  if ((rc = stg.make_events(1))) return rc;
-  stg.start(a);
-  return stg.wait_all(s);
+  if (rand32 && (rc = c->out_rand.ensure(a.n * 32))) return rc;
+  if ((rc = pack_results_locked(c, a, d_bits, rand32 ? (uint8_t*)c->out_rand.p : nullptr, s))) return rc;
+  if (bits) HIP_TRY(hipMemcpyAsync(bits, d_bits, (a.n + 7) / 8, hipMemcpyDeviceToHost, s));
+  if (reason) HIP_TRY(hipMemcpyAsync(reason, c->status.p, a.n, reason_kind, s));
+  if (rand32) HIP_TRY(hipMemcpyAsync(rand32, c->out_rand.p, a.n * 32, hipMemcpyDeviceToHost, s));
+  return DGPU_OK;
 }
 
 // Host-buffer verify: stage, verify, copy the verdicts back (synchronous).
 // rand32 (optional, n x 32 bytes): the verified rounds' randomness, returned
 // with the verdicts.
-int verify_host_pageable_locked(dgpu_ctx* c, const key_entry* key, verify_args a, uint8_t* verdict_bits,
-                                uint8_t* reason, uint8_t* rand32);
 int verify_host_locked(dgpu_ctx* c, const key_entry* key, verify_args a, uint8_t* verdict_bits, uint8_t* reason,
                        uint8_t* rand32 = nullptr) {
-  if (c->stage_pageable) return verify_host_pageable_locked(c, key, a, verdict_bits, reason, rand32);
   int rc = check_args(c, key, a);
   if (rc || a.n == 0) return rc;
   if (!verdict_bits) return set_err(DGPU_EINVAL, "null verdict buffer");
   hipStream_t s = c->stream;
   stream_order ord(c, s);
-  if ((rc = c->out_bits.ensure((a.n + 7) / 8)) || (rc = c->out_reason.ensure(a.n))) return rc;
-  if (rand32 && (rc = c->out_rand.ensure(a.n * 32))) return rc;
-  // (a's signature pointers are the device copies from here on)
-  if ((rc = verify_status_host_locked(c, key, a, s)) ||
-      (rc = pack_results_locked(c, a, (uint8_t*)c->out_bits.p, rand32 ? (uint8_t*)c->out_rand.p : nullptr, s)))
-    return rc;
-  HIP_TRY(hipMemcpyAsync(verdict_bits, c->out_bits.p, (a.n + 7) / 8, hipMemcpyDeviceToHost, s));
-  if (reason) HIP_TRY(hipMemcpyAsync(reason, c->status.p, a.n, hipMemcpyDeviceToHost, s));
-  if (rand32) HIP_TRY(hipMemcpyAsync(rand32, c->out_rand.p, a.n * 32, hipMemcpyDeviceToHost, s));
+  // (a's pointers are the device copies from here on; DGPU_STAGE=pageable, A/B build: the pre-ring path)
+  if (c->stage_pageable) rc = (rc = stage_inputs_locked(c, a, s)) ? rc : verify_status_locked(c, key, a, s);
+  else rc = verify_status_host_locked(c, key, a, s);
+  if (rc || (rc = results_out_locked(c, a, nullptr, verdict_bits, reason, hipMemcpyDeviceToHost, rand32, s))) return rc;
   HIP_TRY(hipStreamSynchronize(s));
-  return DGPU_OK;
-}
-
-// The pre-ring host path (whole batch staged by pageable hipMemcpyAsync, then
-// verified): kept for the A/B build's DGPU_STAGE=pageable comparison.
-int verify_host_pageable_locked(dgpu_ctx* c, const key_entry* key, verify_args a, uint8_t* verdict_bits,
-                                uint8_t* reason, uint8_t* rand32) {
-  int rc = check_args(c, key, a);
-  if (rc || a.n == 0) return rc;
-  if (!verdict_bits) return set_err(DGPU_EINVAL, "null verdict buffer");
-  hipStream_t s = c->stream;
-  stream_order ord(c, s);
-  if ((rc = stage_inputs_locked(c, a, s))) return rc;
-  if ((rc = c->out_bits.ensure((a.n + 7) / 8)) || (rc = c->out_reason.ensure(a.n))) return rc;
-  if (rand32 && (rc = c->out_rand.ensure(a.n * 32))) return rc;
-  if ((rc = verify_device_locked(c, key, a, (uint8_t*)c->out_bits.p, (uint8_t*)c->out_reason.p, s,
-                                 rand32 ? (uint8_t*)c->out_rand.p : nullptr)))
-    return rc;
-  HIP_TRY(hipMemcpyAsync(verdict_bits, c->out_bits.p, (a.n + 7) / 8, hipMemcpyDeviceToHost, s));
-  if (reason) HIP_TRY(hipMemcpyAsync(reason, c->out_reason.p, a.n, hipMemcpyDeviceToHost, s));
-  if (rand32) HIP_TRY(hipMemcpyAsync(rand32, c->out_rand.p, a.n * 32, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return DGPU_OK;
-}
-
-// The host side of a rows_src over a.n > 0 rows: the argument checks of the
-// row entry points, the staged lengths and the packed positions.
-int rows_src_init(rows_src& R, const verify_args& a, const uint8_t* base, const uint64_t* row_off,
-                  const uint32_t* row_len, size_t prev_stride, const uint64_t* keys) {
-  if (!base || !row_off || !row_len) return set_err(DGPU_EINVAL, "null row or output buffer");
-  if (a.sig_stride < (sig_on_g1(a.scheme) ? 48u : 96u)) return set_err(DGPU_EINVAL, "bad signature stride");
-  const size_t max_len = ingest_row_max_len(a.sig_stride, prev_stride);
-  if (a.sig_stride > STAGE_SLOT_BYTES || prev_stride > STAGE_SLOT_BYTES || max_len + 16 > STAGE_SLOT_BYTES)
-    return set_err(DGPU_EINVAL, "strides too large for the staging ring");
-  R.base = base, R.off = row_off, R.len = row_len, R.keys = keys;
-  R.sig_stride = a.sig_stride, R.prev_stride = prev_stride;
-  R.slen.resize(a.n);
-  R.pos.resize(a.n + 1);
-  uint64_t at = 0;
-  for (size_t i = 0; i < a.n; ++i) {
-    R.slen[i] = row_len[i] <= max_len ? row_len[i] : 0;
-    R.pos[i] = at;
-    at += R.slen[i];
-  }
-  R.pos[a.n] = at;
   return DGPU_OK;
 }
 
 // dgpu_verify_rows: verify_host_locked with the records decoded on the device
-// from the caller's stored rows; the decoder's ok flags and rounds come back
-// with the verdicts.
-int verify_rows_locked(dgpu_ctx* c, const key_entry* key, verify_args a, const uint8_t* base, const uint64_t* row_off,
-                       const uint32_t* row_len, size_t prev_stride, uint64_t* rounds_out, uint8_t* row_ok,
+// from the caller's stored rows (a.m.rows); the decoder's ok flags and rounds
+// come back with the verdicts.
+int verify_rows_locked(dgpu_ctx* c, const key_entry* key, verify_args a, uint64_t* rounds_out, uint8_t* row_ok,
                        uint8_t* verdict_bits, uint8_t* reason) {
-  verify_args a0 = a;  // scheme, mode and key before anything else (n = 0 checks no buffers)
-  a0.n = 0;
-  int rc = check_args(c, key, a0);
+  int rc = check_args(c, key, a);
   if (rc || a.n == 0) return rc;
   if (!row_ok || !verdict_bits) return set_err(DGPU_EINVAL, "null row or output buffer");
-  rows_src R{};
-  if ((rc = rows_src_init(R, a, base, row_off, row_len, prev_stride, nullptr))) return rc;
   hipStream_t s = c->stream;
   stream_order ord(c, s);
-  if ((rc = c->out_bits.ensure((a.n + 7) / 8)) || (rc = c->out_reason.ensure(a.n))) return rc;
-  if ((rc = verify_status_host_locked(c, key, a, s, &R)) ||
-      (rc = pack_results_locked(c, a, (uint8_t*)c->out_bits.p, nullptr, s)))
+  if ((rc = verify_status_host_locked(c, key, a, s)) ||
+      (rc = results_out_locked(c, a, nullptr, verdict_bits, reason, hipMemcpyDeviceToHost, nullptr, s)))
     return rc;
-  HIP_TRY(hipMemcpyAsync(verdict_bits, c->out_bits.p, (a.n + 7) / 8, hipMemcpyDeviceToHost, s));
-  if (reason) HIP_TRY(hipMemcpyAsync(reason, c->status.p, a.n, hipMemcpyDeviceToHost, s));
+  const rows_src& R = *a.m.rows;
   HIP_TRY(hipMemcpyAsync(row_ok, R.d_ok, a.n, hipMemcpyDeviceToHost, s));
   if (rounds_out) HIP_TRY(hipMemcpyAsync(rounds_out, R.d_rounds, a.n * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -2154,21 +2063,17 @@ int check_rows_args(size_t n, const uint8_t* base, const uint64_t* row_off, cons
   return DGPU_OK;
 }
 
-// dgpu_check_rows on one context (arguments checked by check_rows_args).
-int check_rows_locked(dgpu_ctx* c, const key_entry* key, verify_args a, const uint8_t* base, const uint64_t* row_off,
-                      const uint32_t* row_len, const uint64_t* keys, size_t prev_stride, uint64_t first, size_t count,
+// dgpu_check_rows on one context (arguments checked by check_rows_args; the
+// rows and their keys: a.m.rows).
+int check_rows_locked(dgpu_ctx* c, const key_entry* key, verify_args a, uint64_t first, size_t count,
                       size_t faulty_cap, size_t left_cap, check_lists& out, uint8_t* reason) {
-  verify_args a0 = a;  // scheme, mode and key (n = 0 checks no buffers)
-  a0.n = 0;
-  int rc = check_args(c, key, a0);
+  int rc = check_args(c, key, a);
   if (rc) return rc;
-  rows_src R{};
-  if (a.n && (rc = rows_src_init(R, a, base, row_off, row_len, prev_stride, keys))) return rc;
   hipStream_t s = c->stream;
   stream_order ord(c, s);
-  if (a.n && (rc = verify_status_host_locked(c, key, a, s, &R))) return rc;
+  if (a.n && (rc = verify_status_host_locked(c, key, a, s))) return rc;
   if (a.n) mark(c, s);
-  if ((rc = check_lists_locked(c, first, count, a.n, R.d_keys, faulty_cap, left_cap, out, s))) return rc;
+  if ((rc = check_lists_locked(c, first, count, a.n, a.m.rows->d_keys, faulty_cap, left_cap, out, s))) return rc;
   if (reason && a.n) {
     HIP_TRY(hipMemcpyAsync(reason, c->status.p, a.n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -2455,9 +2360,10 @@ int dgpu_verify_rows(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t pk_len, 
   int rc = get_key_locked(c, scheme, pk, pk_len, &k);
   if (rc) return rc;
   // (the record pointers are the context's buffers once the call is staged)
-  const verify_args a{scheme, n, beacon_src(nullptr, nullptr, prev_stride, nullptr, scheme == DGPU_SCHEME_CHAINED),
+  rows_src R = rows_src_of(base, row_off, row_len, nullptr, sig_stride, prev_stride);
+  const verify_args a{scheme, n, rows_records_src(&R, prev_stride, scheme == DGPU_SCHEME_CHAINED),
                       nullptr, sig_stride, nullptr, mode, rlc_seed};
-  return verify_rows_locked(c, k, a, base, row_off, row_len, prev_stride, rounds_out, row_ok, verdict_bits, reason);
+  return verify_rows_locked(c, k, a, rounds_out, row_ok, verdict_bits, reason);
 }
 
 int dgpu_faulty_rounds_device(dgpu_ctx* c, uint64_t first, size_t count, size_t n, const uint64_t* d_keys,
@@ -2492,12 +2398,11 @@ int dgpu_check_rows(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t pk_len, s
   HIP_TRY(hipSetDevice(c->device));
   key_entry* k = nullptr;
   if ((rc = get_key_locked(c, scheme, pk, pk_len, &k))) return rc;
-  const verify_args a{scheme, n, beacon_src(nullptr, nullptr, prev_stride, nullptr, scheme == DGPU_SCHEME_CHAINED),
+  rows_src R = rows_src_of(base, row_off, row_len, keys, sig_stride, prev_stride);
+  const verify_args a{scheme, n, rows_records_src(&R, prev_stride, scheme == DGPU_SCHEME_CHAINED),
                       nullptr, sig_stride, nullptr, mode, rlc_seed};
   check_lists L;
-  if ((rc = check_rows_locked(c, k, a, base, row_off, row_len, keys, prev_stride, first, count, faulty_cap, left_cap, L,
-                              reason)))
-    return rc;
+  if ((rc = check_rows_locked(c, k, a, first, count, faulty_cap, left_cap, L, reason))) return rc;
   check_lists_store(L, faulty_pos, faulty_val, faulty_cap, n_faulty, left_rows, left_cap, n_left);
   return DGPU_OK;
 }
@@ -2594,7 +2499,6 @@ int dgpu_rlc_root_bytes(int scheme) {
 static int rlc_root_pending_locked(dgpu_ctx* c, const verify_args& a, const uint8_t* pk, size_t pk_len,
                                    uint8_t* d_root, void* stream) {
   const int scheme = a.scheme;
-  const size_t n = a.n;
   HIP_TRY(hipSetDevice(c->device));
   key_entry* k = nullptr;
   int rc = get_key_locked(c, scheme, pk, pk_len, &k);
@@ -2603,21 +2507,7 @@ static int rlc_root_pending_locked(dgpu_ctx* c, const verify_args& a, const uint
   stream_order ord(c, s);
   if ((rc = check_args(c, k, a))) return rc;
   c->rlc_pending = false;
-  const rlc_geom G = rlc_geom_of(sig_on_g1(scheme));
-  if (n == 0) {
-    uint32_t inf[G2J_WORDS];
-    rlc_identity_words(G.g1, inf);
-    HIP_TRY(hipMemcpyAsync(d_root, inf, (size_t)G.jw * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_root + (size_t)G.jw * 4, inf, (size_t)G.jw * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));  // the host source goes out of scope
-  } else {
-    if ((rc = c->status.ensure(n))) return rc;
-    c->n_ev = 0;
-    c->ev_overflow = false;
-    rlc_root_layout root;
-    if ((rc = rlc_points_locked(c, a, s)) || (rc = rlc_root_msm_locked(c, a, s, c->msm_root, &root))) return rc;
-    HIP_TRY(hipMemcpyAsync(d_root, root.P, layout_bytes<rlc_root_layout>(G.jw), hipMemcpyDeviceToDevice, s));
-  }
+  if ((rc = rlc_shard_root_locked(c, a, d_root, s))) return rc;
   c->rlc_args = a;
   memcpy(c->rlc_pk, pk, pk_len);
   c->rlc_pk_len = pk_len;
@@ -2669,29 +2559,10 @@ int dgpu_rlc_finish_device(dgpu_ctx* c, size_t n_roots, const uint8_t* d_roots, 
   if (rc) return rc;
   hipStream_t s = caller_stream(stream);
   stream_order ord(c, s);
-  const rlc_geom G = rlc_geom_of(sig_on_g1(a.scheme));
-  rlc_root_layout sum, shard;  // (the shard's root: dgpu_rlc_root_device left it in msm_root)
-  if ((rc = carve(c->rlc_root, &sum, G.jw)) || (rc = carve(c->msm_root, &shard, G.jw))) return rc;
-  mark(c, s, "rlc_root_sum");
-  if (G.g1)
-    hipLaunchKernelGGL(k_rlc_sum_roots<G1Ops>, dim3(1), dim3(64), 0, s, (int)n_roots, (const uint32_t*)d_roots, sum.P,
-                       sum.S);
-  else
-    hipLaunchKernelGGL(k_rlc_sum_roots<G2Ops>, dim3(1), dim3(64), 0, s, (int)n_roots, (const uint32_t*)d_roots, sum.P,
-                       sum.S);
-  HIP_TRY(hipGetLastError());
-  std::vector<uint8_t> fail;
-  if ((rc = rlc_check_locked(c, k, std::vector<uint32_t>{0}, 1, sum.P, sum.S, s, &fail))) return rc;
-  if (a.n == 0) return DGPU_OK;
-  // this shard's verdicts, its own root first unless it is the node's (one root)
-  if (fail[0] && (rc = rlc_resolve_locked(c, k, a, s, shard, n_roots == 1))) return rc;
-  const uint8_t* st = (const uint8_t*)c->status.p;
-  mark(c, s, "pack_verdicts");
-  hipLaunchKernelGGL(k_pack_verdicts, dim3(grid_for((a.n + 7) / 8, 256)), dim3(256), 0, s, a.n, st, d_bits);
-  HIP_TRY(hipGetLastError());
-  mark(c, s);
-  if (d_reason) HIP_TRY(hipMemcpyAsync(d_reason, st, a.n, hipMemcpyDeviceToDevice, s));
-  return DGPU_OK;
+  bool fail = false;
+  if ((rc = rlc_node_check_locked(c, k, n_roots, d_roots, s, &fail)) || a.n == 0) return rc;
+  if ((rc = rlc_shard_finish_locked(c, k, a, fail, n_roots, s))) return rc;
+  return results_out_locked(c, a, d_bits, nullptr, d_reason, hipMemcpyDeviceToDevice, nullptr, s);
 }
 
 int dgpu_verify_recovered(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t pk_len, size_t n, const uint8_t* msgs,
@@ -2785,8 +2656,7 @@ int dgpu_digest_batch(dgpu_ctx* c, int scheme, size_t n, const uint64_t* rounds,
   if (chained) {
     if ((rc = c->in_prev.ensure(n * prev_stride + 1))) return rc;
     if ((rc = c->in_prev_len.ensure(n * 4))) return rc;
-    for (size_t i = 0; i < n; ++i)
-      if (prev_len[i] > prev_stride) return set_err(DGPU_EINVAL, "prev_len[%zu]=%u > prev_stride", i, prev_len[i]);
+    if ((rc = lengths_check(prev_len, n, prev_stride, PREV_LEN_FMT))) return rc;
     if (prev_stride) HIP_TRY(hipMemcpyAsync(c->in_prev.p, prev, n * prev_stride, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(c->in_prev_len.p, prev_len, n * 4, hipMemcpyHostToDevice, s));
     d_prev = (const uint8_t*)c->in_prev.p;
@@ -2805,8 +2675,7 @@ int dgpu_hash_to_curve(dgpu_ctx* c, int scheme, size_t n, const uint8_t* msgs, s
   if (!c || !msg_len || !out || (!msgs && msg_stride)) return set_err(DGPU_EINVAL, "null argument");
   if (!scheme_known(scheme)) return set_err(DGPU_EINVAL, "bad scheme %d", scheme);
   if (n == 0) return DGPU_OK;
-  for (size_t i = 0; i < n; ++i)
-    if (msg_len[i] > msg_stride) return set_err(DGPU_EINVAL, "msg_len[%zu]=%u > msg_stride", i, msg_len[i]);
+  if (int rc = lengths_check(msg_len, n, msg_stride, MSG_LEN_FMT)) return rc;
   const bool g1 = sig_on_g1(scheme);
   const size_t ob = g1 ? 48 : 96;
   std::lock_guard<std::mutex> lk(c->mu);
@@ -2861,8 +2730,7 @@ int dgpu_sign(dgpu_ctx* c, int scheme, const uint8_t* sk_be32, size_t n, const u
   if (!c || !sk_be32 || !msg_len || !out_sigs || (!msgs && msg_stride)) return set_err(DGPU_EINVAL, "null argument");
   if (!scheme_known(scheme)) return set_err(DGPU_EINVAL, "bad scheme %d", scheme);
   if (n == 0) return DGPU_OK;
-  for (size_t i = 0; i < n; ++i)
-    if (msg_len[i] > msg_stride) return set_err(DGPU_EINVAL, "msg_len[%zu]=%u > msg_stride", i, msg_len[i]);
+  if (int rc = lengths_check(msg_len, n, msg_stride, MSG_LEN_FMT)) return rc;
   const bool g1 = sig_on_g1(scheme);
   const size_t ob = g1 ? 48 : 96;
   std::lock_guard<std::mutex> lk(c->mu);

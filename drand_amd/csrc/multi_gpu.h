@@ -216,81 +216,34 @@ int multi_all_gather(dgpu_multi* m, const std::vector<const void*>& src, const s
   return DGPU_OK;
 }
 
-// status -> verdict bits / reasons of one device's shard
-int pack_shard_locked(dgpu_ctx* c, size_t cnt, uint8_t* d_bits, uint8_t* d_reason, hipStream_t s) {
-  if (cnt == 0) return DGPU_OK;
-  hipLaunchKernelGGL(k_pack_verdicts, dim3(grid_for((cnt + 7) / 8, 256)), dim3(256), 0, s, cnt,
-                     (const uint8_t*)c->status.p, d_bits);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(d_reason, c->status.p, cnt, hipMemcpyDeviceToDevice, s));
-  return DGPU_OK;
-}
-
-}  // namespace
-
-namespace {
-
 // The final statuses of device k's shard -> its verdict bits and reasons in
 // the gather buffers and (rand32: optional, the shard's rows of the caller's
 // array) the verified rounds' randomness, straight from the device to the
 // host as dgpu_recover_multi returns its signatures.  a's signature arrays
 // are the staged device copies.
 int shard_results_locked(dgpu_multi* m, int k, const verify_args& a, uint8_t* rand32) {
+  if (a.n == 0) return DGPU_OK;
   dgpu_ctx* c = m->ctx[k];
-  hipStream_t s = c->stream;
-  int rc = pack_shard_locked(c, a.n, (uint8_t*)m->buf[k].bits.p, (uint8_t*)m->buf[k].reasons.p, s);
-  if (rc || !rand32 || a.n == 0) return rc;
-  if ((rc = c->out_rand.ensure(a.n * 32))) return rc;
-  hipLaunchKernelGGL(k_randomness, dim3(grid_for(a.n, 256)), dim3(256), 0, s, a.n, a.sigs, a.sig_stride, a.sig_len,
-                     (const uint8_t*)c->status.p, (uint8_t*)c->out_rand.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(rand32, c->out_rand.p, a.n * 32, hipMemcpyDeviceToHost, s));
-  return DGPU_OK;
+  return results_out_locked(c, a, (uint8_t*)m->buf[k].bits.p, nullptr, (uint8_t*)m->buf[k].reasons.p,
+                            hipMemcpyDeviceToDevice, rand32, c->stream);
 }
 
-// The stored-row form of a multi call (dgpu_check_rows_multi): the caller's
-// rows and keys, each device's rows_src over its shard, the positions
-// [p0[k], p0[k] + pcount[k]) of the visited range device k owns, and the lists
-// each device returns (positions relative to p0[k], rows to the shard).
-struct multi_rows {
-  const uint8_t* base;
-  const uint64_t* off;
-  const uint32_t* len;
-  const uint64_t* keys;
-  size_t prev_stride;
-  uint64_t first;
-  size_t faulty_cap, left_cap;
-  std::vector<rows_src> R;
-  std::vector<uint64_t> p0;
-  std::vector<size_t> pcount;
-  std::vector<check_lists> lists;
-};
-
-// The faulty list of the positions device k owns, once its shard's statuses
-// are final (synchronises the device's stream).
-int shard_lists_locked(dgpu_multi* m, int k, const verify_args& a, multi_rows& mr) {
-  dgpu_ctx* c = m->ctx[k];
-  return check_lists_locked(c, mr.first + mr.p0[k], mr.pcount[k], a.n, mr.R[k].d_keys, mr.faulty_cap, mr.left_cap,
-                            mr.lists[k], c->stream);
-}
+inline int no_shard_done(int, const verify_args&) { return DGPU_OK; }
 
 // The multi-device verify call over host records (dgpu_verify_multi,
-// dgpu_verify_segment_multi): src_of(k, lo, hi) is the message source of
-// shard k = items [lo, hi) of the caller's arrays; everything else -- the
-// shards' signature arrays, per-device seeds, staging through each context's
-// ring, roots, gathers -- is the same for every source.
-// mr (dgpu_check_rows_multi): the records of every shard are decoded on its
-// device from the caller's stored rows (the row form of both staging
-// functions), the faulty-list stage runs on each device once its shard's
-// statuses are final, and no verdict bitmap is gathered (verdict_bits is NULL;
-// the reasons only when the caller asks for them).
-template <class SrcOf>
+// dgpu_verify_segment_multi, dgpu_check_rows_multi).  What varies per form
+// comes as callables: src_of(k, lo, hi) is the message source of shard k =
+// items [lo, hi) of the caller's arrays (a row form attaches the shard's
+// rows_src); shard_done(k, args) runs on device k's thread once a non-empty
+// shard's statuses are final (no_shard_done: nothing to add).  Everything else is the same for
+// every form.  No verdict bitmap is gathered when verdict_bits is NULL, no reasons when reason
+// is (the entry point decides whether either may be).
+template <class SrcOf, class ShardDone>
 int multi_verify(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_len, size_t n, const uint8_t* sigs,
                  size_t sig_stride, const uint32_t* sig_len, int mode, uint64_t rlc_seed, SrcOf&& src_of,
-                 uint8_t* verdict_bits, uint8_t* reason, uint8_t* rand32, multi_rows* mr = nullptr) {
+                 uint8_t* verdict_bits, uint8_t* reason, uint8_t* rand32, ShardDone&& shard_done) {
   if (!m) return set_err(DGPU_EINVAL, "null handle");
   if (n == 0) return DGPU_OK;
-  if (!verdict_bits && !mr) return set_err(DGPU_EINVAL, "null verdict buffer");
   std::lock_guard<std::mutex> mlk(m->mu);
   std::vector<std::unique_lock<std::mutex>> locks;
   for (dgpu_ctx* c : m->ctx) locks.emplace_back(c->mu);
@@ -311,16 +264,7 @@ int multi_verify(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_len, si
     args[k] = verify_args{scheme, hi - lo[k], src_of(k, lo[k], hi), sigs ? sigs + lo[k] * sig_stride : nullptr,
                           sig_stride, sig_len ? sig_len + lo[k] : nullptr, mode,
                           D > 1 ? splitmix_host(rlc_seed ^ (0x5EEDull * (uint64_t)(k + 1))) : rlc_seed};
-    if (mr) {  // (the record arrays are the context's buffers: scheme, mode and key alone, then the rows)
-      verify_args a0 = args[k];
-      a0.n = 0;
-      if ((rc = check_args(c, keys[k], a0)) ||
-          (args[k].n && (rc = rows_src_init(mr->R[k], args[k], mr->base, mr->off + lo[k], mr->len + lo[k],
-                                            mr->prev_stride, mr->keys + lo[k]))))
-        return rc;
-    } else if ((rc = check_args(c, keys[k], args[k]))) {
-      return rc;
-    }
+    if ((rc = check_args(c, keys[k], args[k]))) return rc;
     multi_bufs& b = m->buf[k];
     // (the roots: sized for either group's)
     if ((rc = b.bits.ensure(per / 8)) || (rc = b.reasons.ensure(per)) || (rc = b.all_bits.ensure(D * per / 8)) ||
@@ -330,87 +274,57 @@ int multi_verify(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_len, si
     HIP_TRY(hipStreamWaitEvent(c->stream, c->done, 0));
   }
   const bool rlc = mode == DGPU_MODE_RLC;
-  const bool g1 = sig_on_g1(scheme);
-  const int jw = g1 ? G1J_WORDS : G2J_WORDS;  // root: rlc_root_layout (P, S: stride-1 Jacobian of the signature group)
-  const size_t root_bytes = layout_bytes<rlc_root_layout>(jw);
+  // the roots: rlc_root_layout (P, S: stride-1 Jacobian of the signature group)
+  const size_t root_bytes = layout_bytes<rlc_root_layout>(sig_on_g1(scheme) ? G1J_WORDS : G2J_WORDS);
   // phase 1: stage the shard (the records of the device's shard through its
   // context's pinned ring, overlapped with the verification) and verify it
   // per round (or compute its RLC root)
   rc = for_each_device(m, [&](int k) -> int {
     dgpu_ctx* c = m->ctx[k];
     verify_args& a = args[k];
-    if (a.n == 0) return DGPU_OK;
     hipStream_t s = c->stream;
     int r;
-    if ((r = c->status.ensure(a.n))) return r;
-    c->n_ev = 0;
-    c->ev_overflow = false;
+    if (a.n && (r = c->status.ensure(a.n))) return r;  // (a staging rehearsal packs it too: DGPU_TEST_STAGE_ONLY)
     if (rlc) {  // the shard's points and its root by bucket MSM (the leaves wait for a failing root)
-      c->rlc_pending = false;  // overwrites the points a pending per-rank root (dgpu_rlc_root_device) kept
-      if ((r = stage_all_host_locked(c, a, s, mr ? &mr->R[k] : nullptr)) || (r = rlc_points_locked(c, a, s))) return r;
-      return rlc_root_msm_locked(c, a, s, c->msm_root);
+      if (a.n) {
+        c->rlc_pending = false;  // overwrites the points a pending per-rank root (dgpu_rlc_root_device) kept
+        if ((r = stage_all_host_locked(c, a, s))) return r;
+      }
+      return rlc_shard_root_locked(c, a, (uint8_t*)m->buf[k].root.p, s);  // (ensured above)
     }
+    if (a.n == 0) return DGPU_OK;
     // the shard's records through the context's pinned ring, slice by slice
     // beside the verification (verify_status_host_locked)
-    if ((r = verify_status_host_locked(c, keys[k], a, s, mr ? &mr->R[k] : nullptr)) ||
+    if ((r = verify_status_host_locked(c, keys[k], a, s)) ||
         (r = shard_results_locked(m, k, a, rand32 ? rand32 + 32 * lo[k] : nullptr)))
       return r;
-    return mr ? shard_lists_locked(m, k, a, *mr) : DGPU_OK;
+    return shard_done(k, a);
   });
   if (rc) return rc;
   if (rlc) {
-    bool all_ok = false;
-    {
-      // the per-device roots to every device; one check of their sum on device 0
-      // the identity (Z = 0) of the signature group, for empty shards
-      uint32_t inf_words[G2J_WORDS];
-      rlc_identity_words(g1, inf_words);
-      for (int k = 0; k < D; ++k) {
-        dgpu_ctx* c = m->ctx[k];
-        HIP_TRY(hipSetDevice(c->device));
-        const rlc_root_layout root = layout_at<rlc_root_layout>(m->buf[k].root.p, jw);  // (ensured above)
-        if (args[k].n == 0) {
-          HIP_TRY(hipMemcpyAsync(root.P, inf_words, (size_t)jw * 4, hipMemcpyHostToDevice, c->stream));
-          HIP_TRY(hipMemcpyAsync(root.S, inf_words, (size_t)jw * 4, hipMemcpyHostToDevice, c->stream));
-        } else {
-          HIP_TRY(hipMemcpyAsync(root.P, c->msm_root.p, root_bytes, hipMemcpyDeviceToDevice, c->stream));
-        }
-      }
-      std::vector<const void*> src(D);
-      std::vector<void*> dst(D);
-      for (int k = 0; k < D; ++k) {
-        src[k] = m->buf[k].root.p;
-        dst[k] = m->buf[k].all_roots.p;
-      }
-      if ((rc = multi_all_gather(m, src, dst, root_bytes))) return rc;
-      dgpu_ctx* c0 = m->ctx[0];
-      HIP_TRY(hipSetDevice(c0->device));
-      rlc_root_layout sum;
-      if ((rc = carve(c0->rlc_root, &sum, jw))) return rc;
-      if (g1)
-        hipLaunchKernelGGL(k_rlc_sum_roots<G1Ops>, dim3(1), dim3(64), 0, c0->stream, D,
-                           (const uint32_t*)m->buf[0].all_roots.p, sum.P, sum.S);
-      else
-        hipLaunchKernelGGL(k_rlc_sum_roots<G2Ops>, dim3(1), dim3(64), 0, c0->stream, D,
-                           (const uint32_t*)m->buf[0].all_roots.p, sum.P, sum.S);
-      HIP_TRY(hipGetLastError());
-      std::vector<uint8_t> fail;
-      if ((rc = rlc_check_locked(c0, keys[0], std::vector<uint32_t>{0}, 1, sum.P, sum.S, c0->stream, &fail)))
-        return rc;
-      all_ok = !fail[0];
+    // the per-device roots to every device; one check of their sum on device 0
+    std::vector<const void*> src(D);
+    std::vector<void*> dst(D);
+    for (int k = 0; k < D; ++k) {
+      src[k] = m->buf[k].root.p;
+      dst[k] = m->buf[k].all_roots.p;
     }
+    if ((rc = multi_all_gather(m, src, dst, root_bytes))) return rc;
+    dgpu_ctx* c0 = m->ctx[0];
+    HIP_TRY(hipSetDevice(c0->device));
+    bool fail = false;
+    if ((rc = rlc_node_check_locked(c0, keys[0], (size_t)D, (const uint8_t*)m->buf[0].all_roots.p, c0->stream, &fail)))
+      return rc;
     rc = for_each_device(m, [&](int k) -> int {
       dgpu_ctx* c = m->ctx[k];
-      const size_t cnt = args[k].n;
-      if (cnt == 0) return DGPU_OK;
+      const verify_args& a = args[k];
+      if (a.n == 0) return DGPU_OK;
       int r;
-      // this shard's verdicts, its own root first (D = 1: that root is the node's, known failing)
-      rlc_root_layout shard;  // (phase 1 left the shard's root in msm_root)
-      if (!all_ok && ((r = carve(c->msm_root, &shard, jw)) ||
-                      (r = rlc_resolve_locked(c, keys[k], args[k], c->stream, shard, D == 1))))
+      // (phase 1 left the shard's root in msm_root)
+      if ((r = rlc_shard_finish_locked(c, keys[k], a, fail, (size_t)D, c->stream)) ||
+          (r = shard_results_locked(m, k, a, rand32 ? rand32 + 32 * lo[k] : nullptr)))
         return r;
-      if ((r = shard_results_locked(m, k, args[k], rand32 ? rand32 + 32 * lo[k] : nullptr))) return r;
-      return mr ? shard_lists_locked(m, k, args[k], *mr) : DGPU_OK;
+      return shard_done(k, a);
     });
     if (rc) return rc;
   }
@@ -459,6 +373,7 @@ int dgpu_verify_multi(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_le
                       const uint8_t* sigs, size_t sig_stride, const uint32_t* sig_len, const uint8_t* prev,
                       size_t prev_stride, const uint32_t* prev_len, int mode, uint64_t rlc_seed,
                       uint8_t* verdict_bits, uint8_t* reason) {
+  if (m && n && !verdict_bits) return set_err(DGPU_EINVAL, "null verdict buffer");
   const bool chained = scheme == DGPU_SCHEME_CHAINED;
   return multi_verify(
       m, scheme, pk, pk_len, n, sigs, sig_stride, sig_len, mode, rlc_seed,
@@ -466,7 +381,7 @@ int dgpu_verify_multi(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_le
         return beacon_src(rounds + lo, chained ? prev + lo * prev_stride : nullptr, prev_stride,
                           chained ? prev_len + lo : nullptr, chained);
       },
-      verdict_bits, reason, nullptr);
+      verdict_bits, reason, nullptr, no_shard_done);
 }
 
 // The linked form over the node: shard 0 is dgpu_verify_segment's source (the
@@ -481,6 +396,7 @@ int dgpu_verify_segment_multi(dgpu_multi* m, int scheme, const uint8_t* pk, size
   if (rc) return rc;
   const bool chained = scheme == DGPU_SCHEME_CHAINED;
   if (n && (!sigs || !sig_len)) return set_err(DGPU_EINVAL, "bad signature buffers");
+  if (m && n && !verdict_bits) return set_err(DGPU_EINVAL, "null verdict buffer");
   return multi_verify(
       m, scheme, pk, pk_len, n, sigs, sig_stride, sig_len, mode, rlc_seed,
       [&](int, size_t lo, size_t hi) {
@@ -489,7 +405,7 @@ int dgpu_verify_segment_multi(dgpu_multi* m, int scheme, const uint8_t* pk, size
           return linked_src(first_round, s_lo, sig_stride, sig_len + lo, seed_prev, seed_prev_len, chained);
         return halo_src(first_round + lo, s_lo, sig_stride, sig_len + lo, s_lo - sig_stride, sig_len + lo - 1, chained);
       },
-      verdict_bits, reason, randomness32);
+      verdict_bits, reason, randomness32, no_shard_done);
 }
 
 // dgpu_check_rows over the node.  The rows shard like every batch here; the
@@ -514,27 +430,42 @@ int dgpu_check_rows_multi(dgpu_multi* m, int scheme, const uint8_t* pk, size_t p
                            left_rows, left_cap, n_left);
   if (rc) return rc;
   const int D = m->ndev;
-  multi_rows mr{base, row_off, row_len, keys, prev_stride, first, faulty_cap, left_cap, {}, {}, {}, {}};
-  mr.R.resize(D), mr.p0.assign(D, 0), mr.pcount.assign(D, 0), mr.lists.resize(D);
+  // each device's rows_src over its shard, the positions [p0[k], p0[k] + pcount[k])
+  // of the visited range device k owns, and the lists each device returns
+  // (positions relative to p0[k], rows to the shard)
+  std::vector<rows_src> R(D);
+  std::vector<uint64_t> p0(D, 0);
+  std::vector<size_t> pcount(D, 0);
+  std::vector<check_lists> lists(D);
   std::vector<size_t> lo(D), hi(D);
   for (int k = 0; k < D; ++k) dgpu_shard_range(n, D, k, &lo[k], &hi[k]);
   for (int k = 0; k < D; ++k) {
     if (lo[k] == hi[k]) continue;  // (the non-empty shards are the first ones)
-    mr.p0[k] = k ? keys[lo[k]] - first : 0;
+    p0[k] = k ? keys[lo[k]] - first : 0;
     const bool last = k + 1 == D || lo[k + 1] == hi[k + 1];
-    mr.pcount[k] = (size_t)((last ? (uint64_t)count : keys[lo[k + 1]] - first) - mr.p0[k]);
+    pcount[k] = (size_t)((last ? (uint64_t)count : keys[lo[k + 1]] - first) - p0[k]);
   }
   const bool chained = scheme == DGPU_SCHEME_CHAINED;
+  // No verdict bitmap: the lists are the result.  shard_done: the faulty list of the positions
+  // device k owns, once its shard's statuses are final (synchronises the device's stream).
   rc = multi_verify(
       m, scheme, pk, pk_len, n, nullptr, sig_stride, nullptr, mode, rlc_seed,
-      [&](int, size_t, size_t) { return beacon_src(nullptr, nullptr, prev_stride, nullptr, chained); }, nullptr, reason,
-      nullptr, &mr);
+      [&](int k, size_t lo_k, size_t) {
+        R[k] = rows_src_of(base, row_off + lo_k, row_len + lo_k, keys + lo_k, sig_stride, prev_stride);
+        return rows_records_src(&R[k], prev_stride, chained);
+      },
+      nullptr, reason, nullptr,
+      [&](int k, const verify_args& a) {
+        dgpu_ctx* c = m->ctx[k];
+        return check_lists_locked(c, first + p0[k], pcount[k], a.n, a.m.rows->d_keys, faulty_cap, left_cap,
+                                  lists[k], c->stream);
+      });
   if (rc) return rc;
   check_lists all;
   for (int k = 0; k < D; ++k) {
-    const check_lists& L = mr.lists[k];
+    const check_lists& L = lists[k];
     all.n_faulty += L.n_faulty, all.n_left += L.n_left;
-    for (size_t i = 0; i < L.pos.size(); ++i) all.pos.push_back(L.pos[i] + mr.p0[k]), all.val.push_back(L.val[i]);
+    for (size_t i = 0; i < L.pos.size(); ++i) all.pos.push_back(L.pos[i] + p0[k]), all.val.push_back(L.val[i]);
     for (uint64_t r : L.left) all.left.push_back(r + lo[k]);
   }
   check_lists_store(all, faulty_pos, faulty_val, faulty_cap, n_faulty, left_rows, left_cap, n_left);
