@@ -278,6 +278,8 @@ struct dgpu_ctx {
   bool test_stage_only = false;   // A/B build, DGPU_TEST_STAGE_ONLY=1: host-record calls stage and stop (staging rehearsal)
   size_t last_stage_bytes = 0;
   bool kb_pair = false;          // A/B: DGPU_KB_PAIR=1, the Karabina chain on two lanes per round (k_kb_chain_pair)
+  bool reduce_norm = false;      // A/B: DGPU_REDUCE_NORM=1, k_kb_chain_thr and k_lines_thr with the carried form of
+                                 // fp_reduce_lz (fp.cuh; the form before profiles/r15)
   bool lines_wave = false;       // A/B: DGPU_LINES_WAVE=1, k_lines_thr with a pair per wave (G1 point in SGPRs;
                                  // spills 280 -> 226 but 1.5% slower, r06f)
   int eng_xw = 0;                // 16-group 192-thread engine blocks (no idle lanes): bit 0 the Miller loop
@@ -529,6 +531,12 @@ int eng_fe_kb_locked(dgpu_ctx* c, const uint32_t* consts, size_t cnt, size_t cap
       const bool norm_pre = kb_thread && c->kb_norm_chain;
       if (norm_pre && c->kb_pair)  // two lanes per round
         hipLaunchKernelGGL(k_kb_chain_pair<true>, dim3(grid_for(2 * cnt, 256)), dim3(256), 0, s, cnt, xbuf, ebuf);
+#ifdef DG_AB_KNOBS
+      else if (kb_thread && c->reduce_norm && norm_pre)
+        hipLaunchKernelGGL((k_kb_chain_thr<true, false>), dim3(grid_for(cnt, 256)), dim3(256), 0, s, cnt, xbuf, ebuf);
+      else if (kb_thread && c->reduce_norm)
+        hipLaunchKernelGGL((k_kb_chain_thr<false, false>), dim3(grid_for(cnt, 256)), dim3(256), 0, s, cnt, xbuf, nullptr);
+#endif
       else if (norm_pre)
         hipLaunchKernelGGL(k_kb_chain_thr<true>, dim3(grid_for(cnt, 256)), dim3(256), 0, s, cnt, xbuf, ebuf);
       else if (kb_thread)
@@ -672,6 +680,11 @@ int eng_pairing_locked(dgpu_ctx* c, const pairing_job& job, hipStream_t s) {
           hipLaunchKernelGGL(k_lines_thr<true>, dim3(grid_for(2 * ((cnt + 63) / 64 * 64), 256)), dim3(256), 0, s, n, r0,
                              cnt, h, h_stride, h_idx, sg, pk_items, consts, lines,
                              sig_subgroup ? st : (uint8_t*)nullptr);
+#ifdef DG_AB_KNOBS
+        else if (c->lines_thread && cnt >= c->thr_min && c->reduce_norm)
+          hipLaunchKernelGGL((k_lines_thr<false, false>), dim3(grid_for(2 * cnt, 256)), dim3(256), 0, s, n, r0, cnt, h,
+                             h_stride, h_idx, sg, pk_items, consts, lines, sig_subgroup ? st : (uint8_t*)nullptr);
+#endif
         else if (c->lines_thread && cnt >= c->thr_min)
           hipLaunchKernelGGL(k_lines_thr<false>, dim3(grid_for(2 * cnt, 256)), dim3(256), 0, s, n, r0, cnt, h, h_stride,
                              h_idx, sg, pk_items, consts, lines, sig_subgroup ? st : (uint8_t*)nullptr);
@@ -2192,6 +2205,8 @@ int dgpu_open(int device, dgpu_ctx** out) {
   if (ktf && atol(ktf) >= 1) c->kb_test_flag = (size_t)atol(ktf);
   const char* kpv = getenv("DGPU_KB_PAIR");
   if (kpv) c->kb_pair = !strcmp(kpv, "1");
+  const char* rnv = getenv("DGPU_REDUCE_NORM");
+  if (rnv) c->reduce_norm = !strcmp(rnv, "1");
   const char* lwv = getenv("DGPU_LINES_WAVE");
   if (lwv) c->lines_wave = !strcmp(lwv, "1");
   const char* xwv = getenv("DGPU_ENG_XW");

@@ -621,11 +621,11 @@ DG_FN g1j g1_dbl_body(const g1j& p) {
   const fp A = fp_sqr(p.x);
   const fp XB = fp_norm(fp_add_lz(p.x, B));
   const fp C = fp_sqr(B);
-  const fp Dh = fp_reduce(fp_norm(fp_sub2_lz(fp_sqr(XB), fp_add_lz(A, C))));
+  const fp Dh = fp_reduce_lz(fp_sub2_lz(fp_sqr(XB), fp_add_lz(A, C)));  // limbs < 2^31, value < 33.1p: inside fp_reduce_lz
   const fp E = fp_norm(fp_add_lz(fp_add_lz(A, A), A));
-  r.x = fp_reduce(fp_norm(fp_sub2_lz(fp_sqr(E), fp_norm(fp_mulk_lz(Dh, 4)))));
+  r.x = fp_reduce_lz(fp_sub2_lz(fp_sqr(E), fp_norm(fp_mulk_lz(Dh, 4))));  // limbs < 2^31, value < 33.1p: inside fp_reduce_lz
   const fp DX = fp_norm(fp_sub_lz(fp_add_lz(Dh, Dh), r.x));
-  r.y = fp_reduce(fp_norm(fp_sub2_lz(fp_mul(E, DX), fp_norm(fp_mulk_lz(C, 8)))));
+  r.y = fp_reduce_lz(fp_sub2_lz(fp_mul(E, DX), fp_norm(fp_mulk_lz(C, 8))));  // likewise
   return r;
 }
 
@@ -650,7 +650,8 @@ DG_FN g1j g1_add_body(const g1j& p, const g1j& q) {
   const fp j = fp_mul(h, i);
   const fp v = fp_mul(u1, i);
   g1j r;
-  r.x = fp_reduce(fp_norm(fp_sub2_lz(fp_sqr(rr), fp_norm(fp_add_lz(fp_add_lz(j, v), v)))));
+  // limbs < 2^31, value < 33.1p: inside fp_reduce_lz
+  r.x = fp_reduce_lz(fp_sub2_lz(fp_sqr(rr), fp_norm(fp_add_lz(fp_add_lz(j, v), v))));
   const fp VX = fp_norm(fp_sub_lz(v, r.x));
   r.y = fp_sub(fp_mul(rr, VX), fp_mul(fp_add_lz(s1, s1), j));
   r.z = fp_mul(fp_norm(fp_sub2_lz(fp_sqr(fp_norm(fp_add_lz(p.z, q.z))), fp_add_lz(z1z1, z2z2))), h);  // 66.6 p^2
@@ -681,10 +682,11 @@ DG_FN g1j g1_add_affine_body(const g1j& p, const g1a& q) {
   const fp j = fp_mul(h, i);
   const fp v = fp_mul(p.x, i);
   g1j r;
-  r.x = fp_reduce(fp_norm(fp_sub2_lz(fp_sqr(rr), fp_norm(fp_add_lz(fp_add_lz(j, v), v)))));
+  // limbs < 2^31, value < 33.1p (both): inside fp_reduce_lz
+  r.x = fp_reduce_lz(fp_sub2_lz(fp_sqr(rr), fp_norm(fp_add_lz(fp_add_lz(j, v), v))));
   const fp VX = fp_norm(fp_sub_lz(v, r.x));
   r.y = fp_sub(fp_mul(rr, VX), fp_mul(fp_add_lz(p.y, p.y), j));
-  r.z = fp_reduce(fp_norm(fp_sub2_lz(fp_sqr(fp_norm(fp_add_lz(p.z, h))), fp_add_lz(z1z1, hh))));
+  r.z = fp_reduce_lz(fp_sub2_lz(fp_sqr(fp_norm(fp_add_lz(p.z, h))), fp_add_lz(z1z1, hh)));
   if (h0 && !p_inf) r = r0 ? g1_dbl(g1j{q.x, q.y, fp_one()}) : g1_infinity();
   if (p_inf) r = g1j{q.x, q.y, fp_one()};
   return r;

@@ -257,6 +257,34 @@ DG_FN fp fp_mul(const fp& a, const fp& b) { return fp_mul_r(DG_LIMB_ARGS(a), DG_
 DG_FN fp fp_sqr(const fp& a) { return fp_sqr_r(DG_LIMB_ARGS(a)); }
 DG_FN fp fp_reduce(const fp& a) { return fp_reduce_r(DG_LIMB_ARGS(a)); }
 
+// Lazy value -> CI without the carry pass in front: fp_reduce(fp_norm(a)) up
+// to the choice of representative.  Input: any limbs < 2^32, value < 2^392.
+// fp_reduce_r's own pass already carries in signed 64-bit arithmetic
+// (|a_i - q P_i + c| < 2^32 + 2^44), so unnormalized limbs only change the
+// quotient estimate q = floor(a_13 / PTOP1), taken before the low limbs'
+// carries reach the top limb.  Those carries are < 17 units of 2^364
+// (sum_{i<13} 2^32 2^(28 i) < 16.01 x 2^364), so with a_13 = q PTOP1 + r:
+//   q p < q PTOP1 2^364 <= a_13 2^364 <= value            (result >= 0)
+//   value - q p < (q + r + 17) 2^364 <= (q + PTOP1 + 16) 2^364 < 1.03p
+// (q < 2^28 / PTOP1 < 2521, PTOP1 = 106,514 units per p): q is the
+// normalized form's or one less (about 2^-12 of inputs), and the result is CI.
+// The top-limb line is exact and cannot wrap: it is the top limb of a value in
+// [0, 1.03p), below 2^28.
+// LZ = false (DG_REDUCE_NORM, and the A/B build's DGPU_REDUCE_NORM kernels) is
+// the carried form, kept for comparison (profiles/r15).
+#ifdef DG_REDUCE_NORM
+#define DG_LZ_FORM false
+#else
+#define DG_LZ_FORM true
+#endif
+template <bool LZ = DG_LZ_FORM>
+DG_FN fp fp_reduce_lz(const fp& a) {
+  if constexpr (LZ)
+    return fp_reduce_r(DG_LIMB_ARGS(a));
+  else
+    return fp_reduce(fp_norm(a));
+}
+
 // ---------------------------------------------------------------- lazy add/sub
 DG_FN fp fp_add_lz(const fp& a, const fp& b) {
   fp r;
@@ -282,10 +310,23 @@ DG_FN fp fp_sub2_lz(const fp& a, const fp& b) {
 }
 
 // ---------------------------------------------------------------- safe ops (CI in, CI out)
-DG_FN fp fp_add(const fp& a, const fp& b) { return fp_reduce(fp_norm(fp_add_lz(a, b))); }
-DG_FN fp fp_sub(const fp& a, const fp& b) { return fp_reduce(fp_norm(fp_sub_lz(a, b))); }
-DG_FN fp fp_neg(const fp& a) { return fp_sub(fp_zero(), a); }
-DG_FN fp fp_dbl(const fp& a) { return fp_add(a, a); }
+// limbs < 2^29, value < 4.02p (add) / limbs < 2^29.6, value < 10.01p (sub): inside fp_reduce_lz
+template <bool LZ = DG_LZ_FORM>
+DG_FN fp fp_add(const fp& a, const fp& b) {
+  return fp_reduce_lz<LZ>(fp_add_lz(a, b));
+}
+template <bool LZ = DG_LZ_FORM>
+DG_FN fp fp_sub(const fp& a, const fp& b) {
+  return fp_reduce_lz<LZ>(fp_sub_lz(a, b));
+}
+template <bool LZ = DG_LZ_FORM>
+DG_FN fp fp_neg(const fp& a) {
+  return fp_sub<LZ>(fp_zero(), a);
+}
+template <bool LZ = DG_LZ_FORM>
+DG_FN fp fp_dbl(const fp& a) {
+  return fp_add<LZ>(a, a);
+}
 
 // a / 2 mod p.  a CI.  If odd add p (value < 3.01p), then shift right.
 DG_NOINL fp fp_half(fp a) {

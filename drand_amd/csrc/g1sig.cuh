@@ -46,10 +46,11 @@ DG_FN void iso11_hom4(const fp& N, const fp& D, fp& xn, fp& xd, fp& yn, fp& yd) 
     a2 = fp_add_lz(fp_mul(a2, N), fp_mul(fp_row(ISO11_YNUM, 15 - st), dk));
     a3 = fp_add_lz(fp_mul(a3, N), fp_mul(fp_row(ISO11_YDEN, 15 - st), dk));
   }
-  xn = fp_reduce(fp_norm(a0));
-  xd = fp_reduce(fp_norm(a1));
-  yn = fp_reduce(fp_norm(a2));
-  yd = fp_reduce(fp_norm(a3));
+  // limbs < 2^29, value < 2.02p: inside fp_reduce_lz
+  xn = fp_reduce_lz(a0);
+  xd = fp_reduce_lz(a1);
+  yn = fp_reduce_lz(a2);
+  yd = fp_reduce_lz(a3);
 }
 
 // Simplified SWU on E1' (Z = 11) fused with the 11-isogeny to E1, inversion

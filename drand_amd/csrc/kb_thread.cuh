@@ -29,15 +29,39 @@ namespace dgpu {
 //   tripled plus 2 f (< 103.4p) -> CI; the xi-twisted one reduced to CI first
 //   (xi needs its subtrahend < 7.99p), xi applied lazily and carried
 //   (< 10.01p), tripled plus 2 f1 (< 34.1p) -> CI.
+// The outputs' limbs are < 3 (2^28) + 0x30000000 (minus) or 5 (2^28) (plus),
+// < 2^31, values < 65.3p, 103.4p, 34.1p and (xi cross, below) 133p, 203p:
+// inside fp_reduce_lz.
+// LZ: the form of that last reduction (fp.cuh).
+template <bool LZ = DG_LZ_FORM>
 DG_FN fp kb_t_out(const fp& x3, const fp& f, bool minus) {
   fp t = fp_add_lz(fp_add_lz(x3, x3), x3);
-  return fp_reduce(fp_norm(minus ? fp_sub2_lz(t, fp_add_lz(f, f)) : fp_add_lz(t, fp_add_lz(f, f))));
+  return fp_reduce_lz<LZ>(minus ? fp_sub2_lz(t, fp_add_lz(f, f)) : fp_add_lz(t, fp_add_lz(f, f)));
 }
-DG_FN fp2 kb_t_qsum(const fp2& xx, const fp2& yy) {  // xx + xi yy, carried
-  return fp2{fp_norm(fp_add_lz(xx.c0, fp_sub_lz(yy.c0, yy.c1))), fp_norm(fp_add_lz(xx.c1, fp_add_lz(yy.c0, yy.c1)))};
+// With LZ the sum and the plain cross keep their lazy limbs: fp_reduce_lz needs
+// no carried input, and kb_t_out's 32-bit sums still fit:
+//   qsum limbs < 2 (2^28) + 0x1ffd5558 = 0x3ffd5558, tripled 0xbff80008, plus
+//   0x2ff55560 (the minus form's 32p) < 0xefed5568;
+//   cross limbs < 2^28 + 0x2ff55560 = 0x3ff55560, tripled 0xbfe00020, plus
+//   2 f (< 2^29) < 0xdfe00020
+// (values as above).  The xi cross's limbs reach 2^31, so it keeps its carry
+// in front of the tripling.
+template <bool LZ = DG_LZ_FORM>
+DG_FN fp kb_t_carry(const fp& a) {
+  if constexpr (LZ)
+    return a;
+  else
+    return fp_norm(a);
 }
-DG_FN fp2 kb_t_cross(const fp2& ss, const fp2& xx, const fp2& yy) {  // ss - xx - yy, carried
-  return fp2{fp_norm(fp_sub2_lz(ss.c0, fp_add_lz(xx.c0, yy.c0))), fp_norm(fp_sub2_lz(ss.c1, fp_add_lz(xx.c1, yy.c1)))};
+template <bool LZ = DG_LZ_FORM>
+DG_FN fp2 kb_t_qsum(const fp2& xx, const fp2& yy) {  // xx + xi yy
+  return fp2{kb_t_carry<LZ>(fp_add_lz(xx.c0, fp_sub_lz(yy.c0, yy.c1))),
+             kb_t_carry<LZ>(fp_add_lz(xx.c1, fp_add_lz(yy.c0, yy.c1)))};
+}
+template <bool LZ = DG_LZ_FORM>
+DG_FN fp2 kb_t_cross(const fp2& ss, const fp2& xx, const fp2& yy) {  // ss - xx - yy
+  return fp2{kb_t_carry<LZ>(fp_sub2_lz(ss.c0, fp_add_lz(xx.c0, yy.c0))),
+             kb_t_carry<LZ>(fp_sub2_lz(ss.c1, fp_add_lz(xx.c1, yy.c1)))};
 }
 
 // xi (2 f2 f5) = xi ((f2 + f5)^2 - f2^2 - f5^2) straight from the six product
@@ -56,24 +80,25 @@ DG_FN fp2 kb_t_xi_cross(const fp2& s, const fp2& c2, const fp2& c5) {
   return fp2{fp_norm(re), fp_norm(im)};
 }
 
+template <bool LZ = DG_LZ_FORM>
 DG_FN void kb_sqr_thr(fp2& f1, fp2& f2, fp2& f4, fp2& f5) {
   // C side: f1' and f4' (they need the old f1, f4, which the B side squares)
   fp2 n1, n4;
   {
     const fp2 c2 = fp2_sqr(f2), c5 = fp2_sqr(f5);
     const fp2 c25 = fp2_sqr(fp2_carry(fp2_add_lz(f2, f5)));
-    const fp2 q = kb_t_qsum(c2, c5);
-    n4 = fp2{kb_t_out(q.c0, f4.c0, true), kb_t_out(q.c1, f4.c1, true)};
+    const fp2 q = kb_t_qsum<LZ>(c2, c5);
+    n4 = fp2{kb_t_out<LZ>(q.c0, f4.c0, true), kb_t_out<LZ>(q.c1, f4.c1, true)};
     const fp2 xx = kb_t_xi_cross(c25, c2, c5);
-    n1 = fp2{kb_t_out(xx.c0, f1.c0, false), kb_t_out(xx.c1, f1.c1, false)};
+    n1 = fp2{kb_t_out<LZ>(xx.c0, f1.c0, false), kb_t_out<LZ>(xx.c1, f1.c1, false)};
   }
   // B side: f2' and f5'
   const fp2 a1 = fp2_sqr(f1), a4 = fp2_sqr(f4);
   const fp2 a14 = fp2_sqr(fp2_carry(fp2_add_lz(f1, f4)));
-  const fp2 q = kb_t_qsum(a1, a4);
-  f2 = fp2{kb_t_out(q.c0, f2.c0, true), kb_t_out(q.c1, f2.c1, true)};
-  const fp2 x = kb_t_cross(a14, a1, a4);
-  f5 = fp2{kb_t_out(x.c0, f5.c0, false), kb_t_out(x.c1, f5.c1, false)};
+  const fp2 q = kb_t_qsum<LZ>(a1, a4);
+  f2 = fp2{kb_t_out<LZ>(q.c0, f2.c0, true), kb_t_out<LZ>(q.c1, f2.c1, true)};
+  const fp2 x = kb_t_cross<LZ>(a14, a1, a4);
+  f5 = fp2{kb_t_out<LZ>(x.c0, f5.c0, false), kb_t_out<LZ>(x.c1, f5.c1, false)};
   f1 = n1;
   f4 = n4;
 }
@@ -95,7 +120,7 @@ DG_FN void kb_pair_send(const fp2& x, const fp2& y, bool c, fp2& q, fp2& k) {
 }
 DG_FN fp kb_t_out_sel(const fp& x3, const fp& f, bool minus) {
   const fp t = fp_add_lz(fp_add_lz(x3, x3), x3), f2 = fp_add_lz(f, f);
-  return fp_reduce(fp_norm(fp_cmov(fp_add_lz(t, f2), fp_sub2_lz(t, f2), minus)));
+  return fp_reduce_lz(fp_cmov(fp_add_lz(t, f2), fp_sub2_lz(t, f2), minus));  // kb_t_out's bounds
 }
 DG_FN void kb_pair_recv(fp2& x, fp2& y, bool c, const fp2& rq, const fp2& rk) {
   const fp2 ax{fp_cmov(rk.c0, rq.c0, c), fp_cmov(rk.c1, rq.c1, c)};
@@ -106,14 +131,14 @@ DG_FN void kb_pair_recv(fp2& x, fp2& y, bool c, const fp2& rq, const fp2& rk) {
 
 // 63 compressed squarings of (f1, f2, f4, f5); snap(j, f1, f2, f4, f5) after
 // s = 16, 48, 57, 60, 62, 63 of them (sum of 2^s = |x|).
-template <class Snap>
+template <bool LZ = DG_LZ_FORM, class Snap>
 DG_FN void kb_chain_thr(fp2 f1, fp2 f2, fp2 f4, fp2 f5, Snap&& snap) {
   int s = 0;
 #pragma unroll 1
   for (int j = 0; j < 6; ++j) {
     const int sj = j == 0 ? 16 : j == 1 ? 48 : j == 2 ? 57 : j == 3 ? 60 : j == 4 ? 62 : 63;
 #pragma unroll 1
-    for (; s < sj; ++s) kb_sqr_thr(f1, f2, f4, f5);
+    for (; s < sj; ++s) kb_sqr_thr<LZ>(f1, f2, f4, f5);
     snap(j, f1, f2, f4, f5);
   }
 }
@@ -141,12 +166,13 @@ __device__ __forceinline__ void kb_st_thr(uint32_t* xbuf, size_t i, int plane, i
 // -> nbuf ([j][limb][cnt], round-fastest, coalesced), so k_eng_kb_norm_pre
 // reads 6 x 56 B per round instead of the values' f1 halves from the blocked
 // planes.
-template <bool NORM>
+// LZ: fp_reduce_lz's form in the outputs (false only in the A/B build: DGPU_REDUCE_NORM).
+template <bool NORM, bool LZ = DG_LZ_FORM>
 __global__ void __launch_bounds__(256, DG_KB_THR_OCC) k_kb_chain_thr(size_t cnt, uint32_t* __restrict__ xbuf,
                                                                      uint32_t* __restrict__ nbuf) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= cnt) return;
-  kb_chain_thr(kb_ld_thr(xbuf, i, ENG_KB_PL_M, 2), kb_ld_thr(xbuf, i, ENG_KB_PL_M, 4),
+  kb_chain_thr<LZ>(kb_ld_thr(xbuf, i, ENG_KB_PL_M, 2), kb_ld_thr(xbuf, i, ENG_KB_PL_M, 4),
                kb_ld_thr(xbuf, i, ENG_KB_PL_M, 8), kb_ld_thr(xbuf, i, ENG_KB_PL_M, 10),
                [&](int j, const fp2& f1, const fp2& f2, const fp2& f4, const fp2& f5) {
                  const int pl = ENG_KB_PL_X0 + j;

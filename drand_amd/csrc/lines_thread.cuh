@@ -59,7 +59,8 @@ struct lt_pt_val {
 // (The doubling's T.x and T.z with their first coefficient only normalized,
 // two reductions fewer, measured without gain: profiles/r06/
 // r06s_lines_dbl_c1r_ab.txt; the code is in git history.)
-template <class PT, class Emit>
+// LZ: the form of the reductions inside (fp_reduce_lz, fp.cuh).
+template <bool LZ = DG_LZ_FORM, class PT, class Emit>
 DG_FN void lt_dbl_p(g2p& T, const PT& P, Emit&& emit) {
   const fp nxp = P.nx();
   const fp2 t0 = fp2_sqr(T.y);
@@ -70,34 +71,35 @@ DG_FN void lt_dbl_p(g2p& T, const PT& P, Emit&& emit) {
   const fp2 yz2 = lt_sub32_nr(fp2_sqr(fp2_carry(fp2_add_lz(T.y, T.z))), fp2_add_lz(t0, t1));
   emit(2, fp2_mul_fp(yz2, P.y()));
   const fp2 xt1 = fp2_carry(fp2{fp_sub_lz(t1.c0, t1.c1), fp_add_lz(t1.c0, t1.c1)});
-  const fp2 t2 = fp2{fp_reduce(fp_norm(fp2_mulk_lz(xt1, 12).c0)), fp_reduce(fp_norm(fp2_mulk_lz(xt1, 12).c1))};
-  emit(0, fp2_sub(t0, t2));
-  T.z = fp2_mul(fp2_carry(fp2_mulk_lz(t0, 4)), yz2);
+  // limbs < 12 (2^28) < 2^32, value < 120.2p: inside fp_reduce_lz
+  const fp2 t2 = fp2{fp_reduce_lz<LZ>(fp2_mulk_lz(xt1, 12).c0), fp_reduce_lz<LZ>(fp2_mulk_lz(xt1, 12).c1)};
+  emit(0, fp2_sub<LZ>(t0, t2));
+  T.z = fp2_mul<LZ>(fp2_carry(fp2_mulk_lz(t0, 4)), yz2);
   const fp2 t3 = fp2_carry(fp2_add_lz(fp2_add_lz(t2, t2), t2));
-  T.x = fp2_mul(xy2, fp2_carry(fp2{fp_sub_lz(t0.c0, t3.c0), fp_sub_lz(t0.c1, t3.c1)}));
+  T.x = fp2_mul<LZ>(xy2, fp2_carry(fp2{fp_sub_lz(t0.c0, t3.c0), fp_sub_lz(t0.c1, t3.c1)}));
   const fp2 t2sq = fp2_sqr(t2);
-  T.y = fp2_sub32(fp2_sqr(fp2_carry(fp2_add_lz(t0, t3))), fp2_carry(fp2_mulk_lz(t2sq, 12)));
+  T.y = fp2_sub32<LZ>(fp2_sqr(fp2_carry(fp2_add_lz(t0, t3))), fp2_carry(fp2_mulk_lz(t2sq, 12)));
 }
 
 // Mixed addition T + Q (Q affine) with its chord line (pairing.cuh
 // miller_add_step's formulas; 5 of the 68 steps), coefficients emitted early.
-template <class PT, class Emit>
+template <bool LZ = DG_LZ_FORM, class PT, class Emit>
 DG_FN void lt_add_p(g2p& T, const g2a& Q, const PT& P, Emit&& emit) {
-  const fp2 theta = fp2_sub(T.y, fp2_mul(Q.y, T.z));
-  const fp2 lam = fp2_sub(T.x, fp2_mul(Q.x, T.z));
+  const fp2 theta = fp2_sub<LZ>(T.y, fp2_mul<LZ>(Q.y, T.z));
+  const fp2 lam = fp2_sub<LZ>(T.x, fp2_mul<LZ>(Q.x, T.z));
   emit(1, fp2_mul_fp(theta, P.nx()));
   emit(2, fp2_mul_fp(lam, P.y()));
-  emit(0, fp2_sub(fp2_mul(theta, Q.x), fp2_mul(lam, Q.y)));
+  emit(0, fp2_sub<LZ>(fp2_mul<LZ>(theta, Q.x), fp2_mul<LZ>(lam, Q.y)));
   const fp2 C = fp2_sqr(theta);
   const fp2 D = fp2_sqr(lam);
-  const fp2 E = fp2_mul(lam, D);
-  const fp2 F = fp2_mul(T.z, C);
-  const fp2 G = fp2_mul(T.x, D);
-  const fp2 H = fp2_sub(fp2_add(E, F), fp2_dbl(G));
-  const fp2 ye = fp2_mul(T.y, E);
-  T.x = fp2_mul(lam, H);
-  T.y = fp2_sub(fp2_mul(theta, fp2_sub(G, H)), ye);
-  T.z = fp2_mul(T.z, E);
+  const fp2 E = fp2_mul<LZ>(lam, D);
+  const fp2 F = fp2_mul<LZ>(T.z, C);
+  const fp2 G = fp2_mul<LZ>(T.x, D);
+  const fp2 H = fp2_sub<LZ>(fp2_add<LZ>(E, F), fp2_dbl<LZ>(G));
+  const fp2 ye = fp2_mul<LZ>(T.y, E);
+  T.x = fp2_mul<LZ>(lam, H);
+  T.y = fp2_sub<LZ>(fp2_mul<LZ>(theta, fp2_sub<LZ>(G, H)), ye);
+  T.z = fp2_mul<LZ>(T.z, E);
 }
 
 // The same steps returning the whole line (host emulation, tests).
@@ -121,17 +123,17 @@ struct lt_q_val {
   DG_FN g2a get() const { return q; }
 };
 
-template <class QT, class PT, class Emit>
+template <bool LZ = DG_LZ_FORM, class QT, class PT, class Emit>
 DG_FN g2p lt_pair_p(const QT& Qs, const PT& P, Emit&& emit) {
   const g2a Q0 = Qs.get();
   g2p T{Q0.x, Q0.y, fp2_one()};
   int step = 0;
 #pragma unroll 1
   for (int i = 62; i >= 0; --i) {
-    lt_dbl_p(T, P, [&](int k, const fp2& v) { emit(step, k, v); });
+    lt_dbl_p<LZ>(T, P, [&](int k, const fp2& v) { emit(step, k, v); });
     ++step;
     if ((BLS_X_ABS >> i) & 1ull) {
-      lt_add_p(T, Qs.get(), P, [&](int k, const fp2& v) { emit(step, k, v); });
+      lt_add_p<LZ>(T, Qs.get(), P, [&](int k, const fp2& v) { emit(step, k, v); });
       ++step;
     }
   }
@@ -181,7 +183,8 @@ namespace dgpu {
 // the pair's G1 point -- the key or -g1, the same for every lane -- is
 // wave-uniform and lives in scalar registers (readfirstlane), off the T-step
 // loop's VGPR budget.
-template <bool WAVE>
+// LZ: fp_reduce_lz's form in the T-steps (false only in the A/B build: DGPU_REDUCE_NORM).
+template <bool WAVE, bool LZ = DG_LZ_FORM>
 __global__ void __launch_bounds__(256, DG_LINES_OCC) k_lines_thr(size_t n, size_t r0, size_t cnt,
                                                                  const uint32_t* __restrict__ h_pts, size_t h_stride,
                                                                  const uint32_t* __restrict__ h_idx,
@@ -257,7 +260,7 @@ __global__ void __launch_bounds__(256, DG_LINES_OCC) k_lines_thr(size_t n, size_
     }
   }
 #endif
-  const g2p T = lt_pair_p(Qs, P, [&](int step, int k, const fp2& v) {
+  const g2p T = lt_pair_p<LZ>(Qs, P, [&](int step, int k, const fp2& v) {
     uint2* b = reinterpret_cast<uint2*>(base + (size_t)step * FP_LIMBS * ENG_WAVE_WORDS) + k;
 #pragma unroll
     for (int l = 0; l < FP_LIMBS; ++l) b[l * (ENG_WAVE_WORDS / 2)] = make_uint2(v.c0.l[l], v.c1.l[l]);

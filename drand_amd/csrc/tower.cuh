@@ -24,23 +24,38 @@ struct fp12 {
 // ================================================================ Fp2
 DG_FN fp2 fp2_zero() { return fp2{fp_zero(), fp_zero()}; }
 DG_FN fp2 fp2_one() { return fp2{fp_one(), fp_zero()}; }
-DG_FN fp2 fp2_add(const fp2& a, const fp2& b) { return fp2{fp_add(a.c0, b.c0), fp_add(a.c1, b.c1)}; }
-DG_FN fp2 fp2_sub(const fp2& a, const fp2& b) { return fp2{fp_sub(a.c0, b.c0), fp_sub(a.c1, b.c1)}; }
-DG_FN fp2 fp2_neg(const fp2& a) { return fp2{fp_neg(a.c0), fp_neg(a.c1)}; }
-DG_FN fp2 fp2_dbl(const fp2& a) { return fp2_add(a, a); }
+// LZ: the form of the reductions inside (fp_reduce_lz, fp.cuh)
+template <bool LZ = DG_LZ_FORM>
+DG_FN fp2 fp2_add(const fp2& a, const fp2& b) {
+  return fp2{fp_add<LZ>(a.c0, b.c0), fp_add<LZ>(a.c1, b.c1)};
+}
+template <bool LZ = DG_LZ_FORM>
+DG_FN fp2 fp2_sub(const fp2& a, const fp2& b) {
+  return fp2{fp_sub<LZ>(a.c0, b.c0), fp_sub<LZ>(a.c1, b.c1)};
+}
+template <bool LZ = DG_LZ_FORM>
+DG_FN fp2 fp2_neg(const fp2& a) {
+  return fp2{fp_neg<LZ>(a.c0), fp_neg<LZ>(a.c1)};
+}
+template <bool LZ = DG_LZ_FORM>
+DG_FN fp2 fp2_dbl(const fp2& a) {
+  return fp2_add<LZ>(a, a);
+}
 DG_FN fp2 fp2_conj(const fp2& a) { return fp2{a.c0, fp_neg(a.c1)}; }
 DG_FN fp2 fp2_half(const fp2& a) { return fp2{fp_half(a.c0), fp_half(a.c1)}; }
 
 // Karatsuba: 3 Fp multiplications.  Lazy sums feed the third product
 // (limbs < 2^29, values < 4.02p: inside fp_mul's bounds); c1's subtrahend is
 // an unnormalized sum of two CI values, handled by fp_sub2_lz.
+template <bool LZ = DG_LZ_FORM>
 DG_FN fp2 fp2_mul(const fp2& a, const fp2& b) {
   fp t0 = fp_mul(a.c0, b.c0);
   fp t1 = fp_mul(a.c1, b.c1);
   fp t2 = fp_mul(fp_add_lz(a.c0, a.c1), fp_add_lz(b.c0, b.c1));
   fp2 r;
-  r.c0 = fp_sub(t0, t1);
-  r.c1 = fp_reduce(fp_norm(fp_sub2_lz(t2, fp_add_lz(t0, t1))));
+  r.c0 = fp_sub<LZ>(t0, t1);
+  // limbs < 2^28 + 2^30, value < 33.1p: inside fp_reduce_lz
+  r.c1 = fp_reduce_lz<LZ>(fp_sub2_lz(t2, fp_add_lz(t0, t1)));
   return r;
 }
 
@@ -71,8 +86,10 @@ DG_FN fp2 fp2_mulk_lz(const fp2& a, uint32_t k) {
 }
 // a - b reduced (CI): a CI, b normalized with value < 31.9p or an unnormalized
 // sum of two normalized values (fp_sub2_lz's precondition)
+// (limbs < 2^28 + 2^30, value < 34.1p: inside fp_reduce_lz)
+template <bool LZ = DG_LZ_FORM>
 DG_FN fp2 fp2_sub32(const fp2& a, const fp2& b) {
-  return fp2{fp_reduce(fp_norm(fp_sub2_lz(a.c0, b.c0))), fp_reduce(fp_norm(fp_sub2_lz(a.c1, b.c1)))};
+  return fp2{fp_reduce_lz<LZ>(fp_sub2_lz(a.c0, b.c0)), fp_reduce_lz<LZ>(fp_sub2_lz(a.c1, b.c1))};
 }
 
 // multiply by xi = 1 + u: (a0 - a1) + (a0 + a1) u
