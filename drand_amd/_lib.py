@@ -19,7 +19,7 @@ AB_KNOBS = frozenset({"DGPU_DEC_OVERLAP", "DGPU_MSM_SEG", "DGPU_LANE_SLICES", "D
                       "DGPU_RLC_LOCALIZE", "DGPU_G1_LINES", "DGPU_SUBGROUP", "DGPU_RECOVER", "DGPU_RECOVER_ROWS",
                       "DGPU_KB_INV_CHAIN", "DGPU_KB_TEST_FLAG", "DGPU_TEST_ALLOC_CAP", "DGPU_STAGE",
                       "DGPU_ENG_XW", "DGPU_TEST_STAGE_ONLY", "DGPU_LINES_WAVE", "DGPU_KB_PAIR", "DGPU_TEST_FORCE_EXC",
-                      "DGPU_REDUCE_NORM"})
+                      "DGPU_REDUCE_NORM", "DGPU_KEYED_RANGE"})
 
 DGPU_OK = 0
 DGPU_EINVAL = -1
@@ -41,6 +41,7 @@ REASON_DECODE = 1
 REASON_SUBGROUP = 2
 REASON_PAIRING = 3
 REASON_INFINITY = 4
+REASON_KEY = 5  # the record's key (dgpu_verify_keyed): rejected, or an index outside the table
 
 # every symbol include/drand_gpu.h declares: (name, restype, argtypes)
 _c = ctypes
@@ -119,6 +120,14 @@ SYMBOLS = [
     ("dgpu_multi_set_group", _c.c_int, [_P, _c.c_int, _c.c_int, _P]),
     ("dgpu_multi_set_group_scheme", _c.c_int, [_P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_size_t]),
     ("dgpu_recover_multi", _c.c_int, [_P, _c.c_size_t, _P, _c.c_size_t, _P, _c.c_size_t, _P, _P, _P, _P]),
+    ("dgpu_verify_keyed", _c.c_int, [_P, _c.c_int, _c.c_size_t, _P, _c.c_size_t, _c.c_size_t, _P, _P, _c.c_size_t, _P,
+                                     _P, _c.c_size_t, _P, _c.c_int, _c.c_uint64, _P, _P]),
+    ("dgpu_verify_keyed_device", _c.c_int, [_P, _c.c_int, _c.c_size_t, _P, _c.c_size_t, _c.c_size_t, _P, _P,
+                                            _c.c_size_t, _P, _P, _c.c_size_t, _P, _c.c_int, _c.c_uint64, _P, _P, _P]),
+    ("dgpu_verify_partials", _c.c_int, [_P, _c.c_size_t, _P, _c.c_size_t, _P, _c.c_size_t, _P, _c.c_int, _c.c_uint64,
+                                        _P, _P]),
+    ("dgpu_verify_partials_device", _c.c_int, [_P, _c.c_size_t, _P, _c.c_size_t, _P, _c.c_size_t, _P, _c.c_int,
+                                               _c.c_uint64, _P, _P, _P]),
 ]
 
 ABI_VERSION = 3

@@ -353,6 +353,60 @@ def verify_recovered(scheme: Scheme, pubkey, msgs, sigs, mode=_lib.MODE_PER_ROUN
     return reason
 
 
+def pack_keyed(code, keys, key_idx, msgs, sigs):
+    """The host arrays of a dgpu_verify_keyed call (no device needed): the key
+    table (n_keys x key_len bytes: 48 for the G2-signature schemes, 96 for the
+    G1-signature schemes), the 32-bit key indices, and the fixed-stride message
+    and signature records as verify_recovered packs them.  ValueError for a
+    key of the wrong length or an index outside the table (the library's
+    DGPU_EINVAL, raised before any call)."""
+    g1 = code in (_lib.SCHEME_UNCHAINED_G1, _lib.SCHEME_G1_RFC9380)
+    key_len, width = (96, 48) if g1 else (48, 96)
+    keys = [bytes(k) for k in keys]
+    if not 1 <= len(keys) <= 65536:
+        raise ValueError("a key table holds 1 to 65536 keys")
+    if {len(k) for k in keys} != {key_len}:
+        raise ValueError(f"keys of this scheme are {key_len} bytes each")
+    if not (len(key_idx) == len(msgs) == len(sigs)):
+        raise ValueError("key_idx, msgs and sigs differ in length")
+    idx = np.ascontiguousarray(key_idx, dtype=np.int64)
+    if idx.size and (idx.min() < 0 or idx.max() >= len(keys)):
+        raise ValueError("a key index lies outside the table")
+    kb = np.frombuffer(b"".join(keys), dtype=np.uint8).copy()
+    mb, ml = _pack_msgs(msgs)
+    sb, sl = _pack_msgs(sigs)
+    if sb.shape[1] < width:
+        sb = np.pad(sb, ((0, 0), (0, width - sb.shape[1])))
+    return kb, key_len, idx.astype(np.uint32), mb, ml, sb, sl
+
+
+def verify_keyed(scheme: Scheme, keys, key_idx, msgs, sigs, mode=_lib.MODE_PER_ROUND, rlc_seed=None, device=0,
+                 ctx=None):
+    """Batch bls.Verify(keys[key_idx[i]], msgs[i], sigs[i]) under a key per
+    record (dgpu_verify_keyed): node identities (identity.py), or the records
+    of several chains in one call.  keys: compressed public keys of the
+    scheme's key group.  Returns the DGPU_REASON_* code per record (0 =
+    valid); a record whose key is rejected (undecodable, outside the
+    subgroup, the identity) gets REASON_KEY, whatever its signature.  ctx: a
+    context of the caller's (default: the device's shared one)."""
+    code = scheme_code(scheme)
+    kb, key_len, idx, mb, ml, sb, sl = pack_keyed(code, keys, key_idx, msgs, sigs)
+    n = len(idx)
+    if n == 0:
+        return np.zeros(0, dtype=np.uint8)
+    ctx = ctx or get_context(device)
+    bits = np.zeros((n + 7) // 8, dtype=np.uint8)
+    reason = np.zeros(n, dtype=np.uint8)
+    _lib.check(ctx.lib.dgpu_verify_keyed(ctx.handle, code, kb.size // key_len, _lib.ptr(kb), key_len, n, _lib.ptr(idx),
+                                         _lib.ptr(mb), mb.shape[1], _lib.ptr(ml), _lib.ptr(sb), sb.shape[1],
+                                         _lib.ptr(sl), mode, rlc_seed_for(mode, rlc_seed), _lib.ptr(bits),
+                                         _lib.ptr(reason)), ctx.lib)
+    valid = np.unpackbits(bits, bitorder="little")[:n].astype(bool)
+    if not np.array_equal(valid, reason == _lib.REASON_OK):
+        raise _lib.DrandGPUError(_lib.DGPU_EINVAL, "verdict bitmap and reasons disagree")
+    return reason
+
+
 def hash_to_curve(msgs, scheme: Scheme = None, device=0):
     """Hash raw messages of any length to the scheme's signature group
     (compressed: 96-byte G2 under drand's DST, 48-byte G1 for the G1 schemes)."""

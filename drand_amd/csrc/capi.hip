@@ -32,6 +32,7 @@
 #include "recover_g1.cuh"
 #include "ingest_row.cuh"
 #include "check_rows.cuh"
+#include "keyed.cuh"
 #include "scratch_layouts.h"
 #include "record_arrays.h"
 
@@ -291,6 +292,14 @@ struct dgpu_ctx {
   DevBuf in_keys;               // dgpu_check_rows: the rows' keys, staged beside the rows
   DevBuf chk, chk_out;          // the faulty list's scratch (check_rows_layout) and dgpu_check_rows' device lists
   DevBuf in_halo, in_halo_len;  // a staged shard's halo (dgpu_verify_segment_multi): one record of the stride, its length
+  // dgpu_verify_keyed: the staged key indices; the key table (keyed_table_layout) and the gathered per-item keys;
+  // the pinned copy the table is uploaded from and the event of its last upload
+  DevBuf in_key_idx, ky_tab, ky_keys, ky_rlc, ky_exact;  // ... RLC mode: keyed_rlc_layout, keyed_exact_layout
+  size_t keyed_range = 0;  // A/B: DGPU_KEYED_RANGE=<entries>, list entries per thread of the per-key sums (0: the default)
+  void* ky_host = nullptr;
+  size_t ky_host_cap = 0;
+  hipEvent_t ky_ev = nullptr;
+  bool ky_ev_used = false;
   // optional per-stage HIP-event timing of the last verify call (event pool;
   // durations are summed per stage name: chunked stages repeat)
   bool profile = false;
@@ -1195,13 +1204,15 @@ int stager_wait_all(host_stager* stg, hipStream_t s);
 // s_dec (optional): the signature decode runs on that stream, beside the hash
 // chain on s (it reads only the records and writes sig_pts and the statuses);
 // s waits for it before returning.
+// decode_sub: the decoder checks the signatures' G2 membership whatever the
+// context's setting (a caller that combines the points before any lines kernel).
 // consts (the key's engine constants; optional): calls of at most
 // cof_engine_max rounds clear the cofactor on the engine ladder
 // (pairing_engine.cuh k_cof_*) instead of k_h2c_finish.
 int g2_lane_hash_locked(dgpu_ctx* c, lane_scratch& L, size_t n, const msg_src_host& m, const uint8_t* sigs,
                         size_t sig_stride, const uint32_t* sig_len, uint8_t* st, hipStream_t s,
                         hipStream_t s_dec = nullptr, const uint32_t* consts = nullptr, host_stager* stg = nullptr,
-                        size_t slice = 0) {
+                        size_t slice = 0, bool decode_sub = false) {
   const unsigned B = 256;
   int rc;
   h2c_tmp_layout tmp;  // u, q, then k_h2c_finish's park region and its redo flags
@@ -1216,7 +1227,7 @@ int g2_lane_hash_locked(dgpu_ctx* c, lane_scratch& L, size_t n, const msg_src_ho
   // membership of the signature: checked by the lines kernel (eng_pairing_locked sig_subgroup)
   auto decode = [&](hipStream_t sd) {
     with_src(m, [&](const auto& ms) {
-      if (c->decode_subgroup)
+      if (c->decode_subgroup || decode_sub)
         hipLaunchKernelGGL(SRC_KERNEL(k_decode_g2_sigs_sub, ms), dim3(grid_for(n, B)), dim3(B), 0, sd, n, sigs,
                            sig_stride, sig_len, ms, sg, st);
       else
@@ -2213,6 +2224,8 @@ int dgpu_open(int device, dgpu_ctx** out) {
   if (xwv) c->eng_xw = atoi(xwv) & 3;
   const char* stv = getenv("DGPU_STAGE");
   if (stv && !strcmp(stv, "pageable")) c->stage_pageable = true;
+  const char* krv = getenv("DGPU_KEYED_RANGE");
+  if (krv && atol(krv) >= 1) c->keyed_range = (size_t)atol(krv);
   const char* tso = getenv("DGPU_TEST_STAGE_ONLY");
   if (tso && !strcmp(tso, "1")) c->test_stage_only = true;
   const char* tac = getenv("DGPU_TEST_ALLOC_CAP");
@@ -2262,6 +2275,8 @@ void dgpu_close(dgpu_ctx* c) {
   for (hipEvent_t e : c->cof_ev)
     if (e) hipEventDestroy(e);
   if (c->done) hipEventDestroy(c->done);
+  if (c->ky_ev) hipEventDestroy(c->ky_ev);
+  if (c->ky_host) hipHostFree(c->ky_host);
   if (c->stream_copy) {
     hipStreamSynchronize(c->stream_copy);
     hipStreamDestroy(c->stream_copy);
@@ -2947,4 +2962,5 @@ int dgpu_make_chain(dgpu_ctx* c, int scheme, const uint8_t* sk_be32, size_t n_se
 }  // extern "C"
 
 #include "threshold_host.h"
+#include "keyed_host.h"
 #include "multi_gpu.h"

@@ -5,7 +5,9 @@
 // headers, which a host-only program includes under DG_NO_KERNELS.
 // Which program checks which layout: tests/scratch_layout_check.hip every
 // layout here except those of the row ingest group; tests/check_rows_check.cpp
-// that group (ingest_rows_layout, check_rows_layout, check_lists_layout).
+// that group (ingest_rows_layout, check_rows_layout, check_lists_layout);
+// tests/keyed_groups_check.cpp the keyed calls' RLC scratch (keyed_rlc_layout;
+// keyed_table_layout and keyed_exact_layout are plain arrays back to back).
 //
 // Alignment: a region is aligned to the widest access its kernels make --
 // 16 bytes for k_h2c_finish's park quads, 8 for the wave-blocked planes
@@ -226,6 +228,65 @@ struct commits_misc {
   void fill(carver& c, size_t t, size_t cb) {
     in = c.take<uint8_t>(t * cb);
     rc = c.take<int>(t);
+  }
+};
+
+// ky_tab (dgpu_verify_keyed): the call's n_keys table keys decoded -- affine
+// points, SoA with stride n_keys, G1 (x, y) for 48-byte keys and G2 for
+// 96-byte keys --, their decode codes, and the compressed bytes as given.
+struct keyed_table_layout {
+  uint32_t* pts;
+  int* rc;
+  uint8_t* in;
+  void fill(carver& c, size_t n_keys, size_t key_len) {
+    pts = c.take<uint32_t>(n_keys * (key_len == 96 ? (size_t)G2A_WORDS : 2 * (size_t)FP_LIMBS));
+    rc = c.take<int>(n_keys);
+    in = c.take<uint8_t>(n_keys * key_len);
+  }
+};
+
+// ky_rlc (dgpu_verify_keyed, RLC mode; keyed.cuh, keyed_groups.h): n records
+// under n_groups keys, T list ranges, m candidate slots; aw / jw words per
+// affine / Jacobian point of the signature group, kw words per key.
+struct keyed_rlc_layout {
+  uint32_t *counts, *offsets, *cursor, *cpos;  // [n_groups]
+  uint32_t* totals;                            // listed records, non-empty groups
+  uint32_t* nfail;                             // records listed for the exact check
+  uint32_t *list, *lkey, *flist;               // [n]
+  uint32_t *leaf_p, *leaf_s;                   // Jacobian SoA, stride n
+  uint32_t* sums;                              // [P | S], Jacobian SoA of stride n_groups each
+  uint32_t* part;                              // [P | S], each [A | B] of stride 2 T
+  uint32_t *ch, *cs, *ckeys;                   // the candidates: affine P, S and the key, stride m (each cleared on its own)
+  uint8_t* cst;                                // [m]
+  void fill(carver& c, size_t n, size_t n_groups, size_t T, size_t m, int aw, int jw, int kw) {
+    counts = c.take<uint32_t>(n_groups);
+    offsets = c.take<uint32_t>(n_groups);
+    cursor = c.take<uint32_t>(n_groups);
+    cpos = c.take<uint32_t>(n_groups);
+    totals = c.take<uint32_t>(2);
+    nfail = c.take<uint32_t>(1);
+    list = c.take<uint32_t>(n);
+    lkey = c.take<uint32_t>(n);
+    flist = c.take<uint32_t>(n);
+    leaf_p = c.take<uint32_t>(n * jw);
+    leaf_s = c.take<uint32_t>(n * jw);
+    sums = c.take<uint32_t>(2 * n_groups * jw);
+    part = c.take<uint32_t>(4 * T * jw);
+    ch = c.take<uint32_t>(m * aw);
+    cs = c.take<uint32_t>(m * aw);
+    ckeys = c.take<uint32_t>(m * kw);
+    cst = c.take<uint8_t>(m);
+  }
+};
+// ky_exact: the compact batch of the mf records of failing keys
+struct keyed_exact_layout {
+  uint32_t *h, *s, *keys;
+  uint8_t* st;
+  void fill(carver& c, size_t mf, int aw, int kw) {
+    h = c.take<uint32_t>(mf * aw);
+    s = c.take<uint32_t>(mf * aw);
+    keys = c.take<uint32_t>(mf * kw);
+    st = c.take<uint8_t>(mf);
   }
 };
 

@@ -19,7 +19,7 @@ import threading
 import numpy as np
 
 from . import _lib
-from .chain import get_context
+from .chain import get_context, rlc_seed_for
 from .scheme import Scheme, get_scheme_by_id_with_default, scheme_code
 
 _G1_SIG_CODES = (_lib.SCHEME_UNCHAINED_G1, _lib.SCHEME_G1_RFC9380)
@@ -154,6 +154,30 @@ class ThresholdGroup:
             _lib.check(self.ctx.lib.dgpu_recover_batch(self.ctx.handle, nr, _lib.ptr(mb), m, _lib.ptr(buf), stride,
                                                        _lib.ptr(plen), _lib.ptr(out), _lib.ptr(ok), _lib.ptr(pv)))
         return unpack_recovered(out, ok, pv, partials, m, self.sig_len)
+
+    def verify_partials(self, msgs, partials, mode=_lib.MODE_PER_ROUND, rlc_seed=None):
+        """key.Scheme.VerifyPartial of every partial (chain/beacon/node.go:
+        117-125) without recovering: msgs and partials as recover_batch takes
+        them.  Returns reasons[r][j], the DGPU_REASON_* code of partial j of
+        round r alone (0 = it verifies under PubPoly.Eval(its index); an empty
+        or mis-sized partial is DGPU_REASON_DECODE).  No "stop after t" and no
+        duplicate rule apply."""
+        nr = len(msgs)
+        if nr == 0:
+            return []
+        mb, buf, plen, m, stride = pack_partials(msgs, partials, self.scheme_code)
+        bits = np.zeros((nr * m + 7) // 8, dtype=np.uint8)
+        reason = np.zeros(nr * m, dtype=np.uint8)
+        seed = rlc_seed_for(mode, rlc_seed)
+        with ThresholdGroup._lock:
+            self._install()
+            _lib.check(self.ctx.lib.dgpu_verify_partials(self.ctx.handle, nr, _lib.ptr(mb), m, _lib.ptr(buf), stride,
+                                                         _lib.ptr(plen), mode, seed, _lib.ptr(bits),
+                                                         _lib.ptr(reason)))
+        valid = np.unpackbits(bits, bitorder="little")[:nr * m].astype(bool)
+        if not np.array_equal(valid, reason == _lib.REASON_OK):
+            raise _lib.DrandGPUError(_lib.DGPU_EINVAL, "verdict bitmap and reasons disagree")
+        return [[int(reason[r * m + j]) for j in range(len(partials[r]))] for r in range(nr)]
 
     def recover(self, msg, sigs):
         """key.Scheme.Recover(pub, msg, sigs, t, n): the recovered signature

@@ -69,7 +69,10 @@ extern "C" {
  * over such a shard) and dgpu_verify_segment_multi.  Also additive: stored rows
  * (dgpu_decode_rows_device, dgpu_verify_rows) and the check-chain loop's
  * faulty list built on the device (dgpu_faulty_rounds_device, dgpu_check_rows,
- * dgpu_check_rows_multi). */
+ * dgpu_check_rows_multi).  Also additive: verification under a key per record
+ * (dgpu_verify_keyed, dgpu_verify_keyed_device, reason DGPU_REASON_KEY) and
+ * VerifyPartial of every slot without a recovery (dgpu_verify_partials,
+ * dgpu_verify_partials_device). */
 #define DGPU_ABI_VERSION 3
 
 /* scheme IDs (common/scheme/scheme.go:9,12; bls-unchained-on-g1 added by this build) */
@@ -97,7 +100,9 @@ enum {
   DGPU_REASON_DECODE = 1,   /* kyber UnmarshalBinary error: length, flags, x >= p, not on curve */
   DGPU_REASON_SUBGROUP = 2, /* UnmarshalBinary error: not in the r-order subgroup              */
   DGPU_REASON_PAIRING = 3,  /* bls: invalid signature                                          */
-  DGPU_REASON_INFINITY = 4  /* signature decodes to the identity: pairing check fails          */
+  DGPU_REASON_INFINITY = 4, /* signature decodes to the identity: pairing check fails          */
+  DGPU_REASON_KEY = 5       /* the record's key (dgpu_verify_keyed): undecodable, not in the
+                               subgroup, the identity, or (device form) an index outside the table */
 };
 
 enum { DGPU_MODE_PER_ROUND = 0, DGPU_MODE_RLC = 1 };
@@ -403,6 +408,80 @@ int dgpu_verify_recovered(dgpu_ctx *ctx, int scheme, const uint8_t *pk, size_t p
                           size_t sig_stride, const uint32_t *sig_len, int mode, uint64_t rlc_seed,
                           uint8_t *verdict_bits, uint8_t *reason);
 
+/* Batch form of bls.Verify(keys[key_idx[i]], msg_i, sig_i): every record under
+ * its own key.  Call sites: Identity.ValidSignature / Group.UnsignedIdentities
+ * (key/keys.go:52-63, key/group.go:474-482; core/group_setup.go:187,
+ * core/drand_beacon.go:85) -- AuthScheme.Verify(node.Key, blake2b-256(node.Key),
+ * node.Signature), one key per node, under DGPU_SCHEME_CHAINED's groups and
+ * DST (AuthScheme, key/curve.go:39) --, and a relay or gossip validator that
+ * follows several chains and verifies their records in one call.
+ * Messages and signatures are exactly dgpu_verify_recovered's (raw messages of
+ * any length; msg_len[i] > msg_stride is DGPU_EINVAL); `scheme` selects the
+ * groups and the hash DST as there.
+ * keys: a host pointer in both forms, n_keys x key_len bytes of compressed
+ * keys; key_len is 48 for the G2-signature schemes and 96 for the G1-signature
+ * schemes (any other value: DGPU_EINVAL); 1 <= n_keys <= 65536 (else
+ * DGPU_EINVAL).  The table is copied before the call returns (like pk and
+ * seed_prev) and decoded on the device with the rules of dgpu_decode_pubkey.
+ * A rejected key is not an argument error: every record naming it gets
+ * verdict 0 and DGPU_REASON_KEY, which takes precedence over the record's own
+ * signature reason (the reference decodes the key before it looks at the
+ * signature).  The decode result is never read back by the host: the device
+ * form stays asynchronous.
+ * key_idx[i] >= n_keys: the host form returns DGPU_EINVAL before any device
+ * work; the device form gives the record DGPU_REASON_KEY and reads nothing
+ * outside the table.
+ * Contract: verdict bits and reasons equal dgpu_verify_recovered called once
+ * per key on that key's records under the same scheme and mode -- that call's
+ * reasons for a valid key, DGPU_REASON_KEY where that call returns DGPU_EINVAL.
+ * mode: DGPU_MODE_PER_ROUND (one pairing check per record, each against its
+ * own key, in one pairing batch on one stream) or DGPU_MODE_RLC (any other
+ * value: DGPU_EINVAL).  RLC mode applies at n >= DGPU_RLC_MIN records; below
+ * that the call runs per record, as elsewhere.  A batch under K keys splits
+ * into K independent random linear combinations: per record the leaves
+ * [a_i] H(m_i) + [b_i] endo(H(m_i)) and the same of sig_i, (a_i, b_i) the
+ * halves of the 64-bit coefficient derived from rlc_seed and i; per key the
+ * sums of its undecided records' leaves; one 2-pairing check per non-empty
+ * key.  The records of every failing key are then checked one by one, exactly
+ * (bisection inside a key's group is not built: one bad record costs its
+ * key's whole group a per-record pass), so verdicts and reasons equal
+ * per-record mode's except with probability <= 2^-64 per failing check.
+ * Signatures are subgroup-checked before any combination and table keys at
+ * decode.  RLC mode synchronises the stream once (the count of records left
+ * to the exact check), as the single-key RLC mode does for its node verdict.
+ * Cost: a record's pairing check is replaced by two 64-bit scalar
+ * multiplications in the signature group (measured at 1Mi records: about 70 ms
+ * against 340 ms of pairing checks for G2 signatures, 22 ms for G1
+ * signatures), and every non-empty key adds one pairing check, every failing
+ * key a per-record pass over its records (profiles/r16/keyed_vs_calls.txt).
+ * Clean batches of 1Mi records were faster in RLC mode at every table size
+ * measured, K = 1 to 65,536 (1.7-2.1 times for G2 signatures, 3.3-4.5 times
+ * for G1 signatures).  Stay per record when K approaches n (node identities:
+ * one record per key, nothing to combine) and when most keys are expected to
+ * hold a bad record: the combination is then paid on top of the per-record
+ * pass (with 0.1% corrupted, RLC mode was 1.3 times slower than per record at
+ * K <= 8 and no faster at K = 1,024 for G2 signatures).  A dirty batch under
+ * one key is dgpu_verify_recovered's case, whose RLC mode bisects.
+ * n = 0 is a no-op that accepts NULL pointers; any keyed call cancels a
+ * pending RLC root, like every other call.  The whole call runs on one stream.
+ * The host form stages its records through the pinned ring, the key indices
+ * as one more 4-byte array behind the records; dgpu_staging_stats bytes are
+ * n x (msg_stride + sig_stride + 12). */
+int dgpu_verify_keyed(dgpu_ctx *ctx, int scheme, size_t n_keys, const uint8_t *keys, size_t key_len, size_t n,
+                      const uint32_t *key_idx, const uint8_t *msgs, size_t msg_stride, const uint32_t *msg_len,
+                      const uint8_t *sigs, size_t sig_stride, const uint32_t *sig_len, int mode, uint64_t rlc_seed,
+                      uint8_t *verdict_bits, uint8_t *reason);
+
+/* dgpu_verify_keyed over device-resident records (d_* are device pointers;
+ * keys stays a host pointer), asynchronous on `stream` as
+ * dgpu_verify_beacons_device.  A record with d_msg_len[i] > msg_stride is not
+ * read past its stride and fails with DGPU_REASON_DECODE. */
+int dgpu_verify_keyed_device(dgpu_ctx *ctx, int scheme, size_t n_keys, const uint8_t *keys, size_t key_len, size_t n,
+                             const uint32_t *d_key_idx, const uint8_t *d_msgs, size_t msg_stride,
+                             const uint32_t *d_msg_len, const uint8_t *d_sigs, size_t sig_stride,
+                             const uint32_t *d_sig_len, int mode, uint64_t rlc_seed, uint8_t *d_verdict_bits,
+                             uint8_t *d_reason, void *stream);
+
 /* Batch form of Verifier.VerifyBeacon (chain/verify.go:38-45) over n beacons
  * given as fixed-stride records (host pointers):
  *   rounds[i]                   Beacon.Round
@@ -446,7 +525,12 @@ int dgpu_verify_batch_device(dgpu_ctx *ctx, int scheme, size_t n, const uint64_t
  * rlc_prep, the engine stages of the node checks, rlc_leaves_tree,
  * rlc_bisection; recovery: recover_hash, recover_decode, recover_select,
  * recover_lagrange, engine stages, recover_msm, recover_rlc_g1 (a
- * G1-signature group: recover_rlc_g2), recover_verdict), at most max_stages of them, and returns the
+ * G1-signature group: recover_rlc_g2), recover_verdict; keyed calls: keyed_keys (the table's
+ * upload and decode), the hash and decode stages, keyed_gather, the engine
+ * stages, pack_verdicts, and in RLC mode keyed_leaves, keyed_group, keyed_sums,
+ * keyed_prep ahead of the node checks' engine stages and keyed_fallback -- only
+ * when a key failed -- around the exact check's; dgpu_verify_partials: recover_hash, recover_decode,
+ * the engine stages, pack_verdicts), at most max_stages of them, and returns the
  * number of distinct stages the call recorded (like snprintf: a value above
  * max_stages means the output was truncated).  DGPU_MAX_STAGES bounds every
  * pipeline's count.  A call that recorded more stage events than the
@@ -458,7 +542,7 @@ int dgpu_verify_batch_device(dgpu_ctx *ctx, int scheme, size_t n, const uint64_t
 int dgpu_synchronize(dgpu_ctx *ctx);
 int dgpu_set_profiling(dgpu_ctx *ctx, int enable);
 /* Host-record staging of the last call on the context that took host records
- * (dgpu_verify_beacons, dgpu_verify_batch, dgpu_verify_recovered, a shard of
+ * (dgpu_verify_beacons, dgpu_verify_batch, dgpu_verify_recovered, dgpu_verify_keyed, a shard of
  * dgpu_verify_multi or dgpu_verify_segment_multi) or stored rows
  * (dgpu_verify_rows, dgpu_check_rows, a shard of dgpu_check_rows_multi: their
  * bytes are stated there): the records go through a library-owned pinned ring
@@ -587,6 +671,39 @@ int dgpu_recover_batch(dgpu_ctx *ctx, size_t n_rounds, const uint8_t *msgs32, si
 int dgpu_recover_batch_device(dgpu_ctx *ctx, size_t n_rounds, const uint8_t *d_msgs32, size_t m,
                               const uint8_t *d_partials, size_t partial_stride, const uint32_t *d_partial_len,
                               uint8_t *d_out_sigs, uint8_t *d_ok, uint8_t *d_status, void *stream);
+
+/* key.Scheme.VerifyPartial of every slot of dgpu_recover_batch's input shape
+ * under the installed group (DGPU_ENOKEY without one), as the node runs it on
+ * a partial's arrival (chain/beacon/node.go:117-125) -- which partials verify,
+ * without a recovery.  The item key is PubPoly.Eval(index): from the group's
+ * table for index < n, evaluated on the fly above it.  Partials are in the
+ * installed group's format (98 bytes, or 50 under a G1-signature group).
+ * valid_bits: one bit per slot, ceil(n_rounds m / 8) bytes, slot r m + j at bit
+ * (r m + j) % 8 of byte (r m + j) / 8; reason (optional, n_rounds m bytes): the
+ * DGPU_REASON_* of that partial alone.  There is no "stop after t" and no
+ * duplicate rule; an empty or mis-sized slot (a length above the stride
+ * included, which is never read) is DGPU_REASON_DECODE.  It is the first step
+ * of the exact recovery path (hash, partial decode, one pairing per partial)
+ * followed by the verdict pack.  mode: DGPU_MODE_PER_ROUND or DGPU_MODE_RLC (any
+ * other value: DGPU_EINVAL).  RLC mode, at DGPU_RLC_MIN slots and above, is
+ * dgpu_verify_keyed's per-key combination with the share index as the key
+ * index: one 2-pairing check per share that has an undecided partial, the
+ * round's hash point shared by the round's slots, then the exact check of
+ * every failing share's partials.  A partial whose index lies above the
+ * group's table (its key evaluated on the fly) is not combined: it goes to the
+ * exact check.  Verdicts and reasons equal per-record mode's except with
+ * probability <= 2^-64 per failing check; pass a fresh unpredictable
+ * rlc_seed (partials come from peers).  One stream synchronisation, as there.  n_rounds = 0 is a no-op that accepts
+ * NULL pointers. */
+int dgpu_verify_partials(dgpu_ctx *ctx, size_t n_rounds, const uint8_t *msgs32, size_t m, const uint8_t *partials,
+                         size_t partial_stride, const uint32_t *partial_len, int mode, uint64_t rlc_seed,
+                         uint8_t *valid_bits, uint8_t *reason);
+
+/* dgpu_verify_partials over device buffers, asynchronous on `stream` (as
+ * dgpu_recover_batch_device). */
+int dgpu_verify_partials_device(dgpu_ctx *ctx, size_t n_rounds, const uint8_t *d_msgs32, size_t m,
+                                const uint8_t *d_partials, size_t partial_stride, const uint32_t *d_partial_len,
+                                int mode, uint64_t rlc_seed, uint8_t *d_valid_bits, uint8_t *d_reason, void *stream);
 
 /* Synthetic threshold partials (test/bench data tool; tbls.Sign (R),
  * chain/beacon/node_test.go:56-106 builds the same shape): for item i of
