@@ -58,12 +58,20 @@ int set_err(int code, const char* fmt, ...) {
     hipError_t _e = (expr);                                                                       \
     if (_e != hipSuccess) return set_err(DGPU_EDEVICE, "%s: %s", #expr, hipGetErrorString(_e)); \
   } while (0)
+// the same for the library's own int codes (the message is already set)
+#define RC_TRY(expr)                  \
+  do {                                \
+    if (int _rc = (expr)) return _rc; \
+  } while (0)
 
 // Grow-only device scratch buffer, owner of its allocation.  Growth frees the
 // old allocation only after the device is idle: a kernel enqueued earlier
 // (this call or an earlier asynchronous one) may still read it.  The
 // destructor and release() free at once: the owner has drained the streams
 // that used the buffer (dgpu_close, stream_scratch, the callers of release()).
+// as<T>() (u32() / u8() / u64() for the three common element types): the
+// buffer as the element type a kernel takes; p itself is for the calls that
+// want an untyped pointer (copies, memsets, layout_at, record_ptr_set).
 #ifdef DG_AB_KNOBS
 // test hook of the A/B build (DGPU_TEST_ALLOC_CAP=<bytes>): larger requests
 // fail as an out-of-memory hipMalloc would (the engine chunk's retry path)
@@ -92,8 +100,8 @@ struct DevBuf {
       return set_err(DGPU_ENOMEM, "hipMalloc(%zu): test cap %zu", bytes, g_test_alloc_cap);
 #endif
     if (p) {
-      hipDeviceSynchronize();
-      hipFree(p);
+      (void)hipDeviceSynchronize();
+      (void)hipFree(p);
     }
     p = nullptr;
     cap = 0;
@@ -103,10 +111,15 @@ struct DevBuf {
     return DGPU_OK;
   }
   void release() {
-    if (p) hipFree(p);
+    if (p) (void)hipFree(p);
     p = nullptr;
     cap = 0;
   }
+  template <class T>
+  T* as() const { return static_cast<T*>(p); }
+  uint32_t* u32() const { return as<uint32_t>(); }
+  uint8_t* u8() const { return as<uint8_t>(); }
+  uint64_t* u64() const { return as<uint64_t>(); }
 };
 
 // Size, allocate and carve a buffer with more than one region: the layout's
@@ -120,6 +133,35 @@ int carve(DevBuf& b, L* lay, D... dims) {
 }
 
 inline unsigned grid_for(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
+
+// One checked kernel launch.  The argument types are the kernel's own
+// parameter types (same<> keeps them out of deduction), so arity is checked
+// and T* -> const T* and nullptr convert as in a direct call.  Nothing else
+// happens here: no skip of an empty grid, no synchronisation, no stage mark.
+template <class T>
+struct same_t {
+  using type = T;
+};
+template <class T>
+using same = typename same_t<T>::type;
+template <class... KA>
+int launch(void (*k)(KA...), dim3 grid, dim3 block, hipStream_t s, same<KA>... a) {
+  hipLaunchKernelGGL(k, grid, block, 0, s, a...);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DGPU_OK : set_err(DGPU_EDEVICE, "kernel launch: %s", hipGetErrorString(e));
+}
+// ... of `threads` threads in one-dimensional blocks of `block`
+template <class... KA>
+int launch_n(void (*k)(KA...), size_t threads, unsigned block, hipStream_t s, same<KA>... a) {
+  return launch(k, dim3(grid_for(threads, block)), dim3(block), s, a...);
+}
+
+// Fork or join of two streams: `waiter` continues after what `from` holds now.
+inline int stream_after(hipStream_t waiter, hipStream_t from, hipEvent_t ev) {
+  HIP_TRY(hipEventRecord(ev, from));
+  HIP_TRY(hipStreamWaitEvent(waiter, ev, 0));
+  return DGPU_OK;
+}
 
 // SplitMix64 step on the host: independent RLC seeds derived from a call's
 // seed per device of dgpu_verify_multi (drand_amd/dist.py rank_seed is the
@@ -192,6 +234,15 @@ auto with_src(const msg_src_host& m, F&& f) {
 }
 // the kernel template K for the source type of `src` (inside with_src)
 #define SRC_KERNEL(K, src) K<std::decay_t<decltype(src)>>
+
+// f(group) with the signature group as the type its kernels and host
+// templates are instantiated for: G1Ops{} (signatures on G1) or G2Ops{}.
+template <class F>
+auto with_group(bool g1, F&& f) {
+  return g1 ? f(G1Ops{}) : f(G2Ops{});
+}
+// the group type of `gr` (inside with_group)
+#define GROUP_OF(gr) std::decay_t<decltype(gr)>
 
 }  // namespace
 
@@ -326,8 +377,8 @@ namespace {
 struct stream_order {
   dgpu_ctx* c;
   hipStream_t s;
-  stream_order(dgpu_ctx* c_, hipStream_t s_) : c(c_), s(s_) { hipStreamWaitEvent(s, c->done, 0); }
-  ~stream_order() { hipEventRecord(c->done, s); }
+  stream_order(dgpu_ctx* c_, hipStream_t s_) : c(c_), s(s_) { (void)hipStreamWaitEvent(s, c->done, 0); }
+  ~stream_order() { (void)hipEventRecord(c->done, s); }
 };
 
 // N temporary device buffers of a data tool.  However the tool returns, the
@@ -382,9 +433,17 @@ void mark(dgpu_ctx* c, hipStream_t s, const char* name = nullptr) {
     c->ev.push_back(e);
     c->stage_name.push_back(nullptr);
   }
-  hipEventRecord(c->ev[c->n_ev], s);
+  (void)hipEventRecord(c->ev[c->n_ev], s);
   c->stage_name[c->n_ev] = name;
   c->n_ev++;
+}
+
+// The start of a verify or recovery call's device work: no stage events yet,
+// and a pending per-rank RLC root (dgpu_rlc_root_device) is cancelled.
+void call_reset(dgpu_ctx* c) {
+  c->n_ev = 0;
+  c->ev_overflow = false;
+  c->rlc_pending = false;
 }
 
 // Engine block constants (slot order of tools/gen_engine.py: ONE, the two
@@ -428,8 +487,7 @@ int decode_g1_key_locked(dgpu_ctx* c, key_entry* e, const uint8_t* pk) {
   if (rc) return rc;
   hipStream_t s = c->stream;
   HIP_TRY(hipMemcpyAsync(M.in, pk, 48, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_decode_g1_pk, dim3(1), dim3(64), 0, s, M.in, M.out, M.rc);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch(k_decode_g1_pk, dim3(1), dim3(64), s, M.in, M.out, M.rc));
   uint32_t host[2 * FP_LIMBS + 1];  // out and, next to it, rc
   HIP_TRY(hipMemcpyAsync(host, M.out, sizeof host, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -461,21 +519,16 @@ int decode_g2_key_locked(dgpu_ctx* c, key_entry* e, const uint8_t* pk) {
   hipStream_t s = c->stream;
   hipError_t err = hipMemcpyAsync(d_in, pk, 96, hipMemcpyHostToDevice, s);
   if (err == hipSuccess) err = hipMemcpyAsync(d_g2, gw, sizeof gw, hipMemcpyHostToDevice, s);
-  if (err == hipSuccess) {
-    hipLaunchKernelGGL(k_decode_g2_pk, dim3(1), dim3(64), 0, s, d_in, d_pk, d_rc);
-    err = hipGetLastError();
-  }
+  if (err != hipSuccess) return set_err(DGPU_EDEVICE, "set_pubkey: %s", hipGetErrorString(err));
+  RC_TRY(launch(k_decode_g2_pk, dim3(1), dim3(64), s, d_in, d_pk, d_rc));
   int drc = -1;
-  if (err == hipSuccess) err = hipMemcpyAsync(&drc, d_rc, sizeof drc, hipMemcpyDeviceToHost, s);
+  err = hipMemcpyAsync(&drc, d_rc, sizeof drc, hipMemcpyDeviceToHost, s);
   if (err == hipSuccess) err = hipStreamSynchronize(s);
   if (err != hipSuccess) return set_err(DGPU_EDEVICE, "set_pubkey: %s", hipGetErrorString(err));
   if (drc != DEC_OK) return set_err(DGPU_EINVAL, "public key rejected (decode code %d)", drc);
-  hipLaunchKernelGGL(k_eng_lines, dim3(1), dim3(ENG_BLOCK), 0, s, (size_t)1, (size_t)0, (size_t)1,
-                     (const uint32_t*)d_pk, (size_t)1, (const uint32_t*)nullptr, (const uint32_t*)d_g2,
-                     (const uint32_t*)nullptr, (const uint32_t*)unit.p, (uint32_t*)e->table.p, (uint8_t*)nullptr,
-                     (uint32_t*)nullptr);
-  err = hipGetLastError();
-  if (err == hipSuccess) err = hipStreamSynchronize(s);
+  RC_TRY(launch(k_eng_lines, dim3(1), dim3(ENG_BLOCK), s, 1, 0, 1, d_pk, 1, nullptr, d_g2, nullptr, unit.u32(),
+                e->table.u32(), nullptr, nullptr));
+  err = hipStreamSynchronize(s);
   if (err != hipSuccess) return set_err(DGPU_EDEVICE, "set_pubkey lines: %s", hipGetErrorString(err));
   return DGPU_OK;
 }
@@ -539,54 +592,37 @@ int eng_fe_kb_locked(dgpu_ctx* c, const uint32_t* consts, size_t cnt, size_t cap
       const bool kb_thread = c->kb_thread && cnt >= c->thr_min;
       const bool norm_pre = kb_thread && c->kb_norm_chain;
       if (norm_pre && c->kb_pair)  // two lanes per round
-        hipLaunchKernelGGL(k_kb_chain_pair<true>, dim3(grid_for(2 * cnt, 256)), dim3(256), 0, s, cnt, xbuf, ebuf);
+        RC_TRY(launch_n(k_kb_chain_pair<true>, 2 * cnt, 256, s, cnt, xbuf, ebuf));
 #ifdef DG_AB_KNOBS
-      else if (kb_thread && c->reduce_norm && norm_pre)
-        hipLaunchKernelGGL((k_kb_chain_thr<true, false>), dim3(grid_for(cnt, 256)), dim3(256), 0, s, cnt, xbuf, ebuf);
       else if (kb_thread && c->reduce_norm)
-        hipLaunchKernelGGL((k_kb_chain_thr<false, false>), dim3(grid_for(cnt, 256)), dim3(256), 0, s, cnt, xbuf, nullptr);
+        RC_TRY(launch_n(norm_pre ? k_kb_chain_thr<true, false> : k_kb_chain_thr<false, false>, cnt, 256, s, cnt, xbuf,
+                        norm_pre ? ebuf : nullptr));
 #endif
-      else if (norm_pre)
-        hipLaunchKernelGGL(k_kb_chain_thr<true>, dim3(grid_for(cnt, 256)), dim3(256), 0, s, cnt, xbuf, ebuf);
       else if (kb_thread)
-        hipLaunchKernelGGL(k_kb_chain_thr<false>, dim3(grid_for(cnt, 256)), dim3(256), 0, s, cnt, xbuf, nullptr);
+        RC_TRY(launch_n(norm_pre ? k_kb_chain_thr<true> : k_kb_chain_thr<false>, cnt, 256, s, cnt, xbuf,
+                        norm_pre ? ebuf : nullptr));
       else
-        hipLaunchKernelGGL(k_eng_kb_chain, dim3(grid_for(cnt, 8)), dim3(64), 0, s, cnt, xbuf);
-      HIP_TRY(hipGetLastError());
+        RC_TRY(launch(k_eng_kb_chain, dim3(grid_for(cnt, 8)), dim3(64), s, cnt, xbuf));
       mark(c, s, "eng_fe_kbinv");
-      if (norm_pre)
-        hipLaunchKernelGGL(k_eng_kb_norm<true>, dim3(grid_for(cnt, 256)), dim3(256), 0, s, cnt, r0,
-                           (const uint32_t*)xbuf, pbuf, ebuf, flags, (const uint8_t*)st, c->kb_test_flag);
-      else
-        hipLaunchKernelGGL(k_eng_kb_norm<false>, dim3(grid_for(cnt, 256)), dim3(256), 0, s, cnt, r0,
-                           (const uint32_t*)xbuf, pbuf, ebuf, flags, (const uint8_t*)st, c->kb_test_flag);
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(k_eng_inv, dim3(grid_for(inv_threads, 256)), dim3(256), 0, s, cnt, r0, pbuf, pre, st);
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(k_eng_kb_dec, dim3(grid_for((size_t)ENG_KB_NSNAP * cnt, 256)), dim3(256), 0, s, cnt, xbuf,
-                         (const uint32_t*)pbuf, (const uint32_t*)ebuf, (const uint8_t*)flags);
-      HIP_TRY(hipGetLastError());
+      RC_TRY(launch_n(norm_pre ? k_eng_kb_norm<true> : k_eng_kb_norm<false>, cnt, 256, s, cnt, r0, xbuf, pbuf, ebuf, flags,
+                      st, c->kb_test_flag));
+      RC_TRY(launch_n(k_eng_inv, inv_threads, 256, s, cnt, r0, pbuf, pre, st));
+      RC_TRY(launch_n(k_eng_kb_dec, (size_t)ENG_KB_NSNAP * cnt, 256, s, cnt, xbuf, pbuf, ebuf, flags));
     }
     mark(c, s, "eng_fe");
     const int so = ENG_PROG_FEK_OFF[seg], sl = ENG_PROG_FEK_OFF[seg + 1] - ENG_PROG_FEK_OFF[seg];
+    const bool first = seg == 0, last = seg == nseg - 1;
 #ifdef DG_AB_KNOBS
-    if ((c->eng_xw & 2) && seg > 0 && seg < nseg - 1)  // measured slower too (r06d)
-      hipLaunchKernelGGL(k_eng_fe_seg_xw<ENG_FEK_MID_SLOTS>, dim3(grid_for(cnt, ENG_XW_ITEMS)), dim3(ENG_XW_BLOCK), 0, s,
-                         so, sl, false, false, cnt, r0, consts, (const uint32_t*)f, n1inv, xbuf, flags, fb, st);
-    else if (c->eng_xw & 2)
-      hipLaunchKernelGGL(k_eng_fe_seg_xw<ENG_SLOTS_FE>, dim3(grid_for(cnt, ENG_XW_ITEMS)), dim3(ENG_XW_BLOCK), 0, s,
-                         so, sl, seg == 0, seg == nseg - 1, cnt, r0, consts, (const uint32_t*)f, n1inv, xbuf, flags, fb,
-                         st);
+    if (c->eng_xw & 2)  // measured slower too (r06d)
+      RC_TRY(launch(first || last ? k_eng_fe_seg_xw<ENG_SLOTS_FE> : k_eng_fe_seg_xw<ENG_FEK_MID_SLOTS>,
+                    dim3(grid_for(cnt, ENG_XW_ITEMS)), dim3(ENG_XW_BLOCK), s, so, sl, first, last, cnt, r0, consts, f, n1inv,
+                    xbuf, flags, fb, st));
     else
 #endif
-      hipLaunchKernelGGL(k_eng_fe_seg, dim3(blocks), dim3(ENG_BLOCK), 0, s, so, sl, seg == 0, seg == nseg - 1, cnt, r0,
-                         consts, (const uint32_t*)f, n1inv, xbuf, flags, fb, st);
-    HIP_TRY(hipGetLastError());
+      RC_TRY(launch(k_eng_fe_seg, dim3(blocks), dim3(ENG_BLOCK), s, so, sl, first, last, cnt, r0, consts, f, n1inv, xbuf,
+                    flags, fb, st));
   }
-  hipLaunchKernelGGL(k_eng_fe_fb, dim3(ENG_FB_GRID), dim3(ENG_BLOCK), 0, s, cnt, r0, consts, f, n1inv, st,
-                     (const uint8_t*)flags, (const uint32_t*)fb);
-  HIP_TRY(hipGetLastError());
-  return DGPU_OK;
+  return launch(k_eng_fe_fb, dim3(ENG_FB_GRID), dim3(ENG_BLOCK), s, cnt, r0, consts, f, n1inv, st, flags, fb);
 }
 
 // One batch of pairing checks for eng_pairing_locked: item i passes when
@@ -658,68 +694,60 @@ int eng_pairing_locked(dgpu_ctx* c, const pairing_job& job, hipStream_t s) {
   // k_eng_inv's prefix products (eng_n1_words(cap)) reuse the line buffer: they fit
   // in its cap_blk blocks (scratch_layouts.h's static_assert); the fused path has
   // no line buffer and sizes lane 0's for them alone
-  uint32_t* lines = need_lines ? (uint32_t*)L.lines.p : nullptr;
-  uint32_t* f = (uint32_t*)L.f.p;
-  uint32_t* n1 = (uint32_t*)L.n1.p;
+  uint32_t* lines = need_lines ? L.lines.u32() : nullptr;
+  uint32_t* f = L.f.u32();
+  uint32_t* n1 = L.n1.u32();
   uint32_t* pre = need_lines ? lines : nullptr;
   if (!pre) {
     if ((rc = c->lane[0].lines.ensure(eng_n1_words(cap) * 4))) return rc;
-    pre = (uint32_t*)c->lane[0].lines.p;
+    pre = c->lane[0].lines.u32();
   }
+  uint8_t* const sub_st = sig_subgroup ? st : nullptr;
   for (size_t r0 = 0; r0 < n; r0 += cap) {
     const size_t cnt = std::min(cap, n - r0);
-    const unsigned blocks = grid_for(cnt, ENG_ROUNDS_PER_BLOCK);
+    const dim3 blocks(grid_for(cnt, ENG_ROUNDS_PER_BLOCK)), eng(ENG_BLOCK);
     if (!need_lines) {  // on-G1, lines formed inside the Miller kernel
       mark(c, s, "eng_miller");
-      hipLaunchKernelGGL(k_eng_miller_fixed, dim3(blocks), dim3(ENG_BLOCK), 0, s, n, r0, cnt, consts, h, sg,
-                         fixed_table, f, n1);
-      HIP_TRY(hipGetLastError());
+      RC_TRY(launch(k_eng_miller_fixed, blocks, eng, s, n, r0, cnt, consts, h, sg, fixed_table, f, n1));
     } else {
+      const bool thr = c->lines_thread && cnt >= c->thr_min;
       if (g1form_keys) {  // G1-signature recovery: h and sg affine G1 points, pair 0's G2 point per item
         mark(c, s, "eng_lines");
-        hipLaunchKernelGGL(k_lines_thr_g1, dim3(grid_for(2 * cnt, 256)), dim3(256), 0, s, n, r0, cnt, h, h_stride, h_idx,
-                           sg, g1form_keys, lines);
+        RC_TRY(launch_n(k_lines_thr_g1, 2 * cnt, 256, s, n, r0, cnt, h, h_stride, h_idx, sg, g1form_keys, lines));
       } else if (fixed_table) {  // on-G1: h and sg are affine G1 points, the G2 arguments fixed
         mark(c, s, "eng_lines_fixed");
-        hipLaunchKernelGGL(k_eng_lines_fixed, dim3(blocks, ENG_LINE_STEPS), dim3(ENG_BLOCK), 0, s, n, r0, cnt, h, sg,
-                           fixed_table, lines);
+        RC_TRY(launch(k_eng_lines_fixed, dim3(blocks.x, ENG_LINE_STEPS), eng, s, n, r0, cnt, h, sg, fixed_table, lines));
+      } else if (thr && !pk_items && c->lines_wave) {  // pair per wave: P in SGPRs
+        mark(c, s, "eng_lines");
+        RC_TRY(launch_n(k_lines_thr<true>, 2 * ((cnt + 63) / 64 * 64), 256, s, n, r0, cnt, h, h_stride, h_idx, sg, pk_items,
+                        consts, lines, sub_st));
+      } else if (thr) {
+        mark(c, s, "eng_lines");
+#ifdef DG_AB_KNOBS
+        const auto k = c->reduce_norm ? k_lines_thr<false, false> : k_lines_thr<false>;
+#else
+        const auto k = k_lines_thr<false>;
+#endif
+        RC_TRY(launch_n(k, 2 * cnt, 256, s, n, r0, cnt, h, h_stride, h_idx, sg, pk_items, consts, lines, sub_st));
       } else {
         mark(c, s, "eng_lines");
-        if (c->lines_thread && cnt >= c->thr_min && !pk_items && c->lines_wave)  // pair per wave: P in SGPRs
-          hipLaunchKernelGGL(k_lines_thr<true>, dim3(grid_for(2 * ((cnt + 63) / 64 * 64), 256)), dim3(256), 0, s, n, r0,
-                             cnt, h, h_stride, h_idx, sg, pk_items, consts, lines,
-                             sig_subgroup ? st : (uint8_t*)nullptr);
-#ifdef DG_AB_KNOBS
-        else if (c->lines_thread && cnt >= c->thr_min && c->reduce_norm)
-          hipLaunchKernelGGL((k_lines_thr<false, false>), dim3(grid_for(2 * cnt, 256)), dim3(256), 0, s, n, r0, cnt, h,
-                             h_stride, h_idx, sg, pk_items, consts, lines, sig_subgroup ? st : (uint8_t*)nullptr);
-#endif
-        else if (c->lines_thread && cnt >= c->thr_min)
-          hipLaunchKernelGGL(k_lines_thr<false>, dim3(grid_for(2 * cnt, 256)), dim3(256), 0, s, n, r0, cnt, h, h_stride,
-                             h_idx, sg, pk_items, consts, lines, sig_subgroup ? st : (uint8_t*)nullptr);
-        else
-          hipLaunchKernelGGL(k_eng_lines, dim3(blocks), dim3(ENG_BLOCK), 0, s, n, r0, cnt, h, h_stride, h_idx, sg,
-                           pk_items, consts, lines, sig_subgroup ? st : (uint8_t*)nullptr, (uint32_t*)nullptr);
+        RC_TRY(launch(k_eng_lines, blocks, eng, s, n, r0, cnt, h, h_stride, h_idx, sg, pk_items, consts, lines, sub_st,
+                      nullptr));
       }
-      HIP_TRY(hipGetLastError());
       mark(c, s, "eng_miller");
 #ifdef DG_AB_KNOBS
       if (c->eng_xw & 1)  // no idle lanes, barrier-ordered: measured 8% slower (profiles/r06/r06d_engine_xw_ab.txt)
-        hipLaunchKernelGGL(k_eng_miller_xw, dim3(grid_for(cnt, ENG_XW_ITEMS)), dim3(ENG_XW_BLOCK), 0, s, cnt, consts,
-                           lines, f, n1);
+        RC_TRY(launch(k_eng_miller_xw, dim3(grid_for(cnt, ENG_XW_ITEMS)), dim3(ENG_XW_BLOCK), s, cnt, consts, lines, f, n1));
       else
 #endif
-        hipLaunchKernelGGL(k_eng_miller, dim3(blocks), dim3(ENG_BLOCK), 0, s, cnt, consts, lines, f, n1);
-      HIP_TRY(hipGetLastError());
+        RC_TRY(launch(k_eng_miller, blocks, eng, s, cnt, consts, lines, f, n1));
     }
     const size_t inv_threads = std::max<size_t>(1, (cnt + 63) / 64);
     mark(c, s, "eng_inv");
-    hipLaunchKernelGGL(k_eng_inv, dim3(grid_for(inv_threads, 256)), dim3(256), 0, s, cnt, r0, n1, pre, st);
-    HIP_TRY(hipGetLastError());
+    RC_TRY(launch_n(k_eng_inv, inv_threads, 256, s, cnt, r0, n1, pre, st));
     if (fe_gs) {
       mark(c, s, "eng_fe");
-      hipLaunchKernelGGL(k_eng_fe, dim3(blocks), dim3(ENG_BLOCK), 0, s, cnt, r0, consts, f, n1, st);
-      HIP_TRY(hipGetLastError());
+      RC_TRY(launch(k_eng_fe, blocks, eng, s, cnt, r0, consts, f, n1, st));
     } else if ((rc = eng_fe_kb_locked(c, consts, cnt, cap_blk * ENG_ROUNDS_PER_BLOCK, r0, f, n1, kb, st, s))) {
       return rc;
     }
@@ -736,13 +764,14 @@ struct rlc_geom {
   bool g1;
   int aw, jw;  // affine / Jacobian words per point
 };
-inline rlc_geom rlc_geom_of(bool g1) { return g1 ? rlc_geom{true, G1A_WORDS, G1J_WORDS} : rlc_geom{false, G2A_WORDS, G2J_WORDS}; }
+inline rlc_geom rlc_geom_of(bool g1) {
+  return with_group(g1, [&](auto gr) { return rlc_geom{g1, GrMem<GROUP_OF(gr)>::AFF, GrMem<GROUP_OF(gr)>::JAC}; });
+}
 
 // The SSWU stage of the G2 hash over 2n field elements u -> Jacobian points
 // in q: the fused k_h2c_sswu.
-hipError_t launch_sswu(size_t n, const uint32_t* u, uint32_t* q, hipStream_t s) {
-  hipLaunchKernelGGL(k_h2c_sswu, dim3(grid_for(2 * n, 256)), dim3(256), 0, s, n, u, q);
-  return hipGetLastError();
+int launch_sswu(size_t n, const uint32_t* u, uint32_t* q, hipStream_t s) {
+  return launch_n(k_h2c_sswu, 2 * n, 256, s, n, u, q);
 }
 
 // rlc_tree of a batch of n rounds: the trees' levels and the points R_i.
@@ -767,53 +796,35 @@ int rlc_points_locked(dgpu_ctx* c, const verify_args& a, hipStream_t s) {
   if ((rc = rlc_tree_carve(c, n, G, &tree))) return rc;
   if ((rc = L.sig_pts.ensure(n * G.aw * 4)) || (rc = L.h_pre.ensure(n * FP_WORDS * 4))) return rc;
   uint32_t* const rpts = tree.rpts;
-  uint32_t* sg = (uint32_t*)L.sig_pts.p;
-  uint8_t* st = (uint8_t*)c->status.p;
+  uint32_t* sg = L.sig_pts.u32();
+  uint8_t* st = c->status.u8();
   if (G.g1) {
     mark(c, s, "rlc_hash_to_g1_raw");
-    with_src(a.m, [&](const auto& m) {
-      hipLaunchKernelGGL(SRC_KERNEL(k_hash_to_g1_raw, m), dim3(grid_for(n, B)), dim3(B), 0, s, n, m,
-                         a.scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, rpts, tree.rz);
-    });
-    HIP_TRY(hipGetLastError());
+    RC_TRY(with_src(a.m, [&](const auto& m) {
+      return launch_n(SRC_KERNEL(k_hash_to_g1_raw, m), n, B, s, n, m, a.scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, rpts,
+                      tree.rz);
+    }));
     mark(c, s, "decode_g1");
-    with_src(a.m, [&](const auto& m) {
-      hipLaunchKernelGGL(SRC_KERNEL(k_decode_g1_sigs, m), dim3(grid_for(n, B)), dim3(B), 0, s, n, a.sigs, a.sig_stride,
-                         a.sig_len, m, sg, st);
-    });
-    HIP_TRY(hipGetLastError());
+    RC_TRY(with_src(a.m, [&](const auto& m) {
+      return launch_n(SRC_KERNEL(k_decode_g1_sigs, m), n, B, s, n, a.sigs, a.sig_stride, a.sig_len, m, sg, st);
+    }));
     mark(c, s, "rlc_affine");
-    hipLaunchKernelGGL(k_g1_batch_affine, dim3(grid_for((n + 15) / 16, B)), dim3(B), 0, s, n, rpts,
-                       (const uint32_t*)tree.rz, (uint32_t*)L.h_pre.p);
-    HIP_TRY(hipGetLastError());
-    return DGPU_OK;
+    return launch_n(k_g1_batch_affine, (n + 15) / 16, B, s, n, rpts, tree.rz, L.h_pre.u32());
   }
   h2c_tmp_layout tmp;
   if ((rc = carve(L.h_tmp, &tmp, n, false))) return rc;
   mark(c, s, "rlc_hash_to_g2_raw");
-  {
-    // the per-round hash's field and SSWU stages, then Q0 + Q1 without the cofactor
-    uint32_t *const u = tmp.u, *const q = tmp.q;
-    with_src(a.m, [&](const auto& m) {
-      hipLaunchKernelGGL(SRC_KERNEL(k_h2c_field, m), dim3(grid_for(n, B)), dim3(B), 0, s, n, m, u);
-    });
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(launch_sswu(n, u, q, s));
-    hipLaunchKernelGGL(k_h2c_sum, dim3(grid_for(n, B)), dim3(B), 0, s, n, (const uint32_t*)q, rpts);
-    HIP_TRY(hipGetLastError());
-  }
+  // the per-round hash's field and SSWU stages, then Q0 + Q1 without the cofactor
+  RC_TRY(with_src(a.m, [&](const auto& m) { return launch_n(SRC_KERNEL(k_h2c_field, m), n, B, s, n, m, tmp.u); }));
+  RC_TRY(launch_sswu(n, tmp.u, tmp.q, s));
+  RC_TRY(launch_n(k_h2c_sum, n, B, s, n, tmp.q, rpts));
   mark(c, s, "decode_g2");
-  with_src(a.m, [&](const auto& m) {
-    hipLaunchKernelGGL(SRC_KERNEL(k_decode_g2_sigs_sub, m), dim3(grid_for(n, B)), dim3(B), 0, s, n, a.sigs, a.sig_stride,
-                       a.sig_len, m, sg, st);
-  });
-  HIP_TRY(hipGetLastError());
+  RC_TRY(with_src(a.m, [&](const auto& m) {
+    return launch_n(SRC_KERNEL(k_decode_g2_sigs_sub, m), n, B, s, n, a.sigs, a.sig_stride, a.sig_len, m, sg, st);
+  }));
   mark(c, s, "rlc_affine");
   // R_i to affine in place (X, Y slots; Z follows them in the Jacobian SoA)
-  hipLaunchKernelGGL(k_g2_batch_affine, dim3(grid_for((n + 15) / 16, B)), dim3(B), 0, s, n, rpts,
-                     (const uint32_t*)tree.rz, (uint32_t*)L.h_pre.p);
-  HIP_TRY(hipGetLastError());
-  return DGPU_OK;
+  return launch_n(k_g2_batch_affine, (n + 15) / 16, B, s, n, rpts, tree.rz, L.h_pre.u32());
 }
 
 // RLC root by bucket MSM (rlc_msm.cuh) into root (P then S, stride-1
@@ -835,8 +846,8 @@ int rlc_root_msm_t(dgpu_ctx* c, const verify_args& a, hipStream_t s, const rlc_r
       (rc = carve(c->msm_counts, &mc)) || (rc = carve(c->msm_list, &ml, n)) ||
       (rc = c->msm_buckets.ensure(MSM_KEYS * M::JAC * 4)) || (rc = carve(c->msm_runs, &mr, M::JAC)))
     return rc;
-  uint32_t* aos = (uint32_t*)c->msm_aos.p;
-  uint8_t* flags = (uint8_t*)c->msm_flags.p;
+  uint32_t* aos = c->msm_aos.u32();
+  uint8_t* flags = c->msm_flags.u8();
   uint32_t *const counts = mc.counts, *const offsets = mc.offsets, *const cursor = mc.cursor;
   uint32_t* const list = ml.list;
   uint32_t* const keys = c->msm_seg ? ml.keys : nullptr;  // the key of every list entry
@@ -844,47 +855,30 @@ int rlc_root_msm_t(dgpu_ctx* c, const verify_args& a, hipStream_t s, const rlc_r
   const size_t seg_threads = (size_t)c->n_cu * 4 * 2 * 64;
   if (c->msm_seg && (rc = c->msm_part.ensure(2 * seg_threads * M::JAC * 4))) return rc;
   mark(c, s, stage);
-  hipLaunchKernelGGL(k_msm_aos<Gr>, dim3(grid_for(n, B)), dim3(B), 0, s, n, (const uint32_t*)tree.rpts,
-                     (const uint32_t*)c->lane[0].sig_pts.p, (const uint8_t*)c->status.p, aos, flags);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_msm_aos<Gr>, n, B, s, n, tree.rpts, c->lane[0].sig_pts.u32(), c->status.u8(), aos, flags));
   HIP_TRY(hipMemsetAsync(counts, 0, MSM_KEYS * 4, s));
-  hipLaunchKernelGGL(k_msm_count, dim3(grid_for(n, B)), dim3(B), 0, s, n, a.seed, (const uint8_t*)flags, counts);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_msm_scan, dim3(1), dim3(1024), 0, s, (const uint32_t*)counts, offsets, cursor);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_msm_scatter, dim3(grid_for(n, B)), dim3(B), 0, s, n, a.seed, (const uint8_t*)flags, cursor,
-                     list, keys);
-  HIP_TRY(hipGetLastError());
-  uint32_t* buckets = (uint32_t*)c->msm_buckets.p;
+  RC_TRY(launch_n(k_msm_count, n, B, s, n, a.seed, flags, counts));
+  RC_TRY(launch(k_msm_scan, dim3(1), dim3(1024), s, counts, offsets, cursor));
+  RC_TRY(launch_n(k_msm_scatter, n, B, s, n, a.seed, flags, cursor, list, keys));
+  uint32_t* buckets = c->msm_buckets.u32();
   if (c->msm_seg) {
-    uint32_t* part = (uint32_t*)c->msm_part.p;
-    hipLaunchKernelGGL(k_msm_bucket_seg<Gr>, dim3(grid_for(seg_threads, B)), dim3(B), 0, s, n, seg_threads,
-                       (const uint32_t*)offsets, (const uint32_t*)counts, (const uint32_t*)list, (const uint32_t*)keys,
-                       (const uint32_t*)aos, buckets, part);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_msm_fixup<Gr>, dim3(grid_for(MSM_KEYS, B)), dim3(B), 0, s, seg_threads,
-                       (const uint32_t*)offsets, (const uint32_t*)counts, (const uint32_t*)part, buckets);
+    uint32_t* part = c->msm_part.u32();
+    RC_TRY(launch_n(k_msm_bucket_seg<Gr>, seg_threads, B, s, n, seg_threads, offsets, counts, list, keys, aos, buckets,
+                    part));
+    RC_TRY(launch_n(k_msm_fixup<Gr>, MSM_KEYS, B, s, seg_threads, offsets, counts, part, buckets));
   } else {
-    hipLaunchKernelGGL(k_msm_bucket<Gr>, dim3(grid_for(MSM_KEYS, B)), dim3(B), 0, s, n, (const uint32_t*)offsets,
-                       (const uint32_t*)counts, (const uint32_t*)list, (const uint32_t*)aos, buckets);
+    RC_TRY(launch_n(k_msm_bucket<Gr>, MSM_KEYS, B, s, n, offsets, counts, list, aos, buckets));
   }
-  HIP_TRY(hipGetLastError());
   uint32_t *runs = mr.runs, *runs2 = mr.runs2;
-  hipLaunchKernelGGL(k_msm_window<Gr>, dim3(grid_for((size_t)MSM_MW * MSM_RUNS, B)), dim3(B), 0, s,
-                     (const uint32_t*)buckets, runs);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_msm_window<Gr>, (size_t)MSM_MW * MSM_RUNS, B, s, buckets, runs));
   size_t len = MSM_RUNS;
   while (len > 1) {  // pairwise tree per (MSM, window), ping-pong between the two run buffers
     const size_t nl = (len + 1) / 2;
-    hipLaunchKernelGGL(k_sum_level<Gr>, dim3(grid_for((size_t)MSM_MW * nl, B)), dim3(B), 0, s, MSM_MW, len,
-                       (const uint32_t*)runs, nl, runs2);
-    HIP_TRY(hipGetLastError());
+    RC_TRY(launch_n(k_sum_level<Gr>, (size_t)MSM_MW * nl, B, s, MSM_MW, len, runs, nl, runs2));
     std::swap(runs, runs2);
     len = nl;
   }
-  hipLaunchKernelGGL(k_msm_root<Gr>, dim3(1), dim3(64), 0, s, (const uint32_t*)runs, root.P, root.S);
-  HIP_TRY(hipGetLastError());
-  return DGPU_OK;
+  return launch(k_msm_root<Gr>, dim3(1), dim3(64), s, runs, root.P, root.S);
 }
 
 // The root goes to `dst` (rlc_root_layout: P then S).
@@ -894,8 +888,7 @@ int rlc_root_msm_locked(dgpu_ctx* c, const verify_args& a, hipStream_t s, DevBuf
   int rc = carve(dst, &root, rlc_geom_of(sig_on_g1(a.scheme)).jw);
   if (rc) return rc;
   if (out) *out = root;
-  return sig_on_g1(a.scheme) ? rlc_root_msm_t<G1Ops>(c, a, s, root, stage)
-                             : rlc_root_msm_t<G2Ops>(c, a, s, root, stage);
+  return with_group(sig_on_g1(a.scheme), [&](auto gr) { return rlc_root_msm_t<GROUP_OF(gr)>(c, a, s, root, stage); });
 }
 
 // The segment trees of one RLC batch (leaves P_i = r_i R_i, S_i = r_i sig_i,
@@ -910,25 +903,19 @@ int rlc_tree_t(dgpu_ctx* c, const verify_args& a, hipStream_t s, rlc_trees& T, b
   if (rc) return rc;
   T = tree.T;
   mark(c, s, plain ? "rlc_plain_tree" : "rlc_leaves_tree");
+  const uint32_t* const sg = c->lane[0].sig_pts.u32();
+  const uint8_t* const st = c->status.u8();
   if (plain)
-    hipLaunchKernelGGL(k_rlc_leaves_plain<Gr>, dim3(grid_for(2 * n, B)), dim3(B), 0, s, n,
-                       (const uint32_t*)tree.rpts, (const uint32_t*)c->lane[0].sig_pts.p,
-                       (const uint8_t*)c->status.p, T.P[0], T.S[0]);
+    RC_TRY(launch_n(k_rlc_leaves_plain<Gr>, 2 * n, B, s, n, tree.rpts, sg, st, T.P[0], T.S[0]));
   else
-    hipLaunchKernelGGL(k_rlc_leaves<Gr>, dim3(grid_for(2 * n, B)), dim3(B), 0, s, n, a.seed,
-                       (const uint32_t*)tree.rpts, (const uint32_t*)c->lane[0].sig_pts.p,
-                       (const uint8_t*)c->status.p, T.P[0], T.S[0]);
-  HIP_TRY(hipGetLastError());
-  for (int l = 0; l < T.top(); ++l) {
-    hipLaunchKernelGGL(k_rlc_level<Gr>, dim3(grid_for(2 * T.sz[l + 1], B)), dim3(B), 0, s, T.sz[l], T.P[l], T.S[l],
-                       T.sz[l + 1], T.P[l + 1], T.S[l + 1]);
-    HIP_TRY(hipGetLastError());
-  }
+    RC_TRY(launch_n(k_rlc_leaves<Gr>, 2 * n, B, s, n, a.seed, tree.rpts, sg, st, T.P[0], T.S[0]));
+  for (int l = 0; l < T.top(); ++l)
+    RC_TRY(launch_n(k_rlc_level<Gr>, 2 * T.sz[l + 1], B, s, T.sz[l], T.P[l], T.S[l], T.sz[l + 1], T.P[l + 1], T.S[l + 1]));
   return DGPU_OK;
 }
 
 int rlc_tree_locked(dgpu_ctx* c, const verify_args& a, hipStream_t s, rlc_trees& T, bool plain = false) {
-  return sig_on_g1(a.scheme) ? rlc_tree_t<G1Ops>(c, a, s, T, plain) : rlc_tree_t<G2Ops>(c, a, s, T, plain);
+  return with_group(sig_on_g1(a.scheme), [&](auto gr) { return rlc_tree_t<GROUP_OF(gr)>(c, a, s, T, plain); });
 }
 
 // The identity (Z = 0) of the signature group as a stride-1 Jacobian point
@@ -957,32 +944,27 @@ int rlc_check_locked(dgpu_ctx* c, const key_entry* key, const std::vector<uint32
   if ((rc = c->rlc_idx.ensure(m * 4)) || (rc = c->rlc_fail.ensure(m))) return rc;
   if ((rc = c->rlc_h.ensure(m * G.aw * 4)) || (rc = c->rlc_s.ensure(m * G.aw * 4)) || (rc = c->rlc_st.ensure(m)))
     return rc;
-  uint32_t* d_idx = (uint32_t*)c->rlc_idx.p;
-  uint8_t* d_fail = (uint8_t*)c->rlc_fail.p;
+  uint32_t* d_idx = c->rlc_idx.u32();
+  uint8_t* d_fail = c->rlc_fail.u8();
   HIP_TRY(hipMemcpyAsync(d_idx, cand.data(), m * 4, hipMemcpyHostToDevice, s));
-  uint32_t* ch = (uint32_t*)c->rlc_h.p;
-  uint32_t* cs = (uint32_t*)c->rlc_s.p;
-  uint8_t* cst = (uint8_t*)c->rlc_st.p;
+  uint32_t* ch = c->rlc_h.u32();
+  uint32_t* cs = c->rlc_s.u32();
+  uint8_t* cst = c->rlc_st.u8();
   mark(c, s, "rlc_prep");
-  if (G.g1)
-    hipLaunchKernelGGL(k_rlc_prep<G1Ops>, dim3(grid_for(m, 64)), dim3(64), 0, s, m, d_idx, n_level, P_lvl, S_lvl, ch,
-                       cs, cst);
-  else
-    hipLaunchKernelGGL(k_rlc_prep<G2Ops>, dim3(grid_for(m, 64)), dim3(64), 0, s, m, d_idx, n_level, P_lvl, S_lvl, ch,
-                       cs, cst);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(with_group(G.g1, [&](auto gr) {
+    return launch_n(k_rlc_prep<GROUP_OF(gr)>, m, 64, s, m, d_idx, n_level, P_lvl, S_lvl, ch, cs, cst);
+  }));
   if ((rc = eng_pairing_locked(c,
-                               {.consts = (const uint32_t*)key->consts.p,
+                               {.consts = key->consts.u32(),
                                 .n = m,
                                 .h = ch,
                                 .sg = cs,
                                 .st = cst,
-                                .fixed_table = G.g1 ? (const uint32_t*)key->table.p : nullptr},
+                                .fixed_table = G.g1 ? key->table.u32() : nullptr},
                                s)))
     return rc;
   mark(c, s, "rlc_bisection");
-  hipLaunchKernelGGL(k_rlc_fail, dim3(grid_for(m, B)), dim3(B), 0, s, m, cst, d_fail);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_rlc_fail, m, B, s, m, cst, d_fail));
   if (fail) {
     fail->resize(m);
     HIP_TRY(hipMemcpyAsync(fail->data(), d_fail, m, hipMemcpyDeviceToHost, s));
@@ -1002,7 +984,7 @@ int rlc_descend_locked(dgpu_ctx* c, const key_entry* key, const rlc_trees& T, hi
   const unsigned B = 256;
   const int D = c->rlc_descent_step;
   const int top = T.top();
-  uint8_t* st = (uint8_t*)c->status.p;
+  uint8_t* st = c->status.u8();
   std::vector<uint8_t> fail;
   std::vector<uint32_t> cand{0};
   mark(c, s, "rlc_bisection");
@@ -1027,9 +1009,7 @@ int rlc_descend_locked(dgpu_ctx* c, const key_entry* key, const rlc_trees& T, hi
     int rc = rlc_check_locked(c, key, cand, T.sz[l], T.P[l], T.S[l], s, l == 0 ? nullptr : &fail);
     if (rc) return rc;
     if (l == 0) {
-      hipLaunchKernelGGL(k_rlc_mark, dim3(grid_for(cand.size(), B)), dim3(B), 0, s, cand.size(),
-                         (const uint32_t*)c->rlc_idx.p, (const uint8_t*)c->rlc_fail.p, st);
-      HIP_TRY(hipGetLastError());
+      RC_TRY(launch_n(k_rlc_mark, cand.size(), B, s, cand.size(), c->rlc_idx.u32(), c->rlc_fail.u8(), st));
       if (leaf_cand) leaf_cand->swap(cand);  // rlc_idx / rlc_fail still hold them on the device
       break;
     }
@@ -1082,28 +1062,19 @@ int rlc_confirm_t(dgpu_ctx* c, const key_entry* key, const verify_args& a, hipSt
   uint32_t nf = 0;
   if (mc) {
     HIP_TRY(hipMemsetAsync(count, 0, 4, s));
-    hipLaunchKernelGGL(k_rlc_compact_fail, dim3(grid_for(mc, B)), dim3(B), 0, s, mc, (const uint32_t*)c->rlc_idx.p,
-                       (const uint8_t*)c->rlc_fail.p, list, count);
-    HIP_TRY(hipGetLastError());
+    RC_TRY(launch_n(k_rlc_compact_fail, mc, B, s, mc, c->rlc_idx.u32(), c->rlc_fail.u8(), list, count));
     HIP_TRY(hipMemcpyAsync(&nf, count, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
   }
   if (nf) {  // the marked rounds' leaves, summed pairwise to one (P, S)
     sum_levels F;
     if ((rc = carve(c->rlc_fsum, &F, (size_t)nf, M::JAC))) return rc;
-    hipLaunchKernelGGL(k_rlc_leaves_list<Gr>, dim3(grid_for(2 * (size_t)nf, B)), dim3(B), 0, s, (size_t)nf,
-                       (const uint32_t*)list, a.n, a.seed, (const uint32_t*)tree.rpts,
-                       (const uint32_t*)c->lane[0].sig_pts.p, F.P[0], F.S[0]);
-    HIP_TRY(hipGetLastError());
-    for (int l = 0; l < F.top(); ++l) {
-      hipLaunchKernelGGL(k_rlc_level<Gr>, dim3(grid_for(2 * F.sz[l + 1], B)), dim3(B), 0, s, F.sz[l], F.P[l], F.S[l],
-                         F.sz[l + 1], F.P[l + 1], F.S[l + 1]);
-      HIP_TRY(hipGetLastError());
-    }
+    RC_TRY(launch_n(k_rlc_leaves_list<Gr>, 2 * (size_t)nf, B, s, nf, list, a.n, a.seed, tree.rpts,
+                    c->lane[0].sig_pts.u32(), F.P[0], F.S[0]));
+    for (int l = 0; l < F.top(); ++l)
+      RC_TRY(launch_n(k_rlc_level<Gr>, 2 * F.sz[l + 1], B, s, F.sz[l], F.P[l], F.S[l], F.sz[l + 1], F.P[l + 1], F.S[l + 1]));
     // (one node: stride 1; the kernel reads the shard's root and writes conf as P | S)
-    hipLaunchKernelGGL(k_rlc_sub_root<Gr>, dim3(1), dim3(64), 0, s, (const uint32_t*)shard_root.P,
-                       (const uint32_t*)F.P[F.top()], (const uint32_t*)F.S[F.top()], conf.P);
-    HIP_TRY(hipGetLastError());
+    RC_TRY(launch(k_rlc_sub_root<Gr>, dim3(1), dim3(64), s, shard_root.P, F.P[F.top()], F.S[F.top()], conf.P));
   } else {
     HIP_TRY(hipMemcpyAsync(conf.P, shard_root.P, layout_bytes<rlc_root_layout>(M::JAC), hipMemcpyDeviceToDevice, s));
   }
@@ -1128,17 +1099,18 @@ int rlc_resolve_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a, 
     if ((rc = rlc_tree_locked(c, a, s, T, true)) || (rc = rlc_descend_locked(c, key, T, s, true, &leaf_cand)))
       return rc;
     bool ok = false;
-    rc = g1 ? rlc_confirm_t<G1Ops>(c, key, a, s, shard_root, leaf_cand, &ok)
-            : rlc_confirm_t<G2Ops>(c, key, a, s, shard_root, leaf_cand, &ok);
+    rc = with_group(g1, [&](auto gr) { return rlc_confirm_t<GROUP_OF(gr)>(c, key, a, s, shard_root, leaf_cand, &ok); });
     if (rc || ok) return rc;
   }
   if ((rc = rlc_tree_locked(c, a, s, T))) return rc;
   return rlc_descend_locked(c, key, T, s, true);
 }
 
-// Signatures on G1: H(m) in G1 (+ batch affine), G1 signature decode, then
-// the engine's Miller (fixed-Q lines) / inversion / final-exponentiation kernels.
-int verify_g1_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a, uint8_t* st, hipStream_t s) {
+// Per-round G1 path, first half (the counterpart of g2_lane_hash_locked):
+// H(m) in G1, batch affine and the G1 signature decode of a's records into
+// lane 0's buffers.  side: the decode runs on stream2 beside the hash (as the
+// G2 path's s_dec); s waits for it before returning.
+int g1_hash_decode_locked(dgpu_ctx* c, const verify_args& a, uint8_t* st, hipStream_t s, bool side) {
   const unsigned B = 256;
   const size_t n = a.n;
   int rc;
@@ -1146,49 +1118,49 @@ int verify_g1_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a, ui
   if ((rc = L.h_pts.ensure(n * 2 * FP_WORDS * 4)) || (rc = L.sig_pts.ensure(n * 2 * FP_WORDS * 4)) ||
       (rc = L.h_z.ensure(n * FP_WORDS * 4)) || (rc = L.h_pre.ensure(n * FP_WORDS * 4)))
     return rc;
-  uint32_t* h = (uint32_t*)L.h_pts.p;
-  uint32_t* sg = (uint32_t*)L.sig_pts.p;
-  // the signature decode beside the hash on the second stream (as the G2 path, g2_lane_hash_locked)
-  const bool side = c->dec_overlap && c->lanes > 1 && !c->profile;
+  uint32_t* h = L.h_pts.u32();
+  auto decode = [&](hipStream_t sd) {
+    return with_src(a.m, [&](const auto& m) {
+      return launch_n(SRC_KERNEL(k_decode_g1_sigs, m), n, B, sd, n, a.sigs, a.sig_stride, a.sig_len, m, L.sig_pts.u32(),
+                      st);
+    });
+  };
   side_join join(side ? c->stream2 : nullptr, s, c->lane_ev[1]);
   if (side) {
-    HIP_TRY(hipEventRecord(c->lane_ev[0], s));
-    HIP_TRY(hipStreamWaitEvent(c->stream2, c->lane_ev[0], 0));
-    with_src(a.m, [&](const auto& m) {
-      hipLaunchKernelGGL(SRC_KERNEL(k_decode_g1_sigs, m), dim3(grid_for(n, B)), dim3(B), 0, c->stream2, n, a.sigs,
-                         a.sig_stride, a.sig_len, m, sg, st);
-    });
-    HIP_TRY(hipGetLastError());
+    RC_TRY(stream_after(c->stream2, s, c->lane_ev[0]));
+    RC_TRY(decode(c->stream2));
     HIP_TRY(hipEventRecord(c->lane_ev[1], c->stream2));
   }
   mark(c, s, "hash_to_g1");
-  with_src(a.m, [&](const auto& m) {
-    hipLaunchKernelGGL(SRC_KERNEL(k_hash_to_g1_beacons, m), dim3(grid_for(n, B)), dim3(B), 0, s, n, m,
-                       a.scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, h, (uint32_t*)L.h_z.p);
-  });
-  HIP_TRY(hipGetLastError());
+  RC_TRY(with_src(a.m, [&](const auto& m) {
+    return launch_n(SRC_KERNEL(k_hash_to_g1_beacons, m), n, B, s, n, m, a.scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, h,
+                    L.h_z.u32());
+  }));
   mark(c, s, "h_affine");
-  hipLaunchKernelGGL(k_g1_batch_affine, dim3(grid_for((n + 15) / 16, B)), dim3(B), 0, s, n, h,
-                     (const uint32_t*)L.h_z.p, (uint32_t*)L.h_pre.p);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_g1_batch_affine, (n + 15) / 16, B, s, n, h, L.h_z.u32(), L.h_pre.u32()));
   if (side) {
     HIP_TRY(hipStreamWaitEvent(s, c->lane_ev[1], 0));
     join.release();
-  } else {
-    mark(c, s, "decode_g1");
-    with_src(a.m, [&](const auto& m) {
-      hipLaunchKernelGGL(SRC_KERNEL(k_decode_g1_sigs, m), dim3(grid_for(n, B)), dim3(B), 0, s, n, a.sigs, a.sig_stride,
-                         a.sig_len, m, sg, st);
-    });
-    HIP_TRY(hipGetLastError());
+    return DGPU_OK;
   }
+  mark(c, s, "decode_g1");
+  return decode(s);
+}
+
+// Signatures on G1: the front half above (the decode beside the hash on the
+// second stream), then the engine's Miller (fixed-Q lines) / inversion /
+// final-exponentiation kernels.
+int verify_g1_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a, uint8_t* st, hipStream_t s) {
+  int rc = g1_hash_decode_locked(c, a, st, s, c->dec_overlap && c->lanes > 1 && !c->profile);
+  if (rc) return rc;
+  const lane_scratch& L = c->lane[0];
   return eng_pairing_locked(c,
-                            {.consts = (const uint32_t*)key->consts.p,
-                             .n = n,
-                             .h = h,
-                             .sg = sg,
+                            {.consts = key->consts.u32(),
+                             .n = a.n,
+                             .h = L.h_pts.u32(),
+                             .sg = L.sig_pts.u32(),
                              .st = st,
-                             .fixed_table = (const uint32_t*)key->table.p},
+                             .fixed_table = key->table.u32()},
                             s);
 }
 
@@ -1220,21 +1192,16 @@ int g2_lane_hash_locked(dgpu_ctx* c, lane_scratch& L, size_t n, const msg_src_ho
       (rc = L.h_z.ensure(n * 2 * FP_WORDS * 4)) || (rc = L.h_pre.ensure(n * FP_WORDS * 4)) ||
       (rc = carve(L.h_tmp, &tmp, n, true)))
     return rc;
-  uint32_t* h = (uint32_t*)L.h_pts.p;
-  uint32_t* sg = (uint32_t*)L.sig_pts.p;
+  uint32_t *const h = L.h_pts.u32(), *const sg = L.sig_pts.u32(), *const hz = L.h_z.u32();
   uint32_t *const u = tmp.u, *const q = tmp.q, *const park = tmp.park;
   uint8_t* const redo = tmp.redo;
   // membership of the signature: checked by the lines kernel (eng_pairing_locked sig_subgroup)
   auto decode = [&](hipStream_t sd) {
-    with_src(m, [&](const auto& ms) {
+    return with_src(m, [&](const auto& ms) {
       if (c->decode_subgroup || decode_sub)
-        hipLaunchKernelGGL(SRC_KERNEL(k_decode_g2_sigs_sub, ms), dim3(grid_for(n, B)), dim3(B), 0, sd, n, sigs,
-                           sig_stride, sig_len, ms, sg, st);
-      else
-        hipLaunchKernelGGL(SRC_KERNEL(k_decode_g2_sigs, ms), dim3(grid_for(n, B)), dim3(B), 0, sd, n, sigs, sig_stride,
-                           sig_len, ms, 0, sg, st);
+        return launch_n(SRC_KERNEL(k_decode_g2_sigs_sub, ms), n, B, sd, n, sigs, sig_stride, sig_len, ms, sg, st);
+      return launch_n(SRC_KERNEL(k_decode_g2_sigs, ms), n, B, sd, n, sigs, sig_stride, sig_len, ms, 0, sg, st);
     });
-    return hipGetLastError();
   };
   const bool cof_engine = consts && n <= c->cof_engine_max;
   const unsigned cof_blocks = grid_for(n, ENG_ROUNDS_PER_BLOCK);
@@ -1244,69 +1211,46 @@ int g2_lane_hash_locked(dgpu_ctx* c, lane_scratch& L, size_t n, const msg_src_ho
     return rc;  // allocated before the fork: a failure here leaves nothing on the side stream
   side_join join(s_dec, s, c->lane_ev[1]);
   if (s_dec) {  // first in the second stream's queue: it runs beside the whole hash chain
-    HIP_TRY(hipEventRecord(c->lane_ev[0], s));
-    HIP_TRY(hipStreamWaitEvent(s_dec, c->lane_ev[0], 0));
+    RC_TRY(stream_after(s_dec, s, c->lane_ev[0]));
     if ((rc = stager_wait_sig(stg, slice, s_dec))) return rc;  // host records: the slice's signatures on the device
-    HIP_TRY(decode(s_dec));
+    RC_TRY(decode(s_dec));
     HIP_TRY(hipEventRecord(c->lane_ev[1], s_dec));
   }
   mark(c, s, "hash_to_g2");
-  with_src(m, [&](const auto& ms) {
-    hipLaunchKernelGGL(SRC_KERNEL(k_h2c_field, ms), dim3(grid_for(n, B)), dim3(B), 0, s, n, ms, u);
-  });
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(launch_sswu(n, u, q, s));
+  RC_TRY(with_src(m, [&](const auto& ms) { return launch_n(SRC_KERNEL(k_h2c_field, ms), n, B, s, n, ms, u); }));
+  RC_TRY(launch_sswu(n, u, q, s));
   if (cof_engine) {
-    const unsigned blocks = cof_blocks;
+    const dim3 blocks(cof_blocks), eng(ENG_BLOCK);
     // (the k_cof_* kernels take the planes' base and address them by COF_* themselves)
     uint32_t *const w = cof.pj, *const pa = cof.pa, *const psia = cof.psia, *const t1 = cof.t1, *const t0a = cof.t0a,
                     *const t2 = cof.t2;
-    uint32_t* lines = (uint32_t*)L.lines.p;
-    hipLaunchKernelGGL(k_cof_prep, dim3(grid_for(n, B)), dim3(B), 0, s, n, (const uint32_t*)q, w);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_eng_lines, dim3(blocks), dim3(ENG_BLOCK), 0, s, n, (size_t)0, n,
-                       (const uint32_t*)pa, n, (const uint32_t*)nullptr, (const uint32_t*)psia, (const uint32_t*)nullptr,
-                       consts, lines, (uint8_t*)nullptr, t1);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_cof_mid, dim3(grid_for(n, B)), dim3(B), 0, s, n, w);
-    HIP_TRY(hipGetLastError());
+    uint32_t* lines = L.lines.u32();
+    RC_TRY(launch_n(k_cof_prep, n, B, s, n, q, w));
+    RC_TRY(launch(k_eng_lines, blocks, eng, s, n, 0, n, pa, n, nullptr, psia, nullptr, consts, lines, nullptr, t1));
+    RC_TRY(launch_n(k_cof_mid, n, B, s, n, w));
     // U (everything but [x^2]P) on the second stream beside the second pass
     const bool side = s_dec != nullptr;
     const hipStream_t su = side ? s_dec : s;
-    if (side) {
-      HIP_TRY(hipEventRecord(c->cof_ev[0], s));
-      HIP_TRY(hipStreamWaitEvent(su, c->cof_ev[0], 0));
-    }
-    hipLaunchKernelGGL(k_cof_partial, dim3(grid_for(n, B)), dim3(B), 0, su, n, w);
-    HIP_TRY(hipGetLastError());
+    if (side) RC_TRY(stream_after(su, s, c->cof_ev[0]));
+    RC_TRY(launch_n(k_cof_partial, n, B, su, n, w));
     if (side) HIP_TRY(hipEventRecord(c->cof_ev[1], su));
-    hipLaunchKernelGGL(k_eng_lines, dim3(blocks), dim3(ENG_BLOCK), 0, s, n, (size_t)0, n,
-                       (const uint32_t*)t0a, n, (const uint32_t*)nullptr, (const uint32_t*)t0a, (const uint32_t*)nullptr,
-                       consts, lines, (uint8_t*)nullptr, t2);
-    HIP_TRY(hipGetLastError());
+    RC_TRY(launch(k_eng_lines, blocks, eng, s, n, 0, n, t0a, n, nullptr, t0a, nullptr, consts, lines, nullptr, t2));
     if (side) HIP_TRY(hipStreamWaitEvent(s, c->cof_ev[1], 0));
-    hipLaunchKernelGGL(k_cof_final, dim3(grid_for(n, B)), dim3(B), 0, s, n, (const uint32_t*)w, h, (uint32_t*)L.h_z.p);
+    RC_TRY(launch_n(k_cof_final, n, B, s, n, w, h, hz));
   } else {
-    hipLaunchKernelGGL(k_h2c_finish, dim3(grid_for(n, B)), dim3(B), 0, s, n, (const uint32_t*)q, park, redo, h,
-                       (uint32_t*)L.h_z.p);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_h2c_finish_redo, dim3(grid_for(n, B)), dim3(B), 0, s, n, (const uint8_t*)redo, park, h,
-                       (uint32_t*)L.h_z.p);
+    RC_TRY(launch_n(k_h2c_finish, n, B, s, n, q, park, redo, h, hz));
+    RC_TRY(launch_n(k_h2c_finish_redo, n, B, s, n, redo, park, h, hz));
   }
-  HIP_TRY(hipGetLastError());
   mark(c, s, "h_affine");
-  hipLaunchKernelGGL(k_g2_batch_affine, dim3(grid_for((n + 15) / 16, B)), dim3(B), 0, s, n, h,
-                     (const uint32_t*)L.h_z.p, (uint32_t*)L.h_pre.p);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_g2_batch_affine, (n + 15) / 16, B, s, n, h, hz, L.h_pre.u32()));
   if (s_dec) {
     HIP_TRY(hipStreamWaitEvent(s, c->lane_ev[1], 0));  // the decode (queued first on s_dec)
     join.release();
-  } else {
-    mark(c, s, "decode_g2");
-    if ((rc = stager_wait_sig(stg, slice, s))) return rc;
-    HIP_TRY(decode(s));
+    return DGPU_OK;
   }
-  return DGPU_OK;
+  mark(c, s, "decode_g2");
+  if ((rc = stager_wait_sig(stg, slice, s))) return rc;
+  return decode(s);
 }
 
 // msg_src of items [off, off + cnt) of m.  The linked form keeps its base
@@ -1415,10 +1359,8 @@ int verify_status_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a
   const size_t n = a.n;
   int rc;
   if ((rc = c->status.ensure(n))) return rc;
-  uint8_t* st = (uint8_t*)c->status.p;
-  c->n_ev = 0;
-  c->ev_overflow = false;
-  c->rlc_pending = false;
+  uint8_t* st = c->status.u8();
+  call_reset(c);
   if (a.mode == DGPU_MODE_RLC && n >= c->rlc_min) {
     // root first, by bucket MSM; the tree of leaves only when it fails
     if ((rc = stager_wait_all(stg, s)) || (rc = rlc_points_locked(c, a, s))) return rc;
@@ -1427,17 +1369,14 @@ int verify_status_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a
     std::vector<uint8_t> fail;
     if ((rc = rlc_check_locked(c, key, std::vector<uint32_t>{0}, 1, root.P, root.S, s, &fail))) return rc;
     if (!fail[0] || a.n == 1) {
-      if (fail[0]) {  // one round: its leaf is the root
-        hipLaunchKernelGGL(k_rlc_mark, dim3(1), dim3(64), 0, s, (size_t)1, (const uint32_t*)c->rlc_idx.p,
-                           (const uint8_t*)c->rlc_fail.p, (uint8_t*)c->status.p);
-        HIP_TRY(hipGetLastError());
-      }
+      if (fail[0])  // one round: its leaf is the root
+        RC_TRY(launch(k_rlc_mark, dim3(1), dim3(64), s, 1, c->rlc_idx.u32(), c->rlc_fail.u8(), st));
       return DGPU_OK;
     }
     return rlc_resolve_locked(c, key, a, s, root, true);
   }
   if (sig_on_g1(a.scheme)) return (rc = stager_wait_all(stg, s)) ? rc : verify_g1_locked(c, key, a, st, s);
-  const uint32_t* consts = (const uint32_t*)key->consts.p;
+  const uint32_t* consts = key->consts.u32();
   lane_scratch &L0 = c->lane[0], &L1 = c->lane[1];
   // Two lanes (streams) on the two halves of the batch once it spans more
   // than one engine chunk; lane 1 starts when lane 0's hash/decode kernels
@@ -1457,16 +1396,15 @@ int verify_status_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a
   auto slice_job = [&](lane_scratch& L, size_t cnt, uint8_t* sst) {
     return pairing_job{.consts = consts,
                        .n = cnt,
-                       .h = (const uint32_t*)L.h_pts.p,
-                       .sg = (const uint32_t*)L.sig_pts.p,
+                       .h = L.h_pts.u32(),
+                       .sg = L.sig_pts.u32(),
                        .st = sst,
                        .lane = &L,
                        .sig_subgroup = sub};
   };
   if (!two) return eng_pairing_locked(c, slice_job(L0, n, st), s);
   hipStream_t s2 = c->stream2;
-  HIP_TRY(hipEventRecord(c->lane_ev[0], s));
-  HIP_TRY(hipStreamWaitEvent(s2, c->lane_ev[0], 0));
+  RC_TRY(stream_after(s2, s, c->lane_ev[0]));
   if ((rc = eng_pairing_locked(c, slice_job(L0, n0, st), s))) return rc;
   // the remaining slices alternate between the lanes (stream order keeps each
   // lane's buffers in use by one slice at a time), so a slice's hash runs
@@ -1483,9 +1421,7 @@ int verify_status_locked(dgpu_ctx* c, const key_entry* key, const verify_args& a
       return rc;
     if ((rc = eng_pairing_locked(c, slice_job(*LL[ln], nk, st + off), ss[ln]))) return rc;
   }
-  HIP_TRY(hipEventRecord(c->lane_ev[1], s2));
-  HIP_TRY(hipStreamWaitEvent(s, c->lane_ev[1], 0));
-  return DGPU_OK;
+  return stream_after(s, s2, c->lane_ev[1]);
 }
 
 // ---------------------------------------------------------------- the RLC shard protocol
@@ -1506,8 +1442,7 @@ int rlc_shard_root_locked(dgpu_ctx* c, const verify_args& a, uint8_t* d_root, hi
   rlc_root_layout root;
   int rc;
   if ((rc = c->status.ensure(a.n))) return rc;
-  c->n_ev = 0;
-  c->ev_overflow = false;
+  call_reset(c);  // (the callers cancelled a pending root before they staged anything)
   if ((rc = rlc_points_locked(c, a, s)) || (rc = rlc_root_msm_locked(c, a, s, c->msm_root, &root))) return rc;
   HIP_TRY(hipMemcpyAsync(d_root, root.P, layout_bytes<rlc_root_layout>(G.jw), hipMemcpyDeviceToDevice, s));
   return DGPU_OK;
@@ -1521,13 +1456,9 @@ int rlc_node_check_locked(dgpu_ctx* c, const key_entry* key, size_t n_roots, con
   int rc = carve(c->rlc_root, &sum, rlc_geom_of(key->g2key).jw);
   if (rc) return rc;
   mark(c, s, "rlc_root_sum");
-  if (key->g2key)
-    hipLaunchKernelGGL(k_rlc_sum_roots<G1Ops>, dim3(1), dim3(64), 0, s, (int)n_roots, (const uint32_t*)d_roots, sum.P,
-                       sum.S);
-  else
-    hipLaunchKernelGGL(k_rlc_sum_roots<G2Ops>, dim3(1), dim3(64), 0, s, (int)n_roots, (const uint32_t*)d_roots, sum.P,
-                       sum.S);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(with_group(key->g2key, [&](auto gr) {
+    return launch(k_rlc_sum_roots<GROUP_OF(gr)>, dim3(1), dim3(64), s, (int)n_roots, (const uint32_t*)d_roots, sum.P, sum.S);
+  }));
   std::vector<uint8_t> f;
   if ((rc = rlc_check_locked(c, key, std::vector<uint32_t>{0}, 1, sum.P, sum.S, s, &f))) return rc;
   *fail = f[0] != 0;
@@ -1549,15 +1480,12 @@ int rlc_shard_finish_locked(dgpu_ctx* c, const key_entry* key, const verify_args
 // memory.  Closes the call's stage markers.
 int pack_results_locked(dgpu_ctx* c, const verify_args& a, uint8_t* d_bits, uint8_t* d_rand, hipStream_t s) {
   const unsigned B = 256;
-  const uint8_t* st = (const uint8_t*)c->status.p;
+  const uint8_t* st = c->status.u8();
   mark(c, s, "pack_verdicts");
-  hipLaunchKernelGGL(k_pack_verdicts, dim3(grid_for((a.n + 7) / 8, B)), dim3(B), 0, s, a.n, st, d_bits);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_pack_verdicts, (a.n + 7) / 8, B, s, a.n, st, d_bits));
   if (d_rand) {
     mark(c, s, "randomness");
-    hipLaunchKernelGGL(k_randomness, dim3(grid_for(a.n, B)), dim3(B), 0, s, a.n, a.sigs, a.sig_stride, a.sig_len, st,
-                       d_rand);
-    HIP_TRY(hipGetLastError());
+    RC_TRY(launch_n(k_randomness, a.n, B, s, a.n, a.sigs, a.sig_stride, a.sig_len, st, d_rand));
   }
   mark(c, s);
   return DGPU_OK;
@@ -1692,11 +1620,9 @@ int ring_rows_locked(dgpu_ctx* c, const rows_src& R, size_t a, size_t b) {
     HIP_TRY(hipEventRecord(c->ring_ev[k], c->stream_copy));
     c->ring_busy[k] = true;
     // the piece's rows lie in [0, pos[e]) of the packed run: nothing behind it is on the device yet
-    hipLaunchKernelGGL(k_ingest_rows, dim3(grid_for(m, INGEST_ROWS_PER_WAVE)), dim3(INGEST_ROWS_PER_WAVE), 0,
-                       c->stream_copy, m, (const uint8_t*)R.dev.bytes, (size_t)R.pos[e], (const uint64_t*)R.dev.off + a,
-                       (const uint32_t*)R.dev.len + a, R.d_rounds + a, R.d_sigs + a * R.sig_stride, R.sig_stride,
-                       R.d_sig_len + a, R.d_prev + a * R.prev_stride, R.prev_stride, R.d_prev_len + a, R.d_ok + a);
-    HIP_TRY(hipGetLastError());
+    RC_TRY(launch_n(k_ingest_rows, m, INGEST_ROWS_PER_WAVE, c->stream_copy, m, R.dev.bytes, R.pos[e], R.dev.off + a,
+                    R.dev.len + a, R.d_rounds + a, R.d_sigs + a * R.sig_stride, R.sig_stride, R.d_sig_len + a,
+                    R.d_prev + a * R.prev_stride, R.prev_stride, R.d_prev_len + a, R.d_ok + a));
     a = e;
   }
   return DGPU_OK;
@@ -1886,13 +1812,13 @@ int rows_prepare_locked(dgpu_ctx* c, const verify_args& a) {
       (rc = c->in_row_ok.ensure(a.n)) || (rc = carve(c->in_rows, &rows->dev, (size_t)rows->pos[a.n], a.n)))
     return rc;
   if (rows->keys && (rc = c->in_keys.ensure(a.n * 8))) return rc;
-  rows->d_rounds = (uint64_t*)c->in_rounds.p;
-  rows->d_sigs = (uint8_t*)c->in_sigs.p;
-  rows->d_sig_len = (uint32_t*)c->in_sig_len.p;
-  rows->d_prev = (uint8_t*)c->in_prev.p;
-  rows->d_prev_len = (uint32_t*)c->in_prev_len.p;
-  rows->d_ok = (uint8_t*)c->in_row_ok.p;
-  rows->d_keys = rows->keys ? (uint64_t*)c->in_keys.p : nullptr;
+  rows->d_rounds = c->in_rounds.u64();
+  rows->d_sigs = c->in_sigs.u8();
+  rows->d_sig_len = c->in_sig_len.u32();
+  rows->d_prev = c->in_prev.u8();
+  rows->d_prev_len = c->in_prev_len.u32();
+  rows->d_ok = c->in_row_ok.u8();
+  rows->d_keys = rows->keys ? c->in_keys.u64() : nullptr;
   return DGPU_OK;
 }
 
@@ -1944,10 +1870,10 @@ int results_out_locked(dgpu_ctx* c, const verify_args& a, uint8_t* d_bits, uint8
   int rc;
   if (!d_bits) {
     if ((rc = c->out_bits.ensure((a.n + 7) / 8))) return rc;
-    d_bits = (uint8_t*)c->out_bits.p;
+    d_bits = c->out_bits.u8();
   }
   if (rand32 && (rc = c->out_rand.ensure(a.n * 32))) return rc;
-  if ((rc = pack_results_locked(c, a, d_bits, rand32 ? (uint8_t*)c->out_rand.p : nullptr, s))) return rc;
+  if ((rc = pack_results_locked(c, a, d_bits, rand32 ? c->out_rand.u8() : nullptr, s))) return rc;
   if (bits) HIP_TRY(hipMemcpyAsync(bits, d_bits, (a.n + 7) / 8, hipMemcpyDeviceToHost, s));
   if (reason) HIP_TRY(hipMemcpyAsync(reason, c->status.p, a.n, reason_kind, s));
   if (rand32) HIP_TRY(hipMemcpyAsync(rand32, c->out_rand.p, a.n * 32, hipMemcpyDeviceToHost, s));
@@ -2012,18 +1938,13 @@ int faulty_rounds_locked(dgpu_ctx* c, uint64_t first, size_t count, size_t n, co
   if (rc) return rc;
   const size_t nblk = check_blocks(count);
   HIP_TRY(hipMemsetAsync(L.map, 0xFF, count * 4, s));  // CHECK_NO_ROW everywhere
-  if (n)
-    hipLaunchKernelGGL(k_check_map, dim3(grid_for(n, CHECK_BLOCK)), dim3(CHECK_BLOCK), 0, s, first, count, n, d_keys,
-                       L.map);
-  hipLaunchKernelGGL(k_check_classify, dim3((unsigned)nblk), dim3(CHECK_BLOCK), 0, s, first, count, n,
-                     (const uint32_t*)L.map, d_row_ok, d_rounds, d_status, L.flags, L.blk_faulty, L.blk_left);
-  hipLaunchKernelGGL(k_check_scan, dim3(1), dim3(CHECK_BLOCK), 0, s, nblk, L.blk_faulty, L.blk_left, d_counts);
-  hipLaunchKernelGGL(k_check_scatter, dim3((unsigned)nblk), dim3(CHECK_BLOCK), 0, s, first, count, n,
-                     (const uint32_t*)L.map, d_row_ok, d_rounds, d_status, (const uint8_t*)L.flags,
-                     (const uint64_t*)L.blk_faulty, (const uint64_t*)L.blk_left, d_faulty_pos, d_faulty_val, faulty_cap,
-                     d_left_rows, left_cap);
-  HIP_TRY(hipGetLastError());
-  return DGPU_OK;
+  const dim3 blocks((unsigned)nblk), B(CHECK_BLOCK);
+  if (n) RC_TRY(launch_n(k_check_map, n, CHECK_BLOCK, s, first, count, n, d_keys, L.map));
+  RC_TRY(launch(k_check_classify, blocks, B, s, first, count, n, L.map, d_row_ok, d_rounds, d_status, L.flags,
+                L.blk_faulty, L.blk_left));
+  RC_TRY(launch(k_check_scan, dim3(1), B, s, nblk, L.blk_faulty, L.blk_left, d_counts));
+  return launch(k_check_scatter, blocks, B, s, first, count, n, L.map, d_row_ok, d_rounds, d_status, L.flags, L.blk_faulty,
+                L.blk_left, d_faulty_pos, d_faulty_val, faulty_cap, d_left_rows, left_cap);
 }
 
 // The lists of one context on the host: the totals, and the entries below the caps.
@@ -2046,9 +1967,8 @@ int check_lists_locked(dgpu_ctx* c, uint64_t first, size_t count, size_t n, cons
   check_lists_layout D;
   int rc = carve(c->chk_out, &D, faulty_cap, left_cap);
   if (rc) return rc;
-  if ((rc = faulty_rounds_locked(c, first, count, n, d_keys, (const uint8_t*)c->in_row_ok.p,
-                                 (const uint64_t*)c->in_rounds.p, (const uint8_t*)c->status.p, D.faulty_pos,
-                                 D.faulty_val, faulty_cap, D.left_rows, left_cap, D.counts, s)))
+  if ((rc = faulty_rounds_locked(c, first, count, n, d_keys, c->in_row_ok.u8(), c->in_rounds.u64(), c->status.u8(),
+                                 D.faulty_pos, D.faulty_val, faulty_cap, D.left_rows, left_cap, D.counts, s)))
     return rc;
   uint64_t counts[2];
   HIP_TRY(hipMemcpyAsync(counts, D.counts, sizeof counts, hipMemcpyDeviceToHost, s));
@@ -2265,28 +2185,29 @@ int dgpu_open(int device, dgpu_ctx** out) {
 
 void dgpu_close(dgpu_ctx* c) {
   if (!c) return;
-  hipSetDevice(c->device);
-  if (c->stream) hipStreamSynchronize(c->stream);
-  if (c->stream2) hipStreamSynchronize(c->stream2);
-  if (c->done) hipEventSynchronize(c->done);
-  for (hipEvent_t e : c->ev) hipEventDestroy(e);
+  // teardown: nothing to do about a failure here, the results are dropped on purpose
+  (void)hipSetDevice(c->device);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  if (c->stream2) (void)hipStreamSynchronize(c->stream2);
+  if (c->done) (void)hipEventSynchronize(c->done);
+  for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->lane_ev)
-    if (e) hipEventDestroy(e);
+    if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->cof_ev)
-    if (e) hipEventDestroy(e);
-  if (c->done) hipEventDestroy(c->done);
-  if (c->ky_ev) hipEventDestroy(c->ky_ev);
-  if (c->ky_host) hipHostFree(c->ky_host);
+    if (e) (void)hipEventDestroy(e);
+  if (c->done) (void)hipEventDestroy(c->done);
+  if (c->ky_ev) (void)hipEventDestroy(c->ky_ev);
+  if (c->ky_host) (void)hipHostFree(c->ky_host);
   if (c->stream_copy) {
-    hipStreamSynchronize(c->stream_copy);
-    hipStreamDestroy(c->stream_copy);
+    (void)hipStreamSynchronize(c->stream_copy);
+    (void)hipStreamDestroy(c->stream_copy);
   }
   for (int k = 0; k < 2; ++k) {
-    if (c->ring_ev[k]) hipEventDestroy(c->ring_ev[k]);
-    if (c->ring[k]) hipHostFree(c->ring[k]);
+    if (c->ring_ev[k]) (void)hipEventDestroy(c->ring_ev[k]);
+    if (c->ring[k]) (void)hipHostFree(c->ring[k]);
   }
-  if (c->stream2) hipStreamDestroy(c->stream2);
-  if (c->stream) hipStreamDestroy(c->stream);
+  if (c->stream2) (void)hipStreamDestroy(c->stream2);
+  if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;  // the device buffers go with the context: every stream that used them has been drained
 }
 
@@ -2373,11 +2294,8 @@ int dgpu_decode_rows_device(dgpu_ctx* c, size_t n, const uint8_t* d_rows, size_t
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = caller_stream(stream);
   stream_order ord(c, s);
-  hipLaunchKernelGGL(k_ingest_rows, dim3(grid_for(n, INGEST_ROWS_PER_WAVE)), dim3(INGEST_ROWS_PER_WAVE), 0, s, n, d_rows,
-                     rows_bytes, d_row_off, d_row_len, d_rounds, d_sigs, sig_stride, d_sig_len, d_prev, prev_stride,
-                     d_prev_len, d_ok);
-  HIP_TRY(hipGetLastError());
-  return DGPU_OK;
+  return launch_n(k_ingest_rows, n, INGEST_ROWS_PER_WAVE, s, n, d_rows, rows_bytes, d_row_off, d_row_len, d_rounds, d_sigs,
+                  sig_stride, d_sig_len, d_prev, prev_stride, d_prev_len, d_ok);
 }
 
 int dgpu_verify_rows(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t pk_len, size_t n, const uint8_t* base,
@@ -2689,12 +2607,11 @@ int dgpu_digest_batch(dgpu_ctx* c, int scheme, size_t n, const uint64_t* rounds,
     if ((rc = lengths_check(prev_len, n, prev_stride, PREV_LEN_FMT))) return rc;
     if (prev_stride) HIP_TRY(hipMemcpyAsync(c->in_prev.p, prev, n * prev_stride, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(c->in_prev_len.p, prev_len, n * 4, hipMemcpyHostToDevice, s));
-    d_prev = (const uint8_t*)c->in_prev.p;
-    d_prev_len = (const uint32_t*)c->in_prev_len.p;
+    d_prev = c->in_prev.u8();
+    d_prev_len = c->in_prev_len.u32();
   }
-  hipLaunchKernelGGL(k_digest, dim3(grid_for(n, 256)), dim3(256), 0, s, n, (const uint64_t*)c->in_rounds.p, d_prev,
-                     prev_stride, d_prev_len, chained ? 1 : 0, (uint8_t*)c->misc.p);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_digest, n, 256, s, n, c->in_rounds.u64(), d_prev, prev_stride, d_prev_len, chained ? 1 : 0,
+                  c->misc.u8()));
   HIP_TRY(hipMemcpyAsync(out32, c->misc.p, n * 32, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return DGPU_OK;
@@ -2718,13 +2635,11 @@ int dgpu_hash_to_curve(dgpu_ctx* c, int scheme, size_t n, const uint8_t* msgs, s
     return rc;
   if (msg_stride) HIP_TRY(hipMemcpyAsync(c->in_msgs.p, msgs, n * msg_stride, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(c->in_msg_len.p, msg_len, n * 4, hipMemcpyHostToDevice, s));
-  const msg_src m = raw_src((const uint8_t*)c->in_msgs.p, msg_stride, (const uint32_t*)c->in_msg_len.p);
+  const msg_src m = raw_src(c->in_msgs.u8(), msg_stride, c->in_msg_len.u32());
   if (g1)
-    hipLaunchKernelGGL(k_hash_to_g1_msgs, dim3(grid_for(n, 256)), dim3(256), 0, s, n, m,
-                       scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, (uint8_t*)c->misc.p);
+    RC_TRY(launch_n(k_hash_to_g1_msgs, n, 256, s, n, m, scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, c->misc.u8()));
   else
-    hipLaunchKernelGGL(k_hash_to_g2_msgs, dim3(grid_for(n, 256)), dim3(256), 0, s, n, m, (uint8_t*)c->misc.p);
-  HIP_TRY(hipGetLastError());
+    RC_TRY(launch_n(k_hash_to_g2_msgs, n, 256, s, n, m, c->misc.u8()));
   HIP_TRY(hipMemcpyAsync(out, c->misc.p, n * ob, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return DGPU_OK;
@@ -2773,10 +2688,9 @@ int dgpu_sign(dgpu_ctx* c, int scheme, const uint8_t* sk_be32, size_t n, const u
     return rc;
   if (msg_stride) HIP_TRY(hipMemcpyAsync(c->in_msgs.p, msgs, n * msg_stride, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(c->in_msg_len.p, msg_len, n * 4, hipMemcpyHostToDevice, s));
-  const msg_src m = raw_src((const uint8_t*)c->in_msgs.p, msg_stride, (const uint32_t*)c->in_msg_len.p);
-  hipLaunchKernelGGL(k_sign_msgs, dim3(grid_for(n, 64)), dim3(64), 0, s, n, m, g1 ? 1 : 0,
-                     scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, scalar_from_be32(sk_be32), (uint8_t*)c->misc.p, ob);
-  HIP_TRY(hipGetLastError());
+  const msg_src m = raw_src(c->in_msgs.u8(), msg_stride, c->in_msg_len.u32());
+  RC_TRY(launch_n(k_sign_msgs, n, 64, s, n, m, g1 ? 1 : 0, scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0,
+                  scalar_from_be32(sk_be32), c->misc.u8(), ob));
   HIP_TRY(hipMemcpyAsync(out_sigs, c->misc.p, n * ob, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return DGPU_OK;
@@ -2795,9 +2709,7 @@ int dgpu_decode_g1_points(dgpu_ctx* c, size_t n, const uint8_t* in48, int* rc_ou
   HIP_TRY(hipMemcpyAsync(c->in_msgs.p, in48, n * 48, hipMemcpyHostToDevice, s));
   int* const d_rc = M.rc;
   uint8_t* const d_xy = M.xy;
-  hipLaunchKernelGGL(k_decode_g1_points, dim3(grid_for(n, 64)), dim3(64), 0, s, n, (const uint8_t*)c->in_msgs.p, d_rc,
-                     d_xy);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_decode_g1_points, n, 64, s, n, c->in_msgs.u8(), d_rc, d_xy));
   HIP_TRY(hipMemcpyAsync(rc_out, d_rc, n * 4, hipMemcpyDeviceToHost, s));
   if (xy96) HIP_TRY(hipMemcpyAsync(xy96, d_xy, n * 96, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -2828,22 +2740,13 @@ int dgpu_decode_signatures(dgpu_ctx* c, int scheme, size_t n, const uint8_t* sig
   if (sig_stride) HIP_TRY(hipMemcpyAsync(c->in_sigs.p, sigs, n * sig_stride, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(c->in_sig_len.p, sig_len, n * 4, hipMemcpyHostToDevice, s));
   const msg_src m = beacon_src(nullptr, nullptr, 0, nullptr, false);  // no message part: never a bad record
-  const uint8_t* d_sigs = (const uint8_t*)c->in_sigs.p;
-  const uint32_t* d_len = (const uint32_t*)c->in_sig_len.p;
-  uint32_t* pts = (uint32_t*)c->lane[0].sig_pts.p;
-  uint8_t* st = (uint8_t*)c->status.p;
-  if (g1)
-    hipLaunchKernelGGL(k_decode_g1_sigs<msg_src>, dim3(grid_for(n, 256)), dim3(256), 0, s, n, d_sigs, sig_stride, d_len, m, pts,
-                       st);
-  else
-    hipLaunchKernelGGL(k_decode_g2_sigs_sub<msg_src>, dim3(grid_for(n, 256)), dim3(256), 0, s, n, d_sigs, sig_stride, d_len, m,
-                       pts, st);
-  HIP_TRY(hipGetLastError());
+  uint32_t* pts = c->lane[0].sig_pts.u32();
+  uint8_t* st = c->status.u8();
+  RC_TRY(launch_n(g1 ? k_decode_g1_sigs<msg_src> : k_decode_g2_sigs_sub<msg_src>, n, 256, s, n, c->in_sigs.u8(), sig_stride,
+                  c->in_sig_len.u32(), m, pts, st));
   HIP_TRY(hipMemcpyAsync(reason, st, n, hipMemcpyDeviceToHost, s));
   if (xy) {
-    hipLaunchKernelGGL(k_fp_soa_to_be48, dim3(grid_for(n * nfp, 256)), dim3(256), 0, s, n, nfp, (const uint32_t*)pts, 0,
-                       (uint8_t*)c->misc.p);
-    HIP_TRY(hipGetLastError());
+    RC_TRY(launch_n(k_fp_soa_to_be48, n * nfp, 256, s, n, nfp, pts, 0, c->misc.u8()));
     HIP_TRY(hipMemcpyAsync(xy, c->misc.p, n * nfp * 48, hipMemcpyDeviceToHost, s));
   }
   HIP_TRY(hipStreamSynchronize(s));
@@ -2868,15 +2771,9 @@ int dgpu_decode_pubkey(dgpu_ctx* c, int scheme, const uint8_t* pk, size_t len, u
   uint32_t* const d_pt = M.pt;
   int* const d_rc = M.rc;
   HIP_TRY(hipMemcpyAsync(d_in, pk, want, hipMemcpyHostToDevice, s));
-  if (g2key)
-    hipLaunchKernelGGL(k_decode_g2_pk, dim3(1), dim3(64), 0, s, (const uint8_t*)d_in, d_pt, d_rc);
-  else
-    hipLaunchKernelGGL(k_decode_g1_pk, dim3(1), dim3(64), 0, s, (const uint8_t*)d_in, d_pt, d_rc);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch(g2key ? k_decode_g2_pk : k_decode_g1_pk, dim3(1), dim3(64), s, d_in, d_pt, d_rc));
   const int nfp = g2key ? 4 : 2;
-  hipLaunchKernelGGL(k_fp_soa_to_be48, dim3(1), dim3(64), 0, s, (size_t)1, nfp, (const uint32_t*)d_pt, g2key ? 0 : 1,
-                     d_xy);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch(k_fp_soa_to_be48, dim3(1), dim3(64), s, 1, nfp, d_pt, g2key ? 0 : 1, d_xy));
   int drc = -1;
   uint8_t host[192];
   HIP_TRY(hipMemcpyAsync(&drc, d_rc, sizeof drc, hipMemcpyDeviceToHost, s));
@@ -2897,13 +2794,8 @@ int dgpu_derive_pubkey(dgpu_ctx* c, int scheme, const uint8_t* sk_be32, uint8_t*
   stream_order ord(c, c->stream);
   int rc = c->misc.ensure(128);
   if (rc) return rc;
-  if (sig_on_g1(scheme))
-    hipLaunchKernelGGL(k_derive_pubkey_g2, dim3(1), dim3(64), 0, c->stream, scalar_from_be32(sk_be32),
-                       (uint8_t*)c->misc.p);
-  else
-    hipLaunchKernelGGL(k_derive_pubkey, dim3(1), dim3(64), 0, c->stream, scalar_from_be32(sk_be32),
-                       (uint8_t*)c->misc.p);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch(sig_on_g1(scheme) ? k_derive_pubkey_g2 : k_derive_pubkey, dim3(1), dim3(64), c->stream,
+                scalar_from_be32(sk_be32), c->misc.u8()));
   HIP_TRY(hipMemcpyAsync(pk_out, c->misc.p, want, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return DGPU_OK;
@@ -2940,20 +2832,18 @@ int dgpu_make_chain(dgpu_ctx* c, int scheme, const uint8_t* sk_be32, size_t n_se
   if (e == hipSuccess) e = hipMemcpyAsync(d_prev.p, pv.data(), n_seg * 96, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(d_plen.p, pl.data(), n_seg * 4, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemsetAsync(d_sigs.p, 0, n_seg * seg_len * 96, s);
-  for (size_t j = 0; e == hipSuccess && sig_on_g1(scheme) && j < seg_len; ++j) {
-    hipLaunchKernelGGL(k_sign_step_g1, dim3(grid_for(n_seg, 64)), dim3(64), 0, s, n_seg, (const uint64_t*)d_first.p,
-                       (uint64_t)j, scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, sk, (uint8_t*)d_sigs.p + j * 96,
-                       seg_len * 96);
-    e = hipGetLastError();
-  }
-  for (size_t j = 0; e == hipSuccess && !sig_on_g1(scheme) && j < seg_len; ++j) {
+  if (e != hipSuccess) return set_err(DGPU_EDEVICE, "make_chain: %s", hipGetErrorString(e));
+  for (size_t j = 0; j < seg_len; ++j) {
     // segment-major output: round j of segment s at (s*seg_len + j)*96
-    hipLaunchKernelGGL(k_sign_step, dim3(grid_for(n_seg, 64)), dim3(64), 0, s, n_seg, (const uint64_t*)d_first.p,
-                       (uint64_t)j, (uint8_t*)d_prev.p, (uint32_t*)d_plen.p, chained ? 1 : 0, sk,
-                       (uint8_t*)d_sigs.p + j * 96, seg_len * 96);
-    e = hipGetLastError();
+    uint8_t* const out = d_sigs.u8() + j * 96;
+    if (sig_on_g1(scheme))
+      RC_TRY(launch_n(k_sign_step_g1, n_seg, 64, s, n_seg, d_first.u64(), j, scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, sk,
+                      out, seg_len * 96));
+    else
+      RC_TRY(launch_n(k_sign_step, n_seg, 64, s, n_seg, d_first.u64(), j, d_prev.u8(), d_plen.u32(), chained ? 1 : 0, sk,
+                      out, seg_len * 96));
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(sigs_out, d_sigs.p, n_seg * seg_len * 96, hipMemcpyDeviceToHost, s);
+  e = hipMemcpyAsync(sigs_out, d_sigs.p, n_seg * seg_len * 96, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) return set_err(DGPU_EDEVICE, "make_chain: %s", hipGetErrorString(e));
   return DGPU_OK;

@@ -51,28 +51,20 @@ int keyed_table_locked(dgpu_ctx* c, bool g2key, size_t n_keys, const uint8_t* ke
   HIP_TRY(hipMemcpyAsync(T->in, c->ky_host, bytes, hipMemcpyHostToDevice, s));
   HIP_TRY(hipEventRecord(c->ky_ev, s));
   c->ky_ev_used = true;
-  if (g2key)
-    hipLaunchKernelGGL(k_decode_commits_g2, dim3(grid_for(n_keys, 64)), dim3(64), 0, s, (int)n_keys,
-                       (const uint8_t*)T->in, T->pts, T->rc);
-  else
-    hipLaunchKernelGGL(k_decode_commits, dim3(grid_for(n_keys, 64)), dim3(64), 0, s, (int)n_keys, (const uint8_t*)T->in,
-                       T->pts, T->rc);
-  HIP_TRY(hipGetLastError());
-  return DGPU_OK;
+  return launch_n(g2key ? k_decode_commits_g2 : k_decode_commits, n_keys, 64, s, (int)n_keys, T->in, T->pts, T->rc);
 }
 
-// One pairing batch of m items with a key per item (G2KEY: G1 signatures).
+// One pairing batch of m items with a key per item (g2key: G1 signatures).
 // The signatures behind these items were subgroup-checked at decode.
-template <bool G2KEY>
-pairing_job keyed_items_job(dgpu_ctx* c, size_t m, const uint32_t* h, const uint32_t* sg, const uint32_t* keys,
-                            uint8_t* st) {
-  return {.consts = (const uint32_t*)c->eng_consts.p,
+pairing_job keyed_items_job(dgpu_ctx* c, bool g2key, size_t m, const uint32_t* h, const uint32_t* sg,
+                            const uint32_t* keys, uint8_t* st) {
+  return {.consts = c->eng_consts.u32(),
           .n = m,
           .h = h,
           .sg = sg,
           .st = st,
-          .pk_items = G2KEY ? nullptr : keys,
-          .g1form_keys = G2KEY ? keys : nullptr};
+          .pk_items = g2key ? nullptr : keys,
+          .g1form_keys = g2key ? keys : nullptr};
 }
 
 // What the two front ends hand to the RLC core (device pointers): n items,
@@ -98,9 +90,10 @@ struct keyed_rlc_in {
 // keys: leaves, grouping by key, load-balanced per-key sums, one node check
 // per non-empty key, then the exact check of the failing keys' items (one
 // stream synchronisation to size it).
-template <class Gr, bool G2KEY>
-int keyed_rlc_locked(dgpu_ctx* c, const keyed_rlc_in& in, hipStream_t s) {
+template <class Gr>
+int keyed_rlc_t(dgpu_ctx* c, const keyed_rlc_in& in, hipStream_t s) {
   using M = GrMem<Gr>;
+  constexpr bool G2KEY = std::is_same<Gr, G1Ops>::value;  // G1 signatures: G2 keys
   const unsigned B = 256;
   const size_t n = in.n, n_keys = in.n_groups;
   const uint32_t ng = (uint32_t)n_keys;
@@ -112,43 +105,29 @@ int keyed_rlc_locked(dgpu_ctx* c, const keyed_rlc_in& in, hipStream_t s) {
   int rc = carve(c->ky_rlc, &K, n, n_keys, NT, m, M::AFF, M::JAC, kw);
   if (rc) return rc;
   mark(c, s, "keyed_leaves");
-  hipLaunchKernelGGL(k_keyed_leaves<Gr>, dim3(grid_for(2 * n, B)), dim3(B), 0, s, n, in.seed, h,
-                     in.h_stride, in.h_idx, sg, (const uint8_t*)st, K.leaf_p, K.leaf_s);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_keyed_leaves<Gr>, 2 * n, B, s, n, in.seed, h, in.h_stride, in.h_idx, sg, st, K.leaf_p, K.leaf_s));
   mark(c, s, "keyed_group");
   HIP_TRY(hipMemsetAsync(K.counts, 0, n_keys * 4, s));
   HIP_TRY(hipMemsetAsync(K.nfail, 0, 4, s));
-  hipLaunchKernelGGL(k_keyed_count, dim3(grid_for(n, B)), dim3(B), 0, s, n, ng, d_key_idx, (const uint8_t*)st, K.counts);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_keyed_scan, dim3(1), dim3(KEYED_SCAN_THREADS), 0, s, ng, (const uint32_t*)K.counts, K.offsets,
-                     K.cursor, K.cpos, K.totals);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_keyed_scatter, dim3(grid_for(n, B)), dim3(B), 0, s, n, ng, d_key_idx, (const uint8_t*)st,
-                     K.cursor, K.list, K.lkey);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_keyed_count, n, B, s, n, ng, d_key_idx, st, K.counts));
+  RC_TRY(launch(k_keyed_scan, dim3(1), dim3(KEYED_SCAN_THREADS), s, ng, K.counts, K.offsets, K.cursor, K.cpos, K.totals));
+  RC_TRY(launch_n(k_keyed_scatter, n, B, s, n, ng, d_key_idx, st, K.cursor, K.list, K.lkey));
   mark(c, s, "keyed_sums");
-  hipLaunchKernelGGL(k_keyed_sums<Gr>, dim3(grid_for(2 * NT, B)), dim3(B), 0, s, NT, R, (const uint32_t*)K.totals, ng,
-                     (const uint32_t*)K.offsets, (const uint32_t*)K.counts, (const uint32_t*)K.list,
-                     (const uint32_t*)K.lkey, n, (const uint32_t*)K.leaf_p, (const uint32_t*)K.leaf_s, K.sums, K.part);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_keyed_fixup<Gr>, dim3((unsigned)(2 * n_keys)), dim3(64), 0, s, NT, R, ng,
-                     (const uint32_t*)K.offsets, (const uint32_t*)K.counts, K.part, K.sums);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_keyed_sums<Gr>, 2 * NT, B, s, NT, R, K.totals, ng, K.offsets, K.counts, K.list, K.lkey, n, K.leaf_p,
+                  K.leaf_s, K.sums, K.part));
+  RC_TRY(launch(k_keyed_fixup<Gr>, dim3((unsigned)(2 * n_keys)), dim3(64), s, NT, R, ng, K.offsets, K.counts, K.part,
+                K.sums));
   mark(c, s, "keyed_prep");
   // the slots past the non-empty keys: trivial candidates with zero points
   HIP_TRY(hipMemsetAsync(K.ch, 0, (size_t)M::AFF * m * 4, s));
   HIP_TRY(hipMemsetAsync(K.cs, 0, (size_t)M::AFF * m * 4, s));
   HIP_TRY(hipMemsetAsync(K.ckeys, 0, (size_t)kw * m * 4, s));
   HIP_TRY(hipMemsetAsync(K.cst, RLC_TRIVIAL, m, s));
-  hipLaunchKernelGGL(k_keyed_prep<Gr>, dim3(grid_for(n_keys, 64)), dim3(64), 0, s, ng, m, (const uint32_t*)K.counts,
-                     (const uint32_t*)K.cpos, (const uint32_t*)K.offsets, (const uint32_t*)K.list,
-                     (const uint32_t*)K.sums, n, item_keys, kw, K.ch, K.cs, K.ckeys, K.cst);
-  HIP_TRY(hipGetLastError());
-  if ((rc = eng_pairing_locked(c, keyed_items_job<G2KEY>(c, m, K.ch, K.cs, K.ckeys, K.cst), s))) return rc;
+  RC_TRY(launch_n(k_keyed_prep<Gr>, n_keys, 64, s, ng, m, K.counts, K.cpos, K.offsets, K.list, K.sums, n, item_keys, kw,
+                  K.ch, K.cs, K.ckeys, K.cst));
+  if ((rc = eng_pairing_locked(c, keyed_items_job(c, G2KEY, m, K.ch, K.cs, K.ckeys, K.cst), s))) return rc;
   // the records of the failing keys, one by one
-  hipLaunchKernelGGL(k_keyed_list_failing, dim3(grid_for(n, B)), dim3(B), 0, s, n, ng, d_key_idx, (const uint8_t*)st,
-                     (const uint32_t*)K.cpos, (const uint8_t*)K.cst, K.flist, K.nfail);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_keyed_list_failing, n, B, s, n, ng, d_key_idx, st, K.cpos, K.cst, K.flist, K.nfail));
   uint32_t nf = 0;
   HIP_TRY(hipMemcpyAsync(&nf, K.nfail, 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -157,15 +136,15 @@ int keyed_rlc_locked(dgpu_ctx* c, const keyed_rlc_in& in, hipStream_t s) {
   keyed_exact_layout X;
   if ((rc = carve(c->ky_exact, &X, (size_t)nf, M::AFF, kw))) return rc;
   mark(c, s, "keyed_fallback");
-  hipLaunchKernelGGL(k_keyed_compact, dim3(grid_for(nf, B)), dim3(B), 0, s, (size_t)nf, (const uint32_t*)K.flist, n, h,
-                     in.h_stride, in.h_idx, sg, (int)M::AFF, item_keys, kw, X.h, X.s, X.keys, X.st);
-  HIP_TRY(hipGetLastError());
-  if ((rc = eng_pairing_locked(c, keyed_items_job<G2KEY>(c, nf, X.h, X.s, X.keys, X.st), s))) return rc;
+  RC_TRY(launch_n(k_keyed_compact, nf, B, s, nf, K.flist, n, h, in.h_stride, in.h_idx, sg, M::AFF, item_keys, kw, X.h, X.s,
+                  X.keys, X.st));
+  if ((rc = eng_pairing_locked(c, keyed_items_job(c, G2KEY, nf, X.h, X.s, X.keys, X.st), s))) return rc;
   mark(c, s, "keyed_fallback");
-  hipLaunchKernelGGL(k_keyed_scatter_verdicts, dim3(grid_for(nf, B)), dim3(B), 0, s, (size_t)nf,
-                     (const uint32_t*)K.flist, (const uint8_t*)X.st, st);
-  HIP_TRY(hipGetLastError());
-  return DGPU_OK;
+  return launch_n(k_keyed_scatter_verdicts, nf, B, s, nf, K.flist, X.st, st);
+}
+
+int keyed_rlc_locked(dgpu_ctx* c, bool g1, const keyed_rlc_in& in, hipStream_t s) {
+  return with_group(g1, [&](auto gr) { return keyed_rlc_t<GROUP_OF(gr)>(c, in, s); });
 }
 
 // Everything up to the per-record status of a keyed call over device records
@@ -179,59 +158,30 @@ int keyed_status_locked(dgpu_ctx* c, const verify_args& a, size_t n_keys, const 
   const size_t n = a.n;
   const bool g1 = sig_on_g1(a.scheme);
   int rc;
-  c->n_ev = 0;
-  c->ev_overflow = false;
-  c->rlc_pending = false;
+  call_reset(c);
   const bool rlc = a.mode == DGPU_MODE_RLC && n >= c->rlc_min;
   keyed_table_layout T;
   if ((rc = c->status.ensure(n)) || (rc = c->ky_keys.ensure(n * keyed_key_words(g1) * 4)) ||
       (rc = keyed_table_locked(c, g1, n_keys, keys, key_len, s, &T)))
     return rc;
-  uint8_t* st = (uint8_t*)c->status.p;
-  uint32_t* item_keys = (uint32_t*)c->ky_keys.p;
+  uint8_t* st = c->status.u8();
+  uint32_t* item_keys = c->ky_keys.u32();
   lane_scratch& L = c->lane[0];
-  if (g1) {
-    if ((rc = L.h_pts.ensure(n * 2 * FP_WORDS * 4)) || (rc = L.sig_pts.ensure(n * 2 * FP_WORDS * 4)) ||
-        (rc = L.h_z.ensure(n * FP_WORDS * 4)) || (rc = L.h_pre.ensure(n * FP_WORDS * 4)))
-      return rc;
-    mark(c, s, "hash_to_g1");
-    with_src(a.m, [&](const auto& m) {
-      hipLaunchKernelGGL(SRC_KERNEL(k_hash_to_g1_beacons, m), dim3(grid_for(n, B)), dim3(B), 0, s, n, m,
-                         a.scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, (uint32_t*)L.h_pts.p, (uint32_t*)L.h_z.p);
-    });
-    HIP_TRY(hipGetLastError());
-    mark(c, s, "h_affine");
-    hipLaunchKernelGGL(k_g1_batch_affine, dim3(grid_for((n + 15) / 16, B)), dim3(B), 0, s, n, (uint32_t*)L.h_pts.p,
-                       (const uint32_t*)L.h_z.p, (uint32_t*)L.h_pre.p);
-    HIP_TRY(hipGetLastError());
-    mark(c, s, "decode_g1");
-    with_src(a.m, [&](const auto& m) {
-      hipLaunchKernelGGL(SRC_KERNEL(k_decode_g1_sigs, m), dim3(grid_for(n, B)), dim3(B), 0, s, n, a.sigs, a.sig_stride,
-                         a.sig_len, m, (uint32_t*)L.sig_pts.p, st);
-    });
-    HIP_TRY(hipGetLastError());
-  } else if ((rc = g2_lane_hash_locked(c, L, n, a.m, a.sigs, a.sig_stride, a.sig_len, st, s, nullptr, nullptr, nullptr,
-                                       0, rlc))) {
+  if ((rc = g1 ? g1_hash_decode_locked(c, a, st, s, false)
+               : g2_lane_hash_locked(c, L, n, a.m, a.sigs, a.sig_stride, a.sig_len, st, s, nullptr, nullptr, nullptr, 0,
+                                     rlc)))
     return rc;
-  }
   mark(c, s, "keyed_gather");
-  if (g1)
-    hipLaunchKernelGGL(k_keyed_gather<true>, dim3(grid_for(n, B)), dim3(B), 0, s, n, (uint32_t)n_keys, d_key_idx,
-                       (const uint32_t*)T.pts, (const int*)T.rc, item_keys, st);
-  else
-    hipLaunchKernelGGL(k_keyed_gather<false>, dim3(grid_for(n, B)), dim3(B), 0, s, n, (uint32_t)n_keys, d_key_idx,
-                       (const uint32_t*)T.pts, (const int*)T.rc, item_keys, st);
-  HIP_TRY(hipGetLastError());
-  if (rlc) {
-    const keyed_rlc_in in{n, n_keys, a.seed, d_key_idx, (const uint32_t*)L.h_pts.p, n, nullptr,
-                          (const uint32_t*)L.sig_pts.p, item_keys, st};
-    return g1 ? keyed_rlc_locked<G1Ops, true>(c, in, s) : keyed_rlc_locked<G2Ops, false>(c, in, s);
-  }
+  RC_TRY(launch_n(g1 ? k_keyed_gather<true> : k_keyed_gather<false>, n, B, s, n, n_keys, d_key_idx, T.pts, T.rc, item_keys,
+                  st));
+  if (rlc)
+    return keyed_rlc_locked(c, g1, {n, n_keys, a.seed, d_key_idx, L.h_pts.u32(), n, nullptr, L.sig_pts.u32(), item_keys, st},
+                            s);
   return eng_pairing_locked(c,
-                            {.consts = (const uint32_t*)c->eng_consts.p,
+                            {.consts = c->eng_consts.u32(),
                              .n = n,
-                             .h = (const uint32_t*)L.h_pts.p,
-                             .sg = (const uint32_t*)L.sig_pts.p,
+                             .h = L.h_pts.u32(),
+                             .sg = L.sig_pts.u32(),
                              .st = st,
                              .pk_items = g1 ? nullptr : item_keys,
                              .sig_subgroup = !g1 && !c->decode_subgroup,
@@ -250,23 +200,17 @@ int keyed_status_locked(dgpu_ctx* c, const verify_args& a, size_t n_keys, const 
 int verify_partials_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_msgs, size_t m, const uint8_t* d_parts,
                            size_t stride, const uint32_t* d_plen, int mode, uint64_t seed, uint8_t* d_bits,
                            uint8_t* d_reason, hipStream_t s) {
-  c->n_ev = 0;
-  c->ev_overflow = false;
-  c->rlc_pending = false;
+  call_reset(c);
   recover_walk w;
   int rc;
   if ((rc = recover_begin_locked(c, n_rounds, d_msgs, m, d_parts, stride, d_plen, true, s, &w))) return rc;
-  if (mode == DGPU_MODE_RLC && w.items >= c->rlc_min) {
-    const keyed_rlc_in in{w.items, (size_t)c->grp_n, seed, w.idx, w.h, n_rounds, w.hidx, w.sg, w.keys, w.st};
-    rc = w.g1 ? keyed_rlc_locked<G1Ops, true>(c, in, s) : keyed_rlc_locked<G2Ops, false>(c, in, s);
-  } else {
+  if (mode == DGPU_MODE_RLC && w.items >= c->rlc_min)
+    rc = keyed_rlc_locked(c, w.g1, {w.items, (size_t)c->grp_n, seed, w.idx, w.h, n_rounds, w.hidx, w.sg, w.keys, w.st}, s);
+  else
     rc = eng_pairing_locked(c, item_key_job(c, w, w.items, w.hidx, w.sg, w.keys, w.st), s);
-  }
   if (rc) return rc;
   mark(c, s, "pack_verdicts");
-  hipLaunchKernelGGL(k_pack_verdicts, dim3(grid_for((w.items + 7) / 8, 256)), dim3(256), 0, s, w.items,
-                     (const uint8_t*)w.st, d_bits);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_pack_verdicts, (w.items + 7) / 8, 256, s, w.items, w.st, d_bits));
   mark(c, s);
   if (d_reason) HIP_TRY(hipMemcpyAsync(d_reason, w.st, w.items, hipMemcpyDeviceToDevice, s));
   return DGPU_OK;
@@ -336,7 +280,7 @@ int dgpu_verify_keyed(dgpu_ctx* c, int scheme, size_t n_keys, const uint8_t* key
     return rc;
   HIP_TRY(hipStreamWaitEvent(s, c->ring_ev[c->ring_next ^ 1], 0));  // the copy stream is in order: its last DMA
   c->last_stage_bytes += n * 4;
-  if ((rc = keyed_status_locked(c, a, n_keys, keys, key_len, (const uint32_t*)c->in_key_idx.p, s)) ||
+  if ((rc = keyed_status_locked(c, a, n_keys, keys, key_len, c->in_key_idx.u32(), s)) ||
       (rc = results_out_locked(c, a, nullptr, verdict_bits, reason, hipMemcpyDeviceToHost, nullptr, s)))
     return rc;
   HIP_TRY(hipStreamSynchronize(s));
@@ -380,9 +324,8 @@ int dgpu_verify_partials(dgpu_ctx* c, size_t n_rounds, const uint8_t* msgs32, si
   HIP_TRY(hipMemcpyAsync(c->rec_msgs.p, msgs32, n_rounds * 32, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(c->rec_parts.p, partials, items * partial_stride, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(c->rec_plen.p, partial_len, items * 4, hipMemcpyHostToDevice, s));
-  if ((rc = verify_partials_locked(c, n_rounds, (const uint8_t*)c->rec_msgs.p, m, (const uint8_t*)c->rec_parts.p,
-                                   partial_stride, (const uint32_t*)c->rec_plen.p, mode, rlc_seed,
-                                   (uint8_t*)c->out_bits.p, nullptr, s)))
+  if ((rc = verify_partials_locked(c, n_rounds, c->rec_msgs.u8(), m, c->rec_parts.u8(), partial_stride, c->rec_plen.u32(),
+                                   mode, rlc_seed, c->out_bits.u8(), nullptr, s)))
     return rc;
   HIP_TRY(hipMemcpyAsync(valid_bits, c->out_bits.p, (items + 7) / 8, hipMemcpyDeviceToHost, s));
   if (reason) HIP_TRY(hipMemcpyAsync(reason, c->status.p, items, hipMemcpyDeviceToHost, s));

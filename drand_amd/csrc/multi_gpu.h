@@ -122,7 +122,7 @@ int dgpu_multi_open(int ndev, const int* devs, dgpu_multi** out) {
   if (loopback) {
     m->gev.assign(ndev, nullptr);
     for (int i = 0; i < ndev; ++i) {
-      hipSetDevice(devs[i]);
+      (void)hipSetDevice(devs[i]);
       if (hipEventCreateWithFlags(&m->gev[i], hipEventDisableTiming) != hipSuccess) {
         dgpu_multi_close(m);
         return set_err(DGPU_EDEVICE, "hipEventCreate failed");
@@ -148,8 +148,8 @@ void dgpu_multi_close(dgpu_multi* m) {
   for (size_t i = 0; i < m->comm.size(); ++i)
     if (m->comm[i]) m->api.comm_destroy(m->comm[i]);
   for (size_t i = 0; i < m->ctx.size(); ++i) {
-    hipSetDevice(m->devs[i]);
-    if (i < m->gev.size() && m->gev[i]) hipEventDestroy(m->gev[i]);
+    (void)hipSetDevice(m->devs[i]);
+    if (i < m->gev.size() && m->gev[i]) (void)hipEventDestroy(m->gev[i]);
     dgpu_close(m->ctx[i]);  // drains the context's streams, which the gathers ran on
   }
   delete m;  // the gather buffers go with the handle
@@ -224,8 +224,8 @@ int multi_all_gather(dgpu_multi* m, const std::vector<const void*>& src, const s
 int shard_results_locked(dgpu_multi* m, int k, const verify_args& a, uint8_t* rand32) {
   if (a.n == 0) return DGPU_OK;
   dgpu_ctx* c = m->ctx[k];
-  return results_out_locked(c, a, (uint8_t*)m->buf[k].bits.p, nullptr, (uint8_t*)m->buf[k].reasons.p,
-                            hipMemcpyDeviceToDevice, rand32, c->stream);
+  return results_out_locked(c, a, m->buf[k].bits.u8(), nullptr, m->buf[k].reasons.u8(), hipMemcpyDeviceToDevice, rand32,
+                            c->stream);
 }
 
 inline int no_shard_done(int, const verify_args&) { return DGPU_OK; }
@@ -290,7 +290,7 @@ int multi_verify(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_len, si
         c->rlc_pending = false;  // overwrites the points a pending per-rank root (dgpu_rlc_root_device) kept
         if ((r = stage_all_host_locked(c, a, s))) return r;
       }
-      return rlc_shard_root_locked(c, a, (uint8_t*)m->buf[k].root.p, s);  // (ensured above)
+      return rlc_shard_root_locked(c, a, m->buf[k].root.u8(), s);  // (ensured above)
     }
     if (a.n == 0) return DGPU_OK;
     // the shard's records through the context's pinned ring, slice by slice
@@ -313,7 +313,7 @@ int multi_verify(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_len, si
     dgpu_ctx* c0 = m->ctx[0];
     HIP_TRY(hipSetDevice(c0->device));
     bool fail = false;
-    if ((rc = rlc_node_check_locked(c0, keys[0], (size_t)D, (const uint8_t*)m->buf[0].all_roots.p, c0->stream, &fail)))
+    if ((rc = rlc_node_check_locked(c0, keys[0], (size_t)D, m->buf[0].all_roots.u8(), c0->stream, &fail)))
       return rc;
     rc = for_each_device(m, [&](int k) -> int {
       dgpu_ctx* c = m->ctx[k];
@@ -333,7 +333,7 @@ int multi_verify(dgpu_multi* m, int scheme, const uint8_t* pk, size_t pk_len, si
     HIP_TRY(hipSetDevice(m->ctx[k]->device));
     if (args[k].n < per) {  // padding of a short (or empty) last shard
       const size_t b0 = (args[k].n + 7) / 8;
-      HIP_TRY(hipMemsetAsync((uint8_t*)m->buf[k].bits.p + b0, 0, per / 8 - b0, m->ctx[k]->stream));
+      HIP_TRY(hipMemsetAsync(m->buf[k].bits.u8() + b0, 0, per / 8 - b0, m->ctx[k]->stream));
     }
   }
   {
@@ -549,14 +549,11 @@ int dgpu_recover_multi(dgpu_multi* m, size_t n_rounds, const uint8_t* msgs32, si
     HIP_TRY(hipMemcpyAsync(c->rec_parts.p, partials + lo[k] * m_slots * partial_stride, it * partial_stride,
                            hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(c->rec_plen.p, partial_len + lo[k] * m_slots, it * 4, hipMemcpyHostToDevice, s));
-    if ((r = recover_device_locked(c, nr, (const uint8_t*)c->rec_msgs.p, m_slots, (const uint8_t*)c->rec_parts.p,
-                                   partial_stride, (const uint32_t*)c->rec_plen.p, (uint8_t*)c->rec_out.p,
-                                   (uint8_t*)c->rec_ok.p, partial_valid ? (uint8_t*)c->out_reason.p : nullptr, s)))
+    if ((r = recover_device_locked(c, nr, c->rec_msgs.u8(), m_slots, c->rec_parts.u8(), partial_stride, c->rec_plen.u32(),
+                                   c->rec_out.u8(), c->rec_ok.u8(), partial_valid ? c->out_reason.u8() : nullptr, s)))
       return r;
     HIP_TRY(hipMemsetAsync(m->buf[k].bits.p, 0, per / 8, s));
-    hipLaunchKernelGGL(k_pack_ok, dim3(grid_for((nr + 7) / 8, 256)), dim3(256), 0, s, nr, (const uint8_t*)c->rec_ok.p,
-                       (uint8_t*)m->buf[k].bits.p);
-    HIP_TRY(hipGetLastError());
+    RC_TRY(launch_n(k_pack_ok, (nr + 7) / 8, 256, s, nr, c->rec_ok.u8(), m->buf[k].bits.u8()));
     const size_t sb = group_sig_bytes(c);  // 48 for a G1-signature group
     HIP_TRY(hipMemcpyAsync(out_sigs + lo[k] * sb, c->rec_out.p, nr * sb, hipMemcpyDeviceToHost, s));
     if (partial_valid) {

@@ -32,11 +32,7 @@ int decode_commits_locked(dgpu_ctx* c, bool g2, int t, const uint8_t* commits, D
   uint8_t* const d_in = M.in;
   int* const d_rc = M.rc;
   HIP_TRY(hipMemcpyAsync(d_in, commits, (size_t)t * cb, hipMemcpyHostToDevice, s));
-  if (g2)
-    hipLaunchKernelGGL(k_decode_commits_g2, dim3(grid_for(t, 64)), dim3(64), 0, s, t, d_in, (uint32_t*)dst->p, d_rc);
-  else
-    hipLaunchKernelGGL(k_decode_commits, dim3(grid_for(t, 64)), dim3(64), 0, s, t, d_in, (uint32_t*)dst->p, d_rc);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(g2 ? k_decode_commits_g2 : k_decode_commits, t, 64, s, t, d_in, dst->u32(), d_rc));
   std::vector<int> hrc(t);
   HIP_TRY(hipMemcpyAsync(hrc.data(), d_rc, t * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -55,12 +51,8 @@ int set_group_g2_locked(dgpu_ctx* c, int t, int n, const uint8_t* commits48) {
   if ((rc = c->grp_table.ensure((size_t)n * 2 * FP_LIMBS * 4)) ||
       (rc = c->grp_wtab.ensure((size_t)n * 8 * REC_WTAB_WORDS * 4)))
     return rc;
-  hipLaunchKernelGGL(k_pubpoly_table, dim3(grid_for(n, 64)), dim3(64), 0, s, n, t, (const uint32_t*)c->grp_commits.p,
-                     (uint32_t*)c->grp_table.p);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_pubpoly_wtable, dim3(grid_for(8 * (size_t)n, 64)), dim3(64), 0, s, n,
-                     (const uint32_t*)c->grp_table.p, (uint32_t*)c->grp_wtab.p);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_pubpoly_table, n, 64, s, n, t, c->grp_commits.u32(), c->grp_table.u32()));
+  RC_TRY(launch_n(k_pubpoly_wtable, 8 * (size_t)n, 64, s, n, c->grp_table.u32(), c->grp_wtab.u32()));
   HIP_TRY(hipStreamSynchronize(s));
   c->grp_t = t;
   c->grp_n = n;
@@ -90,12 +82,8 @@ int set_group_g1_locked(dgpu_ctx* c, int scheme, int t, int n, const uint8_t* co
       (rc = c->grp_wtab.ensure((size_t)n * 8 * G2A_WORDS * 4)))
     return rc;
   HIP_TRY(hipMemcpyAsync(c->grp_commits.p, c->grp_stage.p, cw, hipMemcpyDeviceToDevice, s));
-  hipLaunchKernelGGL(k_pubpoly_table_g2, dim3(grid_for(n, 64)), dim3(64), 0, s, n, t,
-                     (const uint32_t*)c->grp_commits.p, (uint32_t*)c->grp_table.p);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_pubpoly_wtable_g2, dim3(grid_for(8 * (size_t)n, 64)), dim3(64), 0, s, n,
-                     (const uint32_t*)c->grp_table.p, (uint32_t*)c->grp_wtab.p);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_pubpoly_table_g2, n, 64, s, n, t, c->grp_commits.u32(), c->grp_table.u32()));
+  RC_TRY(launch_n(k_pubpoly_wtable_g2, 8 * (size_t)n, 64, s, n, c->grp_table.u32(), c->grp_wtab.u32()));
   HIP_TRY(hipStreamSynchronize(s));
   c->grp_t = t;
   c->grp_n = n;
@@ -157,26 +145,16 @@ struct recover_walk {
 };
 
 // H(msg) of n_rounds 32-byte messages as affine points of the signature group.
-hipError_t recover_hash_launch(bool g1, int g1dst, size_t n_rounds, const uint8_t* d_msgs, uint32_t* h, hipStream_t s) {
-  if (g1)
-    hipLaunchKernelGGL(k_hash_to_g1_msgs_pts, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds, d_msgs, g1dst, h);
-  else
-    hipLaunchKernelGGL(k_hash_to_g2_msgs_pts, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds, d_msgs, h);
-  return hipGetLastError();
+int recover_hash_launch(bool g1, int g1dst, size_t n_rounds, const uint8_t* d_msgs, uint32_t* h, hipStream_t s) {
+  if (g1) return launch_n(k_hash_to_g1_msgs_pts, n_rounds, 256, s, n_rounds, d_msgs, g1dst, h);
+  return launch_n(k_hash_to_g2_msgs_pts, n_rounds, 256, s, n_rounds, d_msgs, h);
 }
 
 // Every partial decoded: its signature, share index and share key Eval(i).
-hipError_t recover_decode_launch(dgpu_ctx* c, const recover_walk& w, const uint8_t* d_parts, size_t stride,
-                                 const uint32_t* d_plen, hipStream_t s) {
-  if (w.g1)
-    hipLaunchKernelGGL(k_decode_partials_g1, dim3(grid_for(w.items, 256)), dim3(256), 0, s, w.items, d_parts, stride,
-                       d_plen, c->grp_n, c->grp_t, (const uint32_t*)c->grp_table.p, (const uint32_t*)c->grp_commits.p,
-                       w.sg, w.keys, w.idx, w.st);
-  else
-    hipLaunchKernelGGL(k_decode_partials, dim3(grid_for(w.items, 256)), dim3(256), 0, s, w.items, d_parts, stride,
-                       d_plen, c->grp_n, c->grp_t, (const uint32_t*)c->grp_table.p, (const uint32_t*)c->grp_commits.p,
-                       w.sg, w.keys, w.idx, w.st);
-  return hipGetLastError();
+int recover_decode_launch(dgpu_ctx* c, const recover_walk& w, const uint8_t* d_parts, size_t stride,
+                          const uint32_t* d_plen, hipStream_t s) {
+  return launch_n(w.g1 ? k_decode_partials_g1 : k_decode_partials, w.items, 256, s, w.items, d_parts, stride, d_plen,
+                  c->grp_n, c->grp_t, c->grp_table.u32(), c->grp_commits.u32(), w.sg, w.keys, w.idx, w.st);
 }
 
 // The shared prologue of both recovery paths: the item count validated, the
@@ -206,29 +184,25 @@ int recover_begin_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_msgs, si
   w.n_rounds = n_rounds, w.m = m, w.items = items;
   w.t = c->grp_t;
   w.g1 = g1;
-  w.h = (uint32_t*)L.h_pts.p;
-  w.sg = (uint32_t*)L.sig_pts.p;
-  w.st = (uint8_t*)c->status.p;
-  w.hidx = (uint32_t*)c->rec_hidx.p;
-  w.keys = (uint32_t*)c->rec_pk.p;
-  w.idx = (uint32_t*)c->rec_idx.p;
+  w.h = L.h_pts.u32();
+  w.sg = L.sig_pts.u32();
+  w.st = c->status.u8();
+  w.hidx = c->rec_hidx.u32();
+  w.keys = c->rec_pk.u32();
+  w.idx = c->rec_idx.u32();
   w.sel = sel.sel;
   w.xs = sel.xs;
-  w.dig = (uint64_t*)c->rec_lam.p;
+  w.dig = c->rec_lam.u64();
   w.part = part.slice[0];  // (the kernels take the slices' base)
-  w.rpts = (uint32_t*)c->rec_pts.p;
-  w.rpk = (uint32_t*)c->rec_vpk.p;
-  w.rst = (uint8_t*)c->rec_st.p;
-  w.cls = (uint8_t*)c->rec_cls.p;
+  w.rpts = c->rec_pts.u32();
+  w.rpk = c->rec_vpk.u32();
+  w.rst = c->rec_st.u8();
+  w.cls = c->rec_cls.u8();
   mark(c, s, "recover_hash");
-  HIP_TRY(recover_hash_launch(g1, c->grp_scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, n_rounds, d_msgs, w.h, s));
+  RC_TRY(recover_hash_launch(g1, c->grp_scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, n_rounds, d_msgs, w.h, s));
   mark(c, s, "recover_decode");
-  if (round_of_item) {
-    hipLaunchKernelGGL(k_round_of_item, dim3(grid_for(items, 256)), dim3(256), 0, s, items, m, w.hidx);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(recover_decode_launch(c, w, d_parts, stride, d_plen, s));
-  return DGPU_OK;
+  if (round_of_item) RC_TRY(launch_n(k_round_of_item, items, 256, s, items, m, w.hidx));
+  return recover_decode_launch(c, w, d_parts, stride, d_plen, s);
 }
 
 // The G1 recovery MSM's launches (recover_g1.cuh): shared affine window tables
@@ -239,17 +213,12 @@ int recover_msm_g1_locked(dgpu_ctx* c, const recover_walk& w, const uint8_t* d_o
   if ((rc = c->rec_tab.ensure(ne * 2 * FP_WORDS * 4)) || (rc = c->rec_tabz.ensure(ne * FP_WORDS * 4)) ||
       (rc = c->rec_tabpre.ensure(ne * FP_WORDS * 4)))
     return rc;
-  uint32_t* tab = (uint32_t*)c->rec_tab.p;
-  hipLaunchKernelGGL(k_recover_tables_g1, dim3(grid_for(w.n_rounds * (size_t)w.t, 256)), dim3(256), 0, s, w.n_rounds,
-                     w.t, d_ok, (const uint32_t*)w.sel, (const uint32_t*)w.sg, w.items, tab, (uint32_t*)c->rec_tabz.p);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_g1_batch_affine, dim3(grid_for((ne + 15) / 16, 256)), dim3(256), 0, s, ne, tab,
-                     (const uint32_t*)c->rec_tabz.p, (uint32_t*)c->rec_tabpre.p);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_recover_msm_g1, dim3(grid_for((size_t)slices * w.n_rounds, 256)), dim3(256), 0, s, w.n_rounds,
-                     w.t, d_ok, (const uint64_t*)w.dig, (const uint32_t*)tab, w.part, slices);
-  HIP_TRY(hipGetLastError());
-  return DGPU_OK;
+  uint32_t *const tab = c->rec_tab.u32(), *const tabz = c->rec_tabz.u32();
+  RC_TRY(launch_n(k_recover_tables_g1, w.n_rounds * (size_t)w.t, 256, s, w.n_rounds, w.t, d_ok, w.sel, w.sg, w.items, tab,
+                  tabz));
+  RC_TRY(launch_n(k_g1_batch_affine, (ne + 15) / 16, 256, s, ne, tab, tabz, c->rec_tabpre.u32()));
+  return launch_n(k_recover_msm_g1, (size_t)slices * w.n_rounds, 256, s, w.n_rounds, w.t, d_ok, w.dig, tab, w.part,
+                  slices);
 }
 
 // The batched check's G2 MSM (recover.cuh): shared affine window tables
@@ -260,71 +229,47 @@ int recover_msm_g2_locked(dgpu_ctx* c, const recover_walk& w, const uint8_t* d_o
   if ((rc = c->rec_tab.ensure(ne * G2A_WORDS * 4)) || (rc = c->rec_tabz.ensure(ne * 2 * FP_WORDS * 4)) ||
       (rc = c->rec_tabpre.ensure(ne * FP_WORDS * 4)))
     return rc;
-  uint32_t* tab = (uint32_t*)c->rec_tab.p;
-  hipLaunchKernelGGL(k_recover_tables, dim3(grid_for(w.n_rounds * (size_t)w.t, 256)), dim3(256), 0, s, w.n_rounds, w.t,
-                     d_ok, (const uint32_t*)w.sel, (const uint32_t*)w.sg, w.items, tab, (uint32_t*)c->rec_tabz.p);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_g2_batch_affine, dim3(grid_for((ne + 15) / 16, 256)), dim3(256), 0, s, ne, tab,
-                     (const uint32_t*)c->rec_tabz.p, (uint32_t*)c->rec_tabpre.p);
-  HIP_TRY(hipGetLastError());
-  if (c->recover_rows) {  // the entries as 224-byte rows for the gathers
-    if ((rc = c->rec_tab_rows.ensure(ne * G2A_WORDS * 4))) return rc;
-    hipLaunchKernelGGL(k_recover_tab_rows, dim3(grid_for(ne, 256)), dim3(256), 0, s, ne, (const uint32_t*)tab,
-                       (uint32_t*)c->rec_tab_rows.p);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_recover_msm_aff<true>, dim3(grid_for(5 * w.n_rounds, 256)), dim3(256), 0, s, w.n_rounds, w.t,
-                       d_ok, (const uint64_t*)w.dig, (const uint32_t*)c->rec_tab_rows.p, w.part, 5);
-  } else {
-    hipLaunchKernelGGL(k_recover_msm_aff<false>, dim3(grid_for(5 * w.n_rounds, 256)), dim3(256), 0, s, w.n_rounds, w.t,
-                       d_ok, (const uint64_t*)w.dig, (const uint32_t*)tab, w.part, 5);
-  }
-  HIP_TRY(hipGetLastError());
-  return DGPU_OK;
+  uint32_t *const tab = c->rec_tab.u32(), *const tabz = c->rec_tabz.u32();
+  RC_TRY(launch_n(k_recover_tables, w.n_rounds * (size_t)w.t, 256, s, w.n_rounds, w.t, d_ok, w.sel, w.sg, w.items, tab, tabz));
+  RC_TRY(launch_n(k_g2_batch_affine, (ne + 15) / 16, 256, s, ne, tab, tabz, c->rec_tabpre.u32()));
+  if (!c->recover_rows)
+    return launch_n(k_recover_msm_aff<false>, 5 * w.n_rounds, 256, s, w.n_rounds, w.t, d_ok, w.dig, tab, w.part, 5);
+  // the entries as 224-byte rows for the gathers
+  if ((rc = c->rec_tab_rows.ensure(ne * G2A_WORDS * 4))) return rc;
+  uint32_t* const rows = c->rec_tab_rows.u32();
+  RC_TRY(launch_n(k_recover_tab_rows, ne, 256, s, ne, tab, rows));
+  return launch_n(k_recover_msm_aff<true>, 5 * w.n_rounds, 256, s, w.n_rounds, w.t, d_ok, w.dig, rows, w.part, 5);
 }
 
 // The exact path's G2 MSM: window tables sized to t in private memory (TMAX x
 // 8 Jacobian points per thread), four slices per round.
-hipError_t recover_msm_w4_launch(const recover_walk& w, const uint8_t* d_ok, hipStream_t s) {
+int recover_msm_w4_launch(const recover_walk& w, const uint8_t* d_ok, hipStream_t s) {
   auto msm = w.t <= 8 ? k_recover_msm_w4<8> : w.t <= 16 ? k_recover_msm_w4<16> : w.t <= 24 ? k_recover_msm_w4<24>
                                                                                            : k_recover_msm_w4<32>;
-  hipLaunchKernelGGL(msm, dim3(grid_for(4 * w.n_rounds, 256)), dim3(256), 0, s, w.n_rounds, w.t, d_ok,
-                     (const uint32_t*)w.sel, (const uint64_t*)w.dig, (const uint32_t*)w.sg, w.items, w.part, 4);
-  return hipGetLastError();
+  return launch_n(msm, 4 * w.n_rounds, 256, s, w.n_rounds, w.t, d_ok, w.sel, w.dig, w.sg, w.items, w.part, 4);
 }
 
 // The slices' sums to the round's signature: compressed into d_out's 96-byte
 // slot and affine in rpts; slices = 5 (batched check): rpts gets B.
-hipError_t recover_finish_launch(const recover_walk& w, const uint8_t* d_ok, uint8_t* d_out, int slices, hipStream_t s) {
-  if (w.g1)
-    hipLaunchKernelGGL(k_recover_finish_g1, dim3(grid_for(w.n_rounds, 64)), dim3(64), 0, s, w.n_rounds, d_ok,
-                       (const uint32_t*)w.part, d_out, w.rpts, w.rst, slices);
-  else
-    hipLaunchKernelGGL(k_recover_finish, dim3(grid_for(w.n_rounds, 64)), dim3(64), 0, s, w.n_rounds, d_ok,
-                       (const uint32_t*)w.part, d_out, w.rpts, w.rst, slices);
-  return hipGetLastError();
+int recover_finish_launch(const recover_walk& w, const uint8_t* d_ok, uint8_t* d_out, int slices, hipStream_t s) {
+  return launch_n(w.g1 ? k_recover_finish_g1 : k_recover_finish, w.n_rounds, 64, s, w.n_rounds, d_ok, w.part, d_out, w.rpts,
+                  w.rst, slices);
 }
 
 // The batched check's combination on the other group: A = the random
 // combination of the round's share keys, into rpk (a G2 point per round for
 // G1 signatures).
-hipError_t recover_combine_launch(dgpu_ctx* c, const recover_walk& w, uint8_t* d_ok, hipStream_t s) {
+int recover_combine_launch(dgpu_ctx* c, const recover_walk& w, uint8_t* d_ok, hipStream_t s) {
   mark(c, s, w.g1 ? "recover_rlc_g2" : "recover_rlc_g1");
-  if (w.g1)
-    hipLaunchKernelGGL(k_recover_rlc_g2, dim3(grid_for(w.n_rounds, 64)), dim3(64), 0, s, w.n_rounds, w.t, c->grp_n,
-                       (const uint32_t*)w.sel, (const uint32_t*)w.idx, (const uint64_t*)w.dig,
-                       (const uint32_t*)c->grp_wtab.p, (const uint32_t*)c->grp_commits.p, w.cls, d_ok, w.rpk, w.rst);
-  else
-    hipLaunchKernelGGL(k_recover_rlc_g1, dim3(grid_for(w.n_rounds, 64)), dim3(64), 0, s, w.n_rounds, w.t, c->grp_n,
-                       (const uint32_t*)w.sel, (const uint32_t*)w.idx, (const uint64_t*)w.dig,
-                       (const uint32_t*)c->grp_wtab.p, (const uint32_t*)c->grp_commits.p, w.cls, d_ok, w.rpk, w.rst);
-  return hipGetLastError();
+  return launch_n(w.g1 ? k_recover_rlc_g2 : k_recover_rlc_g1, w.n_rounds, 64, s, w.n_rounds, w.t, c->grp_n, w.sel, w.idx,
+                  w.dig, c->grp_wtab.u32(), c->grp_commits.u32(), w.cls, d_ok, w.rpk, w.rst);
 }
 
 // Pairing checks with a key per item, item i against hash point h_idx[i] (or
 // i): e(key_i, H) e(-g1, sg_i) == 1; G1 signatures: e(H, key_i) e(-sg_i, g2) == 1.
 pairing_job item_key_job(dgpu_ctx* c, const recover_walk& w, size_t n, const uint32_t* h_idx, const uint32_t* sg,
                          const uint32_t* keys, uint8_t* st) {
-  return {.consts = (const uint32_t*)c->eng_consts.p,
+  return {.consts = c->eng_consts.u32(),
           .n = n,
           .h = w.h,
           .sg = sg,
@@ -341,12 +286,12 @@ pairing_job item_key_job(dgpu_ctx* c, const recover_walk& w, size_t n, const uin
 // (the per-round copy is not used on that side).
 pairing_job verify_recovered_job(dgpu_ctx* c, const recover_walk& w) {
   if (w.g1)
-    return {.consts = (const uint32_t*)c->grp_key.consts.p,
+    return {.consts = c->grp_key.consts.u32(),
             .n = w.n_rounds,
             .h = w.h,
             .sg = w.rpts,
             .st = w.rst,
-            .fixed_table = (const uint32_t*)c->grp_key.table.p};
+            .fixed_table = c->grp_key.table.u32()};
   return item_key_job(c, w, w.n_rounds, nullptr, w.rpts, w.rpk, w.rst);
 }
 
@@ -363,25 +308,16 @@ int recover_exact_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_msgs, si
   // VerifyPartial of every partial on the engine
   if ((rc = eng_pairing_locked(c, item_key_job(c, w, w.items, w.hidx, w.sg, w.keys, w.st), s))) return rc;
   mark(c, s, "recover_select");
-  hipLaunchKernelGGL(k_recover_select, dim3(grid_for(n_rounds, 64)), dim3(64), 0, s, n_rounds, m, w.t,
-                     (const uint32_t*)w.idx, (const uint8_t*)w.st, w.sel, w.xs, d_out, d_ok,
-                     (const uint32_t*)c->grp_commits.p, w.rpts, w.rpk, w.rst);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_recover_select, n_rounds, 64, s, n_rounds, m, w.t, w.idx, w.st, w.sel, w.xs, d_out, d_ok,
+                  c->grp_commits.u32(), w.rpts, w.rpk, w.rst));
   mark(c, s, "recover_lagrange");
-  hipLaunchKernelGGL(k_recover_lagrange, dim3(grid_for(n_rounds * RECOVER_MAX_T, 256)), dim3(256), 0, s, n_rounds, w.t,
-                     (const uint8_t*)d_ok, (const uint32_t*)w.xs, w.dig, (uint64_t)0);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_recover_lagrange, n_rounds * RECOVER_MAX_T, 256, s, n_rounds, w.t, d_ok, w.xs, w.dig, 0));
   mark(c, s, "recover_msm");
-  if (w.g1) {
-    if ((rc = recover_msm_g1_locked(c, w, d_ok, 4, s))) return rc;
-  } else {
-    HIP_TRY(recover_msm_w4_launch(w, d_ok, s));
-  }
-  HIP_TRY(recover_finish_launch(w, d_ok, d_out, 4, s));
-  if ((rc = eng_pairing_locked(c, verify_recovered_job(c, w), s))) return rc;
+  if ((rc = w.g1 ? recover_msm_g1_locked(c, w, d_ok, 4, s) : recover_msm_w4_launch(w, d_ok, s)) ||
+      (rc = recover_finish_launch(w, d_ok, d_out, 4, s)) || (rc = eng_pairing_locked(c, verify_recovered_job(c, w), s)))
+    return rc;
   mark(c, s, "recover_verdict");
-  hipLaunchKernelGGL(k_recover_verdict, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds, w.rst, d_out, d_ok);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_recover_verdict, n_rounds, 256, s, n_rounds, w.rst, d_out, d_ok));
   if (d_status) HIP_TRY(hipMemcpyAsync(d_status, w.st, w.items, hipMemcpyDeviceToDevice, s));
   mark(c, s);
   return DGPU_OK;
@@ -394,9 +330,7 @@ int recover_slots_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_msgs, si
                          size_t stride, const uint32_t* d_plen, uint8_t* d_out, uint8_t* d_ok, uint8_t* d_status,
                          hipStream_t s) {
   if (!c->grp_t) return set_err(DGPU_ENOKEY, "no threshold group installed (dgpu_set_group)");
-  c->n_ev = 0;
-  c->ev_overflow = false;
-  c->rlc_pending = false;
+  call_reset(c);
   if (c->recover_exact)
     return recover_exact_locked(c, n_rounds, d_msgs, m, d_parts, stride, d_plen, d_out, d_ok, d_status, s);
   // fresh, unpredictable coefficients per call (partials come from peers)
@@ -407,23 +341,18 @@ int recover_slots_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_msgs, si
   int rc;
   if ((rc = recover_begin_locked(c, n_rounds, d_msgs, m, d_parts, stride, d_plen, false, s, &w))) return rc;
   mark(c, s, "recover_select");
-  hipLaunchKernelGGL(k_recover_cand, dim3(grid_for(n_rounds, 64)), dim3(64), 0, s, n_rounds, m, w.t, d_status ? 1 : 0,
-                     (const uint32_t*)w.idx, (const uint8_t*)w.st, w.sel, w.xs, w.cls, d_ok, d_out);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_recover_cand, n_rounds, 64, s, n_rounds, m, w.t, d_status ? 1 : 0, w.idx, w.st, w.sel, w.xs, w.cls,
+                  d_ok, d_out));
   mark(c, s, "recover_lagrange");
-  hipLaunchKernelGGL(k_recover_lagrange, dim3(grid_for(n_rounds * RECOVER_MAX_T, 256)), dim3(256), 0, s, n_rounds, w.t,
-                     (const uint8_t*)d_ok, (const uint32_t*)w.xs, w.dig, seed);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_recover_lagrange, n_rounds * RECOVER_MAX_T, 256, s, n_rounds, w.t, d_ok, w.xs, w.dig, seed));
   mark(c, s, "recover_msm");
-  if ((rc = w.g1 ? recover_msm_g1_locked(c, w, d_ok, 5, s) : recover_msm_g2_locked(c, w, d_ok, s))) return rc;
-  HIP_TRY(recover_finish_launch(w, d_ok, d_out, 5, s));
-  HIP_TRY(recover_combine_launch(c, w, d_ok, s));
+  if ((rc = w.g1 ? recover_msm_g1_locked(c, w, d_ok, 5, s) : recover_msm_g2_locked(c, w, d_ok, s)) ||
+      (rc = recover_finish_launch(w, d_ok, d_out, 5, s)) || (rc = recover_combine_launch(c, w, d_ok, s)))
+    return rc;
   // one pairing per round: e(A, H) e(-g1, B) == 1; G1 signatures: e(H, A) e(-B, g2) == 1
   if ((rc = eng_pairing_locked(c, item_key_job(c, w, n_rounds, nullptr, w.rpts, w.rpk, w.rst), s))) return rc;
   mark(c, s, "recover_verdict");
-  hipLaunchKernelGGL(k_recover_rlc_verdict, dim3(grid_for(n_rounds, 256)), dim3(256), 0, s, n_rounds,
-                     d_status ? 1 : 0, (const uint8_t*)w.rst, w.cls, d_ok, d_out);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_n(k_recover_rlc_verdict, n_rounds, 256, s, n_rounds, d_status ? 1 : 0, w.rst, w.cls, d_ok, d_out));
   if (d_status) HIP_TRY(hipMemcpyAsync(d_status, w.st, w.items, hipMemcpyDeviceToDevice, s));
   // rounds left to the exact path
   std::vector<uint8_t> hc(n_rounds);
@@ -441,19 +370,13 @@ int recover_slots_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_msgs, si
       (rc = c->rec_x_out.ensure(nx * 96)) || (rc = c->rec_x_ok.ensure(nx)) || (rc = c->rec_x_st.ensure(xi)))
     return rc;
   HIP_TRY(hipMemcpyAsync(c->rec_x_list.p, list.data(), nx * 4, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_gather_rounds, dim3(grid_for(xi, 256)), dim3(256), 0, s, nx, (const uint32_t*)c->rec_x_list.p,
-                     m, stride, d_msgs, d_parts, d_plen, (uint8_t*)c->rec_x_msgs.p, (uint8_t*)c->rec_x_parts.p,
-                     (uint32_t*)c->rec_x_plen.p);
-  HIP_TRY(hipGetLastError());
-  if ((rc = recover_exact_locked(c, nx, (const uint8_t*)c->rec_x_msgs.p, m, (const uint8_t*)c->rec_x_parts.p, stride,
-                                 (const uint32_t*)c->rec_x_plen.p, (uint8_t*)c->rec_x_out.p, (uint8_t*)c->rec_x_ok.p,
-                                 (uint8_t*)c->rec_x_st.p, s)))
-    return rc;
-  hipLaunchKernelGGL(k_scatter_rounds, dim3(grid_for(xi, 256)), dim3(256), 0, s, nx, (const uint32_t*)c->rec_x_list.p,
-                     m, (const uint8_t*)c->rec_x_out.p, (const uint8_t*)c->rec_x_ok.p, (const uint8_t*)c->rec_x_st.p,
-                     d_out, d_ok, d_status);
-  HIP_TRY(hipGetLastError());
-  return DGPU_OK;
+  const uint32_t* const x_list = c->rec_x_list.u32();
+  uint8_t *const x_msgs = c->rec_x_msgs.u8(), *const x_parts = c->rec_x_parts.u8(), *const x_out = c->rec_x_out.u8(),
+                 *const x_ok = c->rec_x_ok.u8(), *const x_st = c->rec_x_st.u8();
+  uint32_t* const x_plen = c->rec_x_plen.u32();
+  RC_TRY(launch_n(k_gather_rounds, xi, 256, s, nx, x_list, m, stride, d_msgs, d_parts, d_plen, x_msgs, x_parts, x_plen));
+  if ((rc = recover_exact_locked(c, nx, x_msgs, m, x_parts, stride, x_plen, x_out, x_ok, x_st, s))) return rc;
+  return launch_n(k_scatter_rounds, xi, 256, s, nx, x_list, m, x_out, x_ok, x_st, d_out, d_ok, d_status);
 }
 
 // recover_slots_locked works on 96-byte round slots (its selection, verdict
@@ -465,12 +388,9 @@ int recover_device_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_msgs, s
   if (!c->grp_g1) return recover_slots_locked(c, n_rounds, d_msgs, m, d_parts, stride, d_plen, d_out, d_ok, d_status, s);
   int rc;
   if ((rc = c->rec_slots.ensure(n_rounds * 96))) return rc;
-  uint8_t* slots = (uint8_t*)c->rec_slots.p;
+  uint8_t* slots = c->rec_slots.u8();
   if ((rc = recover_slots_locked(c, n_rounds, d_msgs, m, d_parts, stride, d_plen, slots, d_ok, d_status, s))) return rc;
-  hipLaunchKernelGGL(k_recover_pack48, dim3(grid_for(n_rounds * 48, 256)), dim3(256), 0, s, n_rounds,
-                     (const uint8_t*)slots, (const uint8_t*)d_ok, d_out);
-  HIP_TRY(hipGetLastError());
-  return DGPU_OK;
+  return launch_n(k_recover_pack48, n_rounds * 48, 256, s, n_rounds, slots, d_ok, d_out);
 }
 
 }  // namespace
@@ -519,9 +439,8 @@ int dgpu_recover_batch(dgpu_ctx* c, size_t n_rounds, const uint8_t* msgs32, size
   HIP_TRY(hipMemcpyAsync(c->rec_msgs.p, msgs32, n_rounds * 32, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(c->rec_parts.p, partials, items * partial_stride, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(c->rec_plen.p, partial_len, items * 4, hipMemcpyHostToDevice, s));
-  if ((rc = recover_device_locked(c, n_rounds, (const uint8_t*)c->rec_msgs.p, m, (const uint8_t*)c->rec_parts.p,
-                                  partial_stride, (const uint32_t*)c->rec_plen.p, (uint8_t*)c->rec_out.p,
-                                  (uint8_t*)c->rec_ok.p, partial_valid ? (uint8_t*)c->out_reason.p : nullptr, s)))
+  if ((rc = recover_device_locked(c, n_rounds, c->rec_msgs.u8(), m, c->rec_parts.u8(), partial_stride, c->rec_plen.u32(),
+                                  c->rec_out.u8(), c->rec_ok.u8(), partial_valid ? c->out_reason.u8() : nullptr, s)))
     return rc;
   std::vector<uint8_t> okv(n_rounds), stv(partial_valid ? items : 0);
   HIP_TRY(hipMemcpyAsync(out_sigs, c->rec_out.p, n_rounds * group_sig_bytes(c), hipMemcpyDeviceToHost, s));
@@ -572,21 +491,12 @@ int dgpu_make_partials_scheme(dgpu_ctx* c, int scheme, size_t n_rounds, const ui
   if (e == hipSuccess) e = hipMemcpyAsync(d_si.p, sign_idx, items * 4, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(d_lb.p, label, items * 4, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(d_sh.p, sh.data(), n_shares * sizeof(scalar256), hipMemcpyHostToDevice, s);
-  if (e == hipSuccess)
-    e = recover_hash_launch(g1, scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, n_rounds, (const uint8_t*)d_msgs.p,
-                            (uint32_t*)d_h.p, s);
-  if (e == hipSuccess) {
-    if (g1)
-      hipLaunchKernelGGL(k_sign_partials_g1, dim3(grid_for(items, 64)), dim3(64), 0, s, items, m, n_rounds,
-                         (const uint32_t*)d_h.p, (const uint32_t*)d_si.p, (const uint32_t*)d_lb.p,
-                         (const scalar256*)d_sh.p, (uint8_t*)d_out.p);
-    else
-      hipLaunchKernelGGL(k_sign_partials, dim3(grid_for(items, 64)), dim3(64), 0, s, items, m, n_rounds,
-                         (const uint32_t*)d_h.p, (const uint32_t*)d_si.p, (const uint32_t*)d_lb.p,
-                         (const scalar256*)d_sh.p, (uint8_t*)d_out.p);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(out98, d_out.p, items * pb, hipMemcpyDeviceToHost, s);
+  if (e != hipSuccess) return set_err(DGPU_EDEVICE, "make_partials: %s", hipGetErrorString(e));
+  if ((rc = recover_hash_launch(g1, scheme == DGPU_SCHEME_G1_RFC9380 ? 1 : 0, n_rounds, d_msgs.u8(), d_h.u32(), s)) ||
+      (rc = launch_n(g1 ? k_sign_partials_g1 : k_sign_partials, items, 64, s, items, m, n_rounds, d_h.u32(), d_si.u32(),
+                     d_lb.u32(), d_sh.as<scalar256>(), d_out.u8())))
+    return rc;
+  e = hipMemcpyAsync(out98, d_out.p, items * pb, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) return set_err(DGPU_EDEVICE, "make_partials: %s", hipGetErrorString(e));
   return DGPU_OK;
