@@ -183,7 +183,7 @@ def stage_times(ctx):
     names = (ctypes.c_char_p * MAX_STAGES)()
     ns = ctx.lib.dgpu_stage_times(ctx.handle, ms, MAX_STAGES, names)
     if ns < 0:
-        check(ns)
+        check(ns, ctx.lib)
     if ns > MAX_STAGES:
         raise DrandGPUError(DGPU_EINVAL, f"{ns} stages > DGPU_MAX_STAGES")
     return {names[i].decode(): float(ms[i]) for i in range(ns)}
@@ -219,6 +219,8 @@ def ptr(buf):
 class Context:
     """One GPU context (dgpu_ctx*).  Thread-safe: the library serializes."""
 
+    installed_group = None  # the key of the threshold group the context holds (calls.set_group)
+
     def __init__(self, device=0, lib_path=None):
         # torch bundles its own HIP runtime under the system one's SONAME: a
         # process that uses both must let torch initialise HIP first, or torch
@@ -253,7 +255,7 @@ class MultiContext:
         self.devices = list(devices)
         arr = (ctypes.c_int * len(self.devices))(*self.devices)
         h = ctypes.c_void_p()
-        check(self.lib.dgpu_multi_open(len(self.devices), arr, ctypes.byref(h)))
+        check(self.lib.dgpu_multi_open(len(self.devices), arr, ctypes.byref(h)), self.lib)
         self.handle = h
 
     def close(self):

@@ -16,14 +16,14 @@ GPU; constructing a Verifier without the HIP library or a gfx950 device
 raises DrandGPUError.
 """
 import hashlib
-import secrets
 import struct
 import threading
 from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib
+from . import _lib, calls
+from .calls import pack_msgs as _pack_msgs, rlc_seed_for  # noqa: F401  (their callers import them from here)
 from .scheme import Scheme, scheme_code
 
 
@@ -104,90 +104,92 @@ def pack_beacons(beacons, sig_stride=96, prev_stride=None):
     return rounds, sigs, sig_len, prev, prev_len
 
 
-def rlc_seed_for(mode, rlc_seed):
-    """RLC coefficients must be unpredictable to whoever produced the
-    beacons: without an explicit seed, RLC mode draws a fresh 64-bit one per
-    call (a known seed lets an attacker choose corruptions that cancel)."""
-    if mode == _lib.MODE_RLC and rlc_seed is None:
-        return secrets.randbits(64)
-    return 0 if rlc_seed is None else int(rlc_seed)
+class RecordCalls:
+    """The batch surface that Verifier and multi.MultiVerifier share: the same
+    packing and checks over `self.ctx`, under the single or the multi form of
+    each entry point."""
+
+    _records = staticmethod(calls.verify_beacons)
+    _segment = staticmethod(calls.verify_segment)
+    _rows = staticmethod(calls.check_rows)
+
+    def verify_reasons(self, beacons, pubkey, mode=_lib.MODE_PER_ROUND, rlc_seed=None):
+        n = len(beacons)
+        if n == 0:
+            return np.zeros(0, dtype=np.uint8)
+        rounds, sigs, sig_len, prev, prev_len = pack_beacons(beacons)
+        return self.verify_records(pubkey, rounds, sigs, sig_len, prev, prev_len, mode, rlc_seed)
+
+    def verify_records(self, pubkey, rounds, sigs, sig_len, prev, prev_len, mode=_lib.MODE_PER_ROUND, rlc_seed=None):
+        """Fixed-stride host records (numpy, as pack_beacons builds them or
+        the native bolt ingest decodes them): DGPU_REASON_* per record."""
+        if len(rounds) == 0:
+            return np.zeros(0, dtype=np.uint8)
+        return self._records(self.ctx, self._code, pubkey, rounds, sigs, sig_len, prev, prev_len, mode, rlc_seed)
+
+    def check_rows(self, pubkey, rows, first, count, mode=_lib.MODE_PER_ROUND, rlc_seed=None, sig_stride=96,
+                   prev_stride=96, reasons=False):
+        """One window of the bulk chain check in one call (dgpu_check_rows):
+        `rows` is an ingest.Rows (keys, off, len, buf), the loop visits rounds
+        first .. first + count - 1.  The rows are decoded and verified on the
+        GPU and the faulty list is built there.  Returns (faulty_pos,
+        faulty_val, left_rows): the positions (round - first) and values of
+        the faulty entries in ascending position, and the indices of the rows
+        that are not canonical -- the caller's to decode with
+        sync.beacon_unmarshal and merge.  reasons=True appends the
+        DGPU_REASON_* code per row."""
+        n = len(rows.off)
+        off = np.ascontiguousarray(rows.off, dtype=np.uint64)
+        ln = np.ascontiguousarray(rows.len, dtype=np.uint32)
+        keys = np.ascontiguousarray(rows.keys, dtype=np.uint64)
+        if len(ln) != n or len(keys) != n:
+            raise ValueError("rows.keys, rows.off and rows.len differ in length")
+        if n and int((off + ln).max()) > rows.buf.size:
+            raise ValueError("a row leaves the buffer")
+        out, reason = self._rows(self.ctx, self._code, pubkey, rows.buf, off, ln, keys, sig_stride, prev_stride, mode,
+                                 rlc_seed, int(first), int(count), reasons)
+        return out + (reason,) if reasons else out
+
+    def verify_segment(self, first_round, sigs, prev_sig, pubkey, mode=_lib.MODE_PER_ROUND, rlc_seed=None,
+                       randomness=True, sig_len=None):
+        """A linked run of rounds known by its signatures alone
+        (dgpu_verify_segment; the walk of client/verify.go:118-178): round
+        first_round + i carries sigs[i], its previous signature is prev_sig
+        for i = 0 and sigs[i - 1] after (ignored by the unchained schemes).
+        sigs: a list of bytes, or an (n, stride) uint8 array with sig_len.
+        Returns (reasons, randomness): the DGPU_REASON_* codes as
+        verify_records returns them, and the (n, 32) uint8 array of
+        SHA-256(sigs[i]) for the rounds that verify (zeros for the others;
+        client/verify.go:207), or None when randomness is False."""
+        width = calls.sig_width(self._code)
+        if isinstance(sigs, np.ndarray):
+            if sig_len is None:
+                raise ValueError("a signature array needs sig_len")
+            buf = np.ascontiguousarray(sigs, dtype=np.uint8)
+            lens = np.ascontiguousarray(sig_len, dtype=np.uint32)
+            if buf.ndim != 2 or lens.shape != (buf.shape[0],):
+                raise ValueError("sigs must be (n, stride) and sig_len (n,)")
+            if buf.shape[1] < width:
+                buf = np.pad(buf, ((0, 0), (0, width - buf.shape[1])))
+        else:
+            buf, lens = calls.pack_msgs([bytes(s or b"") for s in sigs], width)
+        if buf.shape[0] == 0:
+            return np.zeros(0, dtype=np.uint8), np.zeros((0, 32), dtype=np.uint8) if randomness else None
+        return self._segment(self.ctx, self._code, pubkey, first_round, buf, lens, prev_sig, mode, rlc_seed,
+                             randomness)
 
 
-def verify_segment_with(call, lib, code, first_round, sigs, prev_sig, pubkey, mode, rlc_seed, randomness, sig_len):
-    """The packing and result checks of a linked-segment call, shared by
-    Verifier.verify_segment and multi.MultiVerifier.verify_segment: `call` is
-    the entry point with its handle and scheme bound, taking the arguments
-    from pk on (dgpu_verify_segment, dgpu_verify_segment_multi)."""
-    width = 48 if code in (_lib.SCHEME_UNCHAINED_G1, _lib.SCHEME_G1_RFC9380) else 96
-    if isinstance(sigs, np.ndarray):
-        if sig_len is None:
-            raise ValueError("a signature array needs sig_len")
-        buf = np.ascontiguousarray(sigs, dtype=np.uint8)
-        lens = np.ascontiguousarray(sig_len, dtype=np.uint32)
-        if buf.ndim != 2 or lens.shape != (buf.shape[0],):
-            raise ValueError("sigs must be (n, stride) and sig_len (n,)")
-    else:
-        buf, lens = _pack_msgs([bytes(s or b"") for s in sigs])
-    if buf.shape[1] < width:
-        buf = np.pad(buf, ((0, 0), (0, width - buf.shape[1])))
-    n = buf.shape[0]
-    rand = np.zeros((n, 32), dtype=np.uint8) if randomness else None
-    if n == 0:
-        return np.zeros(0, dtype=np.uint8), rand
-    seed = np.frombuffer(bytes(prev_sig or b""), dtype=np.uint8).copy()
-    bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-    reason = np.zeros(n, dtype=np.uint8)
-    pk = np.frombuffer(bytes(pubkey), dtype=np.uint8).copy()
-    _lib.check(call(_lib.ptr(pk), pk.size, int(first_round), n, _lib.ptr(buf), buf.shape[1], _lib.ptr(lens),
-                    _lib.ptr(seed) if seed.size else None, seed.size, mode, rlc_seed_for(mode, rlc_seed),
-                    _lib.ptr(bits), _lib.ptr(reason), None if rand is None else _lib.ptr(rand)), lib)
-    valid = np.unpackbits(bits, bitorder="little")[:n].astype(bool)
-    if not np.array_equal(valid, reason == _lib.REASON_OK):
-        raise _lib.DrandGPUError(_lib.DGPU_EINVAL, "verdict bitmap and reasons disagree")
-    return reason, rand
-
-
-def check_rows_with(call, lib, pubkey, rows, first, count, mode, rlc_seed, sig_stride=96, prev_stride=96,
-                    reasons=False):
-    """The packing of a dgpu_check_rows call, shared by Verifier.check_rows
-    and multi.MultiVerifier.check_rows: `call` is the entry point with its
-    handle and scheme bound, taking the arguments from pk on.  The lists are
-    given room for every position and every row (untouched pages of an empty
-    array cost nothing; the library copies back the entries there are)."""
-    n = len(rows.off)
-    first, count = int(first), int(count)
-    off = np.ascontiguousarray(rows.off, dtype=np.uint64)
-    ln = np.ascontiguousarray(rows.len, dtype=np.uint32)
-    keys = np.ascontiguousarray(rows.keys, dtype=np.uint64)
-    if len(ln) != n or len(keys) != n:
-        raise ValueError("rows.keys, rows.off and rows.len differ in length")
-    if n and int((off + ln).max()) > rows.buf.size:
-        raise ValueError("a row leaves the buffer")
-    pos = np.empty(count, dtype=np.uint64)
-    val = np.empty(count, dtype=np.uint64)
-    left = np.empty(n, dtype=np.uint64)
-    nf, nl = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint64)
-    reason = np.zeros(n, dtype=np.uint8) if reasons else None
-    pk = np.frombuffer(bytes(pubkey), dtype=np.uint8).copy()
-    _lib.check(call(_lib.ptr(pk), pk.size, n, _lib.ptr(rows.buf) if n else None, _lib.ptr(off) if n else None,
-                    _lib.ptr(ln) if n else None, _lib.ptr(keys) if n else None, sig_stride, prev_stride, mode,
-                    rlc_seed_for(mode, rlc_seed), first, count, _lib.ptr(pos) if count else None,
-                    _lib.ptr(val) if count else None, count, _lib.ptr(nf), _lib.ptr(left) if n else None, n,
-                    _lib.ptr(nl), _lib.ptr(reason) if reasons and n else None), lib)
-    out = pos[:int(nf[0])].copy(), val[:int(nf[0])].copy(), left[:int(nl[0])].copy()
-    return out + (reason,) if reasons else out
-
-
-class Verifier:
+class Verifier(RecordCalls):
     """chain.Verifier (chain/verify.go:13-20): stateless apart from the scheme;
     safe for concurrent use (the GPU context serializes).  The public key is
     passed per call, like VerifyBeacon(b, pubkey) (chain/verify.go:38); the
     context caches decoded keys, so verifiers of different chains and schemes
     can share one GPU context."""
 
-    def __init__(self, scheme: Scheme, device=0):
+    def __init__(self, scheme: Scheme, device=0, ctx=None):
+        """ctx: a context of the caller's (default: the device's shared one)."""
         self.scheme = scheme
-        self.ctx = get_context(device)
+        self.ctx = ctx or get_context(device)
         self._code = scheme_code(scheme)
 
     def is_prev_sig_meaningful(self):
@@ -211,39 +213,13 @@ class Verifier:
         out = np.zeros((n, 32), dtype=np.uint8)
         lib = self.ctx.lib
         _lib.check(lib.dgpu_digest_batch(self.ctx.handle, self._code, n, _lib.ptr(r), _lib.ptr(prev), stride,
-                                         _lib.ptr(plen), _lib.ptr(out)))
+                                         _lib.ptr(plen), _lib.ptr(out)), lib)
         return [bytes(row) for row in out]
 
     def verify_beacons(self, beacons, pubkey, mode=_lib.MODE_PER_ROUND, rlc_seed=None):
         """Batch VerifyBeacon: returns a list of (None | VerifyError), one per beacon."""
         reasons = self.verify_reasons(beacons, pubkey, mode, rlc_seed)
         return [None if r == _lib.REASON_OK else VerifyError(b.round, int(r)) for b, r in zip(beacons, reasons)]
-
-    def verify_reasons(self, beacons, pubkey, mode=_lib.MODE_PER_ROUND, rlc_seed=None):
-        n = len(beacons)
-        if n == 0:
-            return np.zeros(0, dtype=np.uint8)
-        rounds, sigs, sig_len, prev, prev_len = pack_beacons(beacons)
-        return self.verify_records(pubkey, rounds, sigs, sig_len, prev, prev_len, mode, rlc_seed)
-
-    def verify_records(self, pubkey, rounds, sigs, sig_len, prev, prev_len, mode=_lib.MODE_PER_ROUND, rlc_seed=None):
-        """Fixed-stride host records (numpy, as pack_beacons builds them or
-        the native bolt ingest decodes them): DGPU_REASON_* per record."""
-        n = len(rounds)
-        if n == 0:
-            return np.zeros(0, dtype=np.uint8)
-        bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-        reason = np.zeros(n, dtype=np.uint8)
-        pk = np.frombuffer(bytes(pubkey), dtype=np.uint8).copy()
-        lib = self.ctx.lib
-        _lib.check(lib.dgpu_verify_beacons(self.ctx.handle, self._code, _lib.ptr(pk), pk.size, n, _lib.ptr(rounds),
-                                           _lib.ptr(sigs), sigs.shape[1], _lib.ptr(sig_len), _lib.ptr(prev),
-                                           prev.shape[1], _lib.ptr(prev_len), mode, rlc_seed_for(mode, rlc_seed),
-                                           _lib.ptr(bits), _lib.ptr(reason)))
-        valid = np.unpackbits(bits, bitorder="little")[:n].astype(bool)
-        if not np.array_equal(valid, reason == _lib.REASON_OK):
-            raise _lib.DrandGPUError(_lib.DGPU_EINVAL, "verdict bitmap and reasons disagree")
-        return reason
 
     def verify_rows(self, pubkey, buf, off, ln, mode=_lib.MODE_PER_ROUND, rlc_seed=None, sig_stride=96,
                     prev_stride=96):
@@ -254,57 +230,15 @@ class Verifier:
         others -- reason DGPU_REASON_DECODE -- are the caller's to decode
         with sync.beacon_unmarshal), and each canonical row's Round."""
         n = len(off)
-        reason = np.zeros(n, dtype=np.uint8)
-        ok = np.zeros(n, dtype=np.uint8)
-        rounds = np.zeros(n, dtype=np.uint64)
         if n == 0:
-            return reason, ok.astype(bool), rounds
+            return np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=bool), np.zeros(0, dtype=np.uint64)
         off = np.ascontiguousarray(off, dtype=np.uint64)
         ln = np.ascontiguousarray(ln, dtype=np.uint32)
         if int((off + ln).max()) > buf.size:
             raise ValueError("a row leaves the buffer")
-        bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-        pk = np.frombuffer(bytes(pubkey), dtype=np.uint8).copy()
-        lib = self.ctx.lib
-        _lib.check(lib.dgpu_verify_rows(self.ctx.handle, self._code, _lib.ptr(pk), pk.size, n, _lib.ptr(buf),
-                                        _lib.ptr(off), _lib.ptr(ln), sig_stride, prev_stride, mode,
-                                        rlc_seed_for(mode, rlc_seed), _lib.ptr(rounds), _lib.ptr(ok), _lib.ptr(bits),
-                                        _lib.ptr(reason)), lib)
-        valid = np.unpackbits(bits, bitorder="little")[:n].astype(bool)
-        if not np.array_equal(valid, reason == _lib.REASON_OK):
-            raise _lib.DrandGPUError(_lib.DGPU_EINVAL, "verdict bitmap and reasons disagree")
+        reason, ok, rounds = calls.verify_rows(self.ctx, self._code, pubkey, buf, off, ln, sig_stride, prev_stride,
+                                               mode, rlc_seed)
         return reason, ok.astype(bool), rounds
-
-    def check_rows(self, pubkey, rows, first, count, mode=_lib.MODE_PER_ROUND, rlc_seed=None, sig_stride=96,
-                   prev_stride=96, reasons=False):
-        """One window of the bulk chain check in one call (dgpu_check_rows):
-        `rows` is an ingest.Rows (keys, off, len, buf), the loop visits rounds
-        first .. first + count - 1.  The rows are decoded and verified on the
-        GPU and the faulty list is built there.  Returns (faulty_pos,
-        faulty_val, left_rows): the positions (round - first) and values of
-        the faulty entries in ascending position, and the indices of the rows
-        that are not canonical -- the caller's to decode with
-        sync.beacon_unmarshal and merge.  reasons=True appends the
-        DGPU_REASON_* code per row."""
-        lib = self.ctx.lib
-        return check_rows_with(lambda *a: lib.dgpu_check_rows(self.ctx.handle, self._code, *a), lib, pubkey, rows,
-                               first, count, mode, rlc_seed, sig_stride, prev_stride, reasons)
-
-    def verify_segment(self, first_round, sigs, prev_sig, pubkey, mode=_lib.MODE_PER_ROUND, rlc_seed=None,
-                       randomness=True, sig_len=None):
-        """A linked run of rounds known by its signatures alone
-        (dgpu_verify_segment; the walk of client/verify.go:118-178): round
-        first_round + i carries sigs[i], its previous signature is prev_sig
-        for i = 0 and sigs[i - 1] after (ignored by the unchained schemes).
-        sigs: a list of bytes, or an (n, stride) uint8 array with sig_len.
-        Returns (reasons, randomness): the DGPU_REASON_* codes as
-        verify_records returns them, and the (n, 32) uint8 array of
-        SHA-256(sigs[i]) for the rounds that verify (zeros for the others;
-        client/verify.go:207), or None when randomness is False."""
-        lib = self.ctx.lib
-        return verify_segment_with(lambda *a: lib.dgpu_verify_segment(self.ctx.handle, self._code, *a), lib,
-                                   self._code, first_round, sigs, prev_sig, pubkey, mode, rlc_seed, randomness,
-                                   sig_len)
 
     def verify_beacon(self, b: Beacon, pubkey: bytes):
         """chain/verify.go:38-45: raises VerifyError (the reference's non-nil
@@ -319,38 +253,18 @@ def new_verifier(scheme: Scheme, device=0):
     return Verifier(scheme, device)
 
 
-def _pack_msgs(msgs):
-    n = len(msgs)
-    stride = max([1] + [len(m) for m in msgs])
-    buf = np.zeros((n, stride), dtype=np.uint8)
-    lens = np.zeros(n, dtype=np.uint32)
-    for i, m in enumerate(msgs):
-        if m:
-            buf[i, : len(m)] = np.frombuffer(bytes(m), dtype=np.uint8)
-        lens[i] = len(m)
-    return buf, lens
-
-
-def verify_recovered(scheme: Scheme, pubkey, msgs, sigs, mode=_lib.MODE_PER_ROUND, rlc_seed=None, device=0):
+def verify_recovered(scheme: Scheme, pubkey, msgs, sigs, mode=_lib.MODE_PER_ROUND, rlc_seed=None, device=0,
+                     ctx=None):
     """Batch key.Scheme.VerifyRecovered(pk, msg, sig) (chain/verify.go:44,
     chain/beacon/chain.go:165; kyber bls.Verify (R)) over raw messages of any
-    length.  Returns the DGPU_REASON_* code per message (0 = valid)."""
-    ctx = get_context(device)
-    n = len(msgs)
-    if n == 0:
+    length.  Returns the DGPU_REASON_* code per message (0 = valid).  ctx: a
+    context of the caller's (default: the device's shared one)."""
+    if len(msgs) == 0:
         return np.zeros(0, dtype=np.uint8)
-    mb, ml = _pack_msgs(msgs)
-    sb, sl = _pack_msgs(sigs)
-    width = 48 if scheme_code(scheme) in (_lib.SCHEME_UNCHAINED_G1, _lib.SCHEME_G1_RFC9380) else 96
-    if sb.shape[1] < width:
-        sb = np.pad(sb, ((0, 0), (0, width - sb.shape[1])))
-    pk = np.frombuffer(bytes(pubkey), dtype=np.uint8).copy()
-    bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-    reason = np.zeros(n, dtype=np.uint8)
-    _lib.check(ctx.lib.dgpu_verify_recovered(ctx.handle, scheme_code(scheme), _lib.ptr(pk), pk.size, n, _lib.ptr(mb),
-                                             mb.shape[1], _lib.ptr(ml), _lib.ptr(sb), sb.shape[1], _lib.ptr(sl), mode,
-                                             rlc_seed_for(mode, rlc_seed), _lib.ptr(bits), _lib.ptr(reason)))
-    return reason
+    code = scheme_code(scheme)
+    mb, ml = calls.pack_msgs(msgs)
+    sb, sl = calls.pack_msgs(sigs, calls.sig_width(code))
+    return calls.verify_recovered(ctx or get_context(device), code, pubkey, mb, ml, sb, sl, mode, rlc_seed)
 
 
 def pack_keyed(code, keys, key_idx, msgs, sigs):
@@ -360,8 +274,7 @@ def pack_keyed(code, keys, key_idx, msgs, sigs):
     and signature records as verify_recovered packs them.  ValueError for a
     key of the wrong length or an index outside the table (the library's
     DGPU_EINVAL, raised before any call)."""
-    g1 = code in (_lib.SCHEME_UNCHAINED_G1, _lib.SCHEME_G1_RFC9380)
-    key_len, width = (96, 48) if g1 else (48, 96)
+    key_len = calls.key_width(code)
     keys = [bytes(k) for k in keys]
     if not 1 <= len(keys) <= 65536:
         raise ValueError("a key table holds 1 to 65536 keys")
@@ -373,10 +286,8 @@ def pack_keyed(code, keys, key_idx, msgs, sigs):
     if idx.size and (idx.min() < 0 or idx.max() >= len(keys)):
         raise ValueError("a key index lies outside the table")
     kb = np.frombuffer(b"".join(keys), dtype=np.uint8).copy()
-    mb, ml = _pack_msgs(msgs)
-    sb, sl = _pack_msgs(sigs)
-    if sb.shape[1] < width:
-        sb = np.pad(sb, ((0, 0), (0, width - sb.shape[1])))
+    mb, ml = calls.pack_msgs(msgs)
+    sb, sl = calls.pack_msgs(sigs, calls.sig_width(code))
     return kb, key_len, idx.astype(np.uint32), mb, ml, sb, sl
 
 
@@ -391,20 +302,9 @@ def verify_keyed(scheme: Scheme, keys, key_idx, msgs, sigs, mode=_lib.MODE_PER_R
     context of the caller's (default: the device's shared one)."""
     code = scheme_code(scheme)
     kb, key_len, idx, mb, ml, sb, sl = pack_keyed(code, keys, key_idx, msgs, sigs)
-    n = len(idx)
-    if n == 0:
+    if len(idx) == 0:
         return np.zeros(0, dtype=np.uint8)
-    ctx = ctx or get_context(device)
-    bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-    reason = np.zeros(n, dtype=np.uint8)
-    _lib.check(ctx.lib.dgpu_verify_keyed(ctx.handle, code, kb.size // key_len, _lib.ptr(kb), key_len, n, _lib.ptr(idx),
-                                         _lib.ptr(mb), mb.shape[1], _lib.ptr(ml), _lib.ptr(sb), sb.shape[1],
-                                         _lib.ptr(sl), mode, rlc_seed_for(mode, rlc_seed), _lib.ptr(bits),
-                                         _lib.ptr(reason)), ctx.lib)
-    valid = np.unpackbits(bits, bitorder="little")[:n].astype(bool)
-    if not np.array_equal(valid, reason == _lib.REASON_OK):
-        raise _lib.DrandGPUError(_lib.DGPU_EINVAL, "verdict bitmap and reasons disagree")
-    return reason
+    return calls.verify_keyed(ctx or get_context(device), code, kb, key_len, idx, mb, ml, sb, sl, mode, rlc_seed)
 
 
 def hash_to_curve(msgs, scheme: Scheme = None, device=0):
@@ -414,12 +314,12 @@ def hash_to_curve(msgs, scheme: Scheme = None, device=0):
     code = scheme_code(scheme or get_scheme_by_id_with_default(""))
     ctx = get_context(device)
     n = len(msgs)
-    mb, ml = _pack_msgs(msgs)
-    width = 48 if code in (_lib.SCHEME_UNCHAINED_G1, _lib.SCHEME_G1_RFC9380) else 96
+    mb, ml = calls.pack_msgs(msgs)
+    width = calls.sig_width(code)
     out = np.zeros(n * width, dtype=np.uint8)
     if n:
         _lib.check(ctx.lib.dgpu_hash_to_curve(ctx.handle, code, n, _lib.ptr(mb), mb.shape[1], _lib.ptr(ml),
-                                              _lib.ptr(out)))
+                                              _lib.ptr(out)), ctx.lib)
     return [bytes(out[i * width:(i + 1) * width]) for i in range(n)]
 
 
@@ -428,17 +328,10 @@ def sign(secret, msgs, scheme: Scheme = None, device=0):
     with a secret scalar (int or 32 big-endian bytes): test/tool surface."""
     from .scheme import get_scheme_by_id_with_default
     code = scheme_code(scheme or get_scheme_by_id_with_default(""))
-    ctx = get_context(device)
-    sk = secret.to_bytes(32, "big") if isinstance(secret, int) else bytes(secret)
-    skb = np.frombuffer(sk, dtype=np.uint8).copy()
-    n = len(msgs)
-    mb, ml = _pack_msgs(msgs)
-    width = 48 if code in (_lib.SCHEME_UNCHAINED_G1, _lib.SCHEME_G1_RFC9380) else 96
-    out = np.zeros(n * width, dtype=np.uint8)
-    if n:
-        _lib.check(ctx.lib.dgpu_sign(ctx.handle, code, _lib.ptr(skb), n, _lib.ptr(mb), mb.shape[1], _lib.ptr(ml),
-                                     _lib.ptr(out)))
-    return [bytes(out[i * width:(i + 1) * width]) for i in range(n)]
+    if not msgs:
+        return []
+    sk = secret if isinstance(secret, int) else bytes(secret)
+    return [bytes(s) for s in calls.sign(get_context(device), code, sk, *calls.pack_msgs(msgs))]
 
 
 def decode_g1_points(points, device=0):
@@ -450,7 +343,7 @@ def decode_g1_points(points, device=0):
     rc = np.zeros(n, dtype=np.int32)
     xy = np.zeros(n * 96, dtype=np.uint8)
     if n:
-        _lib.check(ctx.lib.dgpu_decode_g1_points(ctx.handle, n, _lib.ptr(buf), _lib.ptr(rc), _lib.ptr(xy)))
+        _lib.check(ctx.lib.dgpu_decode_g1_points(ctx.handle, n, _lib.ptr(buf), _lib.ptr(rc), _lib.ptr(xy)), ctx.lib)
     coords = [(int.from_bytes(bytes(xy[i * 96:i * 96 + 48]), "big"), int.from_bytes(bytes(xy[i * 96 + 48:i * 96 + 96]), "big"))
               if rc[i] == 0 else None for i in range(n)]
     return rc.tolist(), coords
@@ -467,7 +360,7 @@ def decode_signatures(scheme, sigs, device=0):
     ctx = get_context(device)
     code = scheme_code(scheme)
     n = len(sigs)
-    g1 = code in (_lib.SCHEME_UNCHAINED_G1, _lib.SCHEME_G1_RFC9380)
+    g1 = code in calls.G1_SIG_CODES
     stride = max([96] + [len(s) for s in sigs])
     buf = np.zeros((max(n, 1), stride), dtype=np.uint8)
     ln = np.zeros(max(n, 1), dtype=np.uint32)
@@ -479,7 +372,7 @@ def decode_signatures(scheme, sigs, device=0):
     xy = np.zeros(max(n, 1) * w, dtype=np.uint8)
     if n:
         _lib.check(ctx.lib.dgpu_decode_signatures(ctx.handle, code, n, _lib.ptr(buf), stride, _lib.ptr(ln),
-                                                  _lib.ptr(reason), _lib.ptr(xy)))
+                                                  _lib.ptr(reason), _lib.ptr(xy)), ctx.lib)
     pts = []
     for i in range(n):
         if reason[i] != _lib.REASON_OK:
@@ -497,9 +390,9 @@ def decode_pubkey(scheme, pk, device=0):
     ctx = get_context(device)
     code = scheme_code(scheme)
     b = np.frombuffer(bytes(pk), dtype=np.uint8).copy()
-    g2 = code in (_lib.SCHEME_UNCHAINED_G1, _lib.SCHEME_G1_RFC9380)
+    g2 = code in calls.G1_SIG_CODES
     xy = np.zeros(192, dtype=np.uint8)
-    _lib.check(ctx.lib.dgpu_decode_pubkey(ctx.handle, code, _lib.ptr(b), len(pk), _lib.ptr(xy)))
+    _lib.check(ctx.lib.dgpu_decode_pubkey(ctx.handle, code, _lib.ptr(b), len(pk), _lib.ptr(xy)), ctx.lib)
     c = _be_coords(xy, 4 if g2 else 2)
     return ((c[0], c[1]), (c[2], c[3])) if g2 else c
 
@@ -510,7 +403,7 @@ def hash_to_g2(msgs, device=0):
     n = len(msgs)
     m = np.frombuffer(b"".join(msgs), dtype=np.uint8).copy()
     out = np.zeros(n * 96, dtype=np.uint8)
-    _lib.check(ctx.lib.dgpu_hash_to_g2(ctx.handle, n, _lib.ptr(m), _lib.ptr(out)))
+    _lib.check(ctx.lib.dgpu_hash_to_g2(ctx.handle, n, _lib.ptr(m), _lib.ptr(out)), ctx.lib)
     return [bytes(out[i * 96:(i + 1) * 96]) for i in range(n)]
 
 
@@ -522,5 +415,5 @@ def hash_to_g1(msgs, scheme_code_=None, device=0):
     m = np.frombuffer(b"".join(msgs), dtype=np.uint8).copy()
     out = np.zeros(n * 48, dtype=np.uint8)
     code = _lib.SCHEME_UNCHAINED_G1 if scheme_code_ is None else scheme_code_
-    _lib.check(ctx.lib.dgpu_hash_to_g1(ctx.handle, code, n, _lib.ptr(m), _lib.ptr(out)))
+    _lib.check(ctx.lib.dgpu_hash_to_g1(ctx.handle, code, n, _lib.ptr(m), _lib.ptr(out)), ctx.lib)
     return [bytes(out[i * 48:(i + 1) * 48]) for i in range(n)]

@@ -84,34 +84,25 @@ def verify_rlc_sharded(ctx, code, pk, n, d_rounds, d_sigs, d_sig_len, d_prev, d_
     `stream` waits on the collective's result), never by a device-wide
     synchronize.  Returns nothing: the verdict bits land in d_bits (and
     reasons in d_reason) in `stream` order."""
-    import ctypes
     import torch
-    import torch.distributed as dist
-    from . import _lib
-    lib = ctx.lib
-    rb = lib.dgpu_rlc_root_bytes(code)
-    _lib.check(min(rb, 0))
+    from . import calls
+    rb = calls.rlc_root_bytes(ctx, code)
     dev = d_bits.device
-    s = ctypes.c_void_p(None if stream is None else stream.cuda_stream)
     lib_stream = torch.cuda.default_stream(dev) if stream is None else stream
     cur = torch.cuda.current_stream(dev)
     with torch.cuda.stream(lib_stream):  # root allocated in the library's stream order
         root = torch.empty(rb, dtype=torch.uint8, device=dev)
-    pkb = pk if hasattr(pk, "ctypes") else np.frombuffer(bytes(pk), dtype=np.uint8).copy()
-    _lib.check(lib.dgpu_rlc_root_device(ctx.handle, code, _lib.ptr(pkb), pkb.size, n, d_rounds.data_ptr(),
-                                        d_sigs.data_ptr(), sig_stride, d_sig_len.data_ptr(), d_prev.data_ptr(),
-                                        prev_stride, d_prev_len.data_ptr(), rank_seed(seed, rank, world),
-                                        root.data_ptr(), s))
-    _finish_rlc_sharded(ctx, root, rb, world, d_bits, d_reason, s, lib_stream, cur)
+    calls.rlc_root_device(ctx, code, pk, d_rounds, d_sigs, d_sig_len, d_prev, d_prev_len, rank_seed(seed, rank, world),
+                          root, stream, n=n, sig_stride=sig_stride, prev_stride=prev_stride)
+    _finish_rlc_sharded(ctx, root, rb, world, d_bits, d_reason, stream, lib_stream, cur)
 
 
-def _finish_rlc_sharded(ctx, root, rb, world, d_bits, d_reason, s, lib_stream, cur):
+def _finish_rlc_sharded(ctx, root, rb, world, d_bits, d_reason, stream, lib_stream, cur):
     """Steps 2-3 of the per-rank RLC protocol: the roots' all-gather (ordered
     against the library's stream by waits) and dgpu_rlc_finish_device."""
     import torch
     import torch.distributed as dist
-    from . import _lib
-    lib = ctx.lib
+    from . import calls
     dev = root.device
     if world > 1:
         cur.wait_stream(lib_stream)  # the root is written before the collective reads it
@@ -127,8 +118,7 @@ def _finish_rlc_sharded(ctx, root, rb, world, d_bits, d_reason, s, lib_stream, c
         roots.record_stream(lib_stream)
     else:
         roots = root
-    _lib.check(lib.dgpu_rlc_finish_device(ctx.handle, world, roots.data_ptr(), d_bits.data_ptr(),
-                                          None if d_reason is None else d_reason.data_ptr(), s))
+    calls.rlc_finish_device(ctx, world, roots, d_bits, d_reason, stream)
 
 
 def halo_len_offset(sig_stride):
@@ -180,20 +170,16 @@ def verify_segment_sharded(ctx, code, pk, first_round, n_total, d_sigs, d_sig_le
     d_bits (reasons in d_reason, randomness in d_randomness) in `stream`
     order.  Measured with two ranks on one GPU only; RCCL with two or more
     real ranks is unmeasured."""
-    import ctypes
     import torch
-    from . import _lib
-    lib = ctx.lib
+    from . import _lib, calls
     rlc = mode == _lib.MODE_RLC
     if rlc and d_randomness is not None:
         raise ValueError("the per-rank RLC protocol returns no randomness")
     lo, hi = shard_range(n_total, world, rank)
     n = hi - lo
     dev = d_bits.device
-    s = ctypes.c_void_p(None if stream is None else stream.cuda_stream)
     lib_stream = torch.cuda.default_stream(dev) if stream is None else stream
     cur = torch.cuda.current_stream(dev)
-    pkb = pk if hasattr(pk, "ctypes") else np.frombuffer(bytes(pk), dtype=np.uint8).copy()
     halo = None
     if world > 1:
         import torch.distributed as dist
@@ -209,30 +195,22 @@ def verify_segment_sharded(ctx, code, pk, first_round, n_total, d_sigs, d_sig_le
             halo = got.to(dev)
             lib_stream.wait_stream(cur)  # the halo is on the device before the library's kernels read it
             halo.record_stream(lib_stream)
-    seedb = np.frombuffer(bytes(seed_prev or b""), dtype=np.uint8).copy()
-    seed_args = (_lib.ptr(seedb) if seedb.size else None, seedb.size)
     halo_args = (None, None) if halo is None else (halo.data_ptr(), halo.data_ptr() + halo_len_offset(sig_stride))
     first = int(first_round) + lo
-    opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    shape = dict(n=n, sig_stride=sig_stride)
     if not rlc:
         if rank == 0 or n == 0:
-            _lib.check(lib.dgpu_verify_segment_device(ctx.handle, code, _lib.ptr(pkb), pkb.size, first, n,
-                                                      d_sigs.data_ptr(), sig_stride, d_sig_len.data_ptr(), *seed_args,
-                                                      mode, 0, d_bits.data_ptr(), opt(d_reason), opt(d_randomness), s),
-                       lib)
+            calls.verify_segment_device(ctx, code, pk, first, d_sigs, d_sig_len, seed_prev, mode, 0, d_bits, d_reason,
+                                        d_randomness, stream, **shape)
         else:
-            _lib.check(lib.dgpu_verify_segment_shard_device(ctx.handle, code, _lib.ptr(pkb), pkb.size, first, n,
-                                                            d_sigs.data_ptr(), sig_stride, d_sig_len.data_ptr(),
-                                                            *halo_args, mode, 0, d_bits.data_ptr(), opt(d_reason),
-                                                            opt(d_randomness), s), lib)
+            calls.verify_segment_shard_device(ctx, code, pk, first, d_sigs, d_sig_len, *halo_args, mode, 0, d_bits,
+                                              d_reason, d_randomness, stream, **shape)
         return
-    rb = lib.dgpu_rlc_root_bytes(code)
-    _lib.check(min(rb, 0))
+    rb = calls.rlc_root_bytes(ctx, code)
     with torch.cuda.stream(lib_stream):  # root allocated in the library's stream order
         root = torch.empty(rb, dtype=torch.uint8, device=dev)
-    _lib.check(lib.dgpu_rlc_root_segment_device(ctx.handle, code, _lib.ptr(pkb), pkb.size, first, n, d_sigs.data_ptr(),
-                                                sig_stride, d_sig_len.data_ptr(), *seed_args,
-                                                *(halo_args if rank and n else (None, None)),
-                                                rank_seed(seed, rank, world), root.data_ptr(), s), lib)
+    calls.rlc_root_segment_device(ctx, code, pk, first, d_sigs, d_sig_len, seed_prev,
+                                  *(halo_args if rank and n else (None, None)), rank_seed(seed, rank, world), root,
+                                  stream, **shape)
     # (the halo tensor stays referenced until the finish step has been enqueued)
-    _finish_rlc_sharded(ctx, root, rb, world, d_bits, d_reason, s, lib_stream, cur)
+    _finish_rlc_sharded(ctx, root, rb, world, d_bits, d_reason, stream, lib_stream, cur)

@@ -17,7 +17,7 @@ import struct
 
 import numpy as np
 
-from . import _lib
+from . import _lib, calls
 from .chain import get_context
 
 R_ORDER = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
@@ -56,6 +56,10 @@ class Chain:
     def __len__(self):
         return len(self.rounds)
 
+    def records(self):
+        """The record arrays in the order the verify calls take them."""
+        return self.rounds, self.sigs, self.sig_len, self.prev, self.prev_len
+
     def beacon(self, i):
         from .chain import Beacon
         return Beacon(bytes(self.prev[i, : self.prev_len[i]]), int(self.rounds[i]),
@@ -67,11 +71,8 @@ def make_chain(seed, n, scheme_code=_lib.SCHEME_CHAINED, seg_len=64, device=0, s
     signed with derive_secret(seed), or with the secret `sk` when given."""
     ctx = get_context(device)
     lib = ctx.lib
-    sk = (derive_secret(seed) if sk is None else sk).to_bytes(32, "big")
-    on_g1 = scheme_code in (_lib.SCHEME_UNCHAINED_G1, _lib.SCHEME_G1_RFC9380)
-    pk = np.zeros(96 if on_g1 else 48, dtype=np.uint8)
-    skb = np.frombuffer(sk, dtype=np.uint8).copy()
-    _lib.check(lib.dgpu_derive_pubkey(ctx.handle, scheme_code, _lib.ptr(skb), _lib.ptr(pk), pk.size))
+    skb = np.frombuffer((derive_secret(seed) if sk is None else sk).to_bytes(32, "big"), dtype=np.uint8).copy()
+    pk = calls.derive_pubkey(ctx, scheme_code, skb)
     seg_len = max(1, min(seg_len, n))
     n_seg = (n + seg_len - 1) // seg_len
     first = (start_round + np.arange(n_seg, dtype=np.uint64) * seg_len).astype(np.uint64)
@@ -81,7 +82,7 @@ def make_chain(seed, n, scheme_code=_lib.SCHEME_CHAINED, seg_len=64, device=0, s
         seeds[s, :32] = np.frombuffer(segment_seed(seed, s + (start_round - 1) // seg_len), dtype=np.uint8)
     out = np.zeros((n_seg * seg_len, 96), dtype=np.uint8)
     _lib.check(lib.dgpu_make_chain(ctx.handle, scheme_code, _lib.ptr(skb), n_seg, seg_len, _lib.ptr(first),
-                                   _lib.ptr(seeds), _lib.ptr(seed_len), _lib.ptr(out)))
+                                   _lib.ptr(seeds), _lib.ptr(seed_len), _lib.ptr(out)), lib)
     out = out[:n]
     rounds = (start_round + np.arange(n, dtype=np.uint64)).astype(np.uint64)
     prev = np.zeros((n, 96), dtype=np.uint8)
@@ -92,8 +93,8 @@ def make_chain(seed, n, scheme_code=_lib.SCHEME_CHAINED, seg_len=64, device=0, s
         starts = np.arange(0, n, seg_len)
         prev[starts] = seeds[: len(starts)]
         prev_len[starts] = 32
-    sig_len = np.full(n, 48 if on_g1 else 96, dtype=np.uint32)
-    return Chain(scheme_code, bytes(pk), rounds, out.copy(), sig_len, prev, prev_len, derive_genesis(seed))
+    sig_len = np.full(n, calls.sig_width(scheme_code), dtype=np.uint32)
+    return Chain(scheme_code, pk, rounds, out.copy(), sig_len, prev, prev_len, derive_genesis(seed))
 
 
 # ---------------------------------------------------------------- corruption catalog
@@ -115,59 +116,10 @@ def splitmix64(x):
     return x, z ^ (z >> 31)
 
 
-def corrupt(chain, seed, rate=1e-3, kinds=ALL_CORRUPTIONS):
-    """Corrupt ~rate*n rounds in place (at least one of each kind).  Returns
-    {index: kind}; every other round is valid by construction."""
-    n = len(chain)
-    count = max(len(kinds), int(round(n * rate)))
+def _choose(seed, n_total, count, kinds, chained):
+    """{index: kind} of `count` rounds of an n_total-round chain, from the seed alone."""
     state = (seed ^ 0xC0FFEE) & 0xFFFFFFFFFFFFFFFF
     chosen = {}
-    chained = chain.scheme_code == _lib.SCHEME_CHAINED
-    k = 0
-    while len(chosen) < min(count, n):
-        state, r = splitmix64(state)
-        i = r % n
-        if i in chosen:
-            continue
-        kind = kinds[k % len(kinds)]
-        k += 1
-        if kind == CORRUPT_PREV and not chained:
-            kind = CORRUPT_Y_SIGN
-        if kind == CORRUPT_OTHER_ROUND and n < 2:
-            kind = CORRUPT_Y_SIGN
-        chosen[int(i)] = kind
-    for i, kind in chosen.items():
-        if kind == CORRUPT_X_BIT:
-            chain.sigs[i, 47] ^= 0x01
-        elif kind == CORRUPT_Y_SIGN:
-            chain.sigs[i, 0] ^= 0x20
-        elif kind == CORRUPT_OTHER_ROUND:
-            j = (i + 1) % n
-            chain.sigs[i] = chain.sigs[j].copy()
-            if j in chosen:  # keep the donor's original bytes irrelevant: any non-matching valid point fails
-                pass
-        elif kind == CORRUPT_PREV:
-            chain.prev[i, 0] ^= 0x01
-        elif kind == CORRUPT_INFINITY:
-            chain.sigs[i] = 0
-            chain.sigs[i, 0] = 0xC0
-        elif kind == CORRUPT_TRUNCATED:
-            chain.sig_len[i] = (chain.sig_len[i] // 2) if (i & 1) else 0
-    return chosen
-
-
-def corrupt_global(shard, seed, n_total, lo, rate=1e-3, kinds=ALL_CORRUPTIONS):
-    """The corruption catalog of a whole n_total-round chain (chosen from the
-    seed alone, like `corrupt`), applied to the shard holding global items
-    [lo, lo + len(shard)).  Returns {global index: kind} for the whole chain,
-    so every rank knows the expected verdict of every round whatever the
-    number of shards; a signature-of-another-round corruption takes its donor
-    from the shard (the next round, or the previous one at the shard's end)."""
-    n = len(shard)
-    count = max(len(kinds), int(round(n_total * rate))) if rate > 0 else 0
-    state = (seed ^ 0xC0FFEE) & 0xFFFFFFFFFFFFFFFF
-    chosen = {}
-    chained = shard.scheme_code == _lib.SCHEME_CHAINED
     k = 0
     while len(chosen) < min(count, n_total):
         state, r = splitmix64(state)
@@ -181,27 +133,52 @@ def corrupt_global(shard, seed, n_total, lo, rate=1e-3, kinds=ALL_CORRUPTIONS):
         if kind == CORRUPT_OTHER_ROUND and n_total < 2:
             kind = CORRUPT_Y_SIGN
         chosen[int(i)] = kind
+    return chosen
+
+
+def _apply(chain, i, kind, donor, odd):
+    """Corrupt record i in place; donor: the record whose signature an
+    other-round corruption takes (None: a one-round shard, where any other
+    valid point fails too)."""
+    if kind == CORRUPT_X_BIT:
+        chain.sigs[i, 47] ^= 0x01
+    elif kind == CORRUPT_Y_SIGN or (kind == CORRUPT_OTHER_ROUND and donor is None):
+        chain.sigs[i, 0] ^= 0x20
+    elif kind == CORRUPT_OTHER_ROUND:
+        chain.sigs[i] = chain.sigs[donor].copy()
+    elif kind == CORRUPT_PREV:
+        chain.prev[i, 0] ^= 0x01
+    elif kind == CORRUPT_INFINITY:
+        chain.sigs[i] = 0
+        chain.sigs[i, 0] = 0xC0
+    elif kind == CORRUPT_TRUNCATED:
+        chain.sig_len[i] = (chain.sig_len[i] // 2) if odd else 0
+
+
+def corrupt(chain, seed, rate=1e-3, kinds=ALL_CORRUPTIONS):
+    """Corrupt ~rate*n rounds in place (at least one of each kind).  Returns
+    {index: kind}; every other round is valid by construction."""
+    n = len(chain)
+    chosen = _choose(seed, n, max(len(kinds), int(round(n * rate))), kinds, chain.scheme_code == _lib.SCHEME_CHAINED)
+    for i, kind in chosen.items():
+        _apply(chain, i, kind, (i + 1) % n, i & 1)
+    return chosen
+
+
+def corrupt_global(shard, seed, n_total, lo, rate=1e-3, kinds=ALL_CORRUPTIONS):
+    """The corruption catalog of a whole n_total-round chain (chosen from the
+    seed alone, like `corrupt`), applied to the shard holding global items
+    [lo, lo + len(shard)).  Returns {global index: kind} for the whole chain,
+    so every rank knows the expected verdict of every round whatever the
+    number of shards; a signature-of-another-round corruption takes its donor
+    from the shard (the next round, or the previous one at the shard's end)."""
+    n = len(shard)
+    count = max(len(kinds), int(round(n_total * rate))) if rate > 0 else 0
+    chosen = _choose(seed, n_total, count, kinds, shard.scheme_code == _lib.SCHEME_CHAINED)
     for gi, kind in chosen.items():
         i = gi - lo
-        if not 0 <= i < n:
-            continue
-        if kind == CORRUPT_X_BIT:
-            shard.sigs[i, 47] ^= 0x01
-        elif kind == CORRUPT_Y_SIGN:
-            shard.sigs[i, 0] ^= 0x20
-        elif kind == CORRUPT_OTHER_ROUND:
-            j = i + 1 if i + 1 < n else i - 1
-            if j < 0:  # one-round shard: any other valid point fails too
-                shard.sigs[i, 0] ^= 0x20
-            else:
-                shard.sigs[i] = shard.sigs[j].copy()
-        elif kind == CORRUPT_PREV:
-            shard.prev[i, 0] ^= 0x01
-        elif kind == CORRUPT_INFINITY:
-            shard.sigs[i] = 0
-            shard.sigs[i, 0] = 0xC0
-        elif kind == CORRUPT_TRUNCATED:
-            shard.sig_len[i] = (shard.sig_len[i] // 2) if (gi & 1) else 0
+        if 0 <= i < n:
+            _apply(shard, i, kind, i + 1 if i + 1 < n else (i - 1 if i else None), gi & 1)
     return chosen
 
 
@@ -237,22 +214,12 @@ def poly_eval(coeffs, x):
     return acc
 
 
-def _sig_len(scheme):
-    return 48 if scheme in (_lib.SCHEME_UNCHAINED_G1, _lib.SCHEME_G1_RFC9380) else 96
-
-
 def make_group(seed, t, n, device=0, scheme=_lib.SCHEME_CHAINED):
     """Commitments derived on the GPU (dgpu_derive_pubkey per coefficient):
     on G1, or on G2 for a G1-signature scheme code."""
     ctx = get_context(device)
     coeffs = share_coeffs(seed, t)
-    commits = []
-    klen = 144 - _sig_len(scheme)  # the key group is the other one
-    for a in coeffs:
-        pk = np.zeros(klen, dtype=np.uint8)
-        skb = np.frombuffer(a.to_bytes(32, "big"), dtype=np.uint8).copy()
-        _lib.check(ctx.lib.dgpu_derive_pubkey(ctx.handle, scheme, _lib.ptr(skb), _lib.ptr(pk), klen))
-        commits.append(bytes(pk))
+    commits = [calls.derive_pubkey(ctx, scheme, a) for a in coeffs]
     return Group(seed, t, n, coeffs, commits, scheme)
 
 
@@ -268,13 +235,8 @@ def sign_partials(group, msgs, sign_idx, labels=None, device=0, scheme=None):
     msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
     sign_idx = np.ascontiguousarray(sign_idx, dtype=np.uint32)
     labels = sign_idx if labels is None else np.ascontiguousarray(labels, dtype=np.uint32)
-    nr, m = sign_idx.shape
     shares = np.frombuffer(b"".join(s.to_bytes(32, "big") for s in group.shares), dtype=np.uint8).copy()
-    out = np.zeros((nr, m, 2 + _sig_len(scheme)), dtype=np.uint8)
-    _lib.check(ctx.lib.dgpu_make_partials_scheme(ctx.handle, scheme, nr, _lib.ptr(msgs), m, _lib.ptr(sign_idx),
-                                                 _lib.ptr(labels), _lib.ptr(shares), len(group.shares),
-                                                 _lib.ptr(out)))
-    return out
+    return calls.make_partials_scheme(ctx, scheme, msgs, sign_idx, labels, shares)
 
 
 def group_signatures(group, msgs, device=0, scheme=None):
@@ -283,13 +245,9 @@ def group_signatures(group, msgs, device=0, scheme=None):
     scheme = group.scheme_code if scheme is None else scheme
     ctx = get_context(device)
     msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
-    nr = msgs.shape[0]
-    zeros = np.zeros(nr, dtype=np.uint32)
+    zeros = np.zeros((msgs.shape[0], 1), dtype=np.uint32)
     sk = np.frombuffer(group.coeffs[0].to_bytes(32, "big"), dtype=np.uint8).copy()
-    out = np.zeros((nr, 2 + _sig_len(scheme)), dtype=np.uint8)
-    _lib.check(ctx.lib.dgpu_make_partials_scheme(ctx.handle, scheme, nr, _lib.ptr(msgs), 1, _lib.ptr(zeros),
-                                                 _lib.ptr(zeros), _lib.ptr(sk), 1, _lib.ptr(out)))
-    return out[:, 2:].copy()
+    return calls.make_partials_scheme(ctx, scheme, msgs, zeros, zeros, sk)[:, 0, 2:].copy()
 
 
 def make_recovery_batch(group, n_rounds, seed, bad_rate=0.1, first_round=1, device=0, scheme=None):

@@ -18,11 +18,10 @@ import threading
 
 import numpy as np
 
-from . import _lib
-from .chain import get_context, rlc_seed_for
+from . import _lib, calls
+from .calls import G1_SIG_CODES as _G1_SIG_CODES, sig_width as sig_bytes  # noqa: F401  (sig_bytes: the older name)
+from .chain import get_context
 from .scheme import Scheme, get_scheme_by_id_with_default, scheme_code
-
-_G1_SIG_CODES = (_lib.SCHEME_UNCHAINED_G1, _lib.SCHEME_G1_RFC9380)
 
 
 def group_scheme_code(commits, scheme=None):
@@ -41,18 +40,13 @@ def group_scheme_code(commits, scheme=None):
         code = int(scheme)
         if code not in (_lib.SCHEME_CHAINED, _lib.SCHEME_UNCHAINED) + _G1_SIG_CODES:
             raise ValueError(f"scheme code {code} is not valid")
-    want = 96 if code in _G1_SIG_CODES else 48
+    want = calls.key_width(code)
     lens = {len(c) for c in commits}
     if lens != {want}:
         if scheme is None and lens == {96}:
             raise ValueError("96-byte (G2) commitments need a G1-signature scheme")
         raise ValueError(f"commitments of lengths {sorted(lens)} do not fit the scheme ({want} bytes each)")
     return code
-
-
-def sig_bytes(code):
-    """Signature length of a scheme code: 48 on G1, 96 on G2."""
-    return 48 if code in _G1_SIG_CODES else 96
 
 
 class RecoverError(Exception):
@@ -98,41 +92,30 @@ def unpack_recovered(out, ok, pv, partials, m, sig_len=96):
 
 
 class ThresholdGroup:
-    """A group's share.PubPoly installed on one GPU context."""
+    """A group's share.PubPoly installed on one GPU context.  A context holds
+    one group at a time and calls.set_group records which on the context
+    object, so groups that share a context take turns."""
 
     _lock = threading.Lock()
 
-    def __init__(self, commits, n, device=0, scheme=None):
+    def __init__(self, commits, n, device=0, scheme=None, ctx=None):
         """scheme: None (48-byte G1 commitments, G2 signatures, as always), or
         a scheme name / Scheme / code; 96-byte G2 commitments require one of
         the G1-signature schemes.  A mismatch raises ValueError before any
-        library call."""
+        library call.  ctx: a context of the caller's (default: the device's
+        shared one)."""
         self.commits = [bytes(c) for c in commits]
         self.scheme_code = group_scheme_code(self.commits, scheme)
         self.sig_len = sig_bytes(self.scheme_code)
         self.t = len(self.commits)
         self.n = n
-        self.ctx = get_context(device)
+        self.ctx = ctx or get_context(device)
         with ThresholdGroup._lock:
-            ThresholdGroup._active = None
-            self._set_group()
-            ThresholdGroup._active = self._key()
-
-    def _key(self):
-        return (id(self.ctx), self.scheme_code, tuple(self.commits), self.n)
-
-    def _set_group(self):
-        buf = np.frombuffer(b"".join(self.commits), dtype=np.uint8).copy()
-        if self.sig_len == 96:
-            _lib.check(self.ctx.lib.dgpu_set_group(self.ctx.handle, self.t, self.n, _lib.ptr(buf)))
-        else:
-            _lib.check(self.ctx.lib.dgpu_set_group_scheme(self.ctx.handle, self.scheme_code, self.t, self.n,
-                                                          _lib.ptr(buf), len(self.commits[0])))
+            self._key = calls.set_group(self.ctx, self.scheme_code, self.t, n, self.commits)
 
     def _install(self):
-        if getattr(ThresholdGroup, "_active", None) != self._key():
-            self._set_group()
-            ThresholdGroup._active = self._key()
+        if getattr(self.ctx, "installed_group", None) != self._key:
+            calls.set_group(self.ctx, self.scheme_code, self.t, self.n, self.commits)
 
     def recover_batch(self, msgs, partials, statuses=True):
         """msgs: list of 32-byte messages (DigestMessage of each round);
@@ -142,17 +125,12 @@ class ThresholdGroup:
         (the reference's error), valid[r][j] = partial j verified.  With
         statuses=False valid is None and the library verifies each round's
         candidates with one batched pairing (recover.cuh)."""
-        nr = len(msgs)
-        if nr == 0:
+        if len(msgs) == 0:
             return [], []
         mb, buf, plen, m, stride = pack_partials(msgs, partials, self.scheme_code)
-        out = np.zeros(nr * self.sig_len, dtype=np.uint8)
-        ok = np.zeros((nr + 7) // 8, dtype=np.uint8)
-        pv = np.zeros(nr * m, dtype=np.uint8) if statuses else None
         with ThresholdGroup._lock:
             self._install()
-            _lib.check(self.ctx.lib.dgpu_recover_batch(self.ctx.handle, nr, _lib.ptr(mb), m, _lib.ptr(buf), stride,
-                                                       _lib.ptr(plen), _lib.ptr(out), _lib.ptr(ok), _lib.ptr(pv)))
+            out, ok, pv = calls.recover_batch(self.ctx, mb, buf, plen, self.sig_len, statuses)
         return unpack_recovered(out, ok, pv, partials, m, self.sig_len)
 
     def verify_partials(self, msgs, partials, mode=_lib.MODE_PER_ROUND, rlc_seed=None):
@@ -166,17 +144,9 @@ class ThresholdGroup:
         if nr == 0:
             return []
         mb, buf, plen, m, stride = pack_partials(msgs, partials, self.scheme_code)
-        bits = np.zeros((nr * m + 7) // 8, dtype=np.uint8)
-        reason = np.zeros(nr * m, dtype=np.uint8)
-        seed = rlc_seed_for(mode, rlc_seed)
         with ThresholdGroup._lock:
             self._install()
-            _lib.check(self.ctx.lib.dgpu_verify_partials(self.ctx.handle, nr, _lib.ptr(mb), m, _lib.ptr(buf), stride,
-                                                         _lib.ptr(plen), mode, seed, _lib.ptr(bits),
-                                                         _lib.ptr(reason)))
-        valid = np.unpackbits(bits, bitorder="little")[:nr * m].astype(bool)
-        if not np.array_equal(valid, reason == _lib.REASON_OK):
-            raise _lib.DrandGPUError(_lib.DGPU_EINVAL, "verdict bitmap and reasons disagree")
+            reason = calls.verify_partials(self.ctx, mb, buf, plen, mode, rlc_seed)
         return [[int(reason[r * m + j]) for j in range(len(partials[r]))] for r in range(nr)]
 
     def recover(self, msg, sigs):

@@ -3,6 +3,8 @@ tests/test_gpu_ingest_rows.py): canonical Beacon.Marshal rows and every way
 of leaving the canonical form that dgpu_ingest_decode distinguishes."""
 import random
 
+import numpy as np
+
 
 def marshal(prev, rnd, sig, case=str.lower):
     """Beacon.Marshal's layout; prev / sig: bytes, or None for JSON null;
@@ -10,6 +12,13 @@ def marshal(prev, rnd, sig, case=str.lower):
     def field(b):
         return "null" if b is None else '"' + case(b.hex()) + '"'
     return ('{"PreviousSig":%s,"Round":%s,"Signature":%s}' % (field(prev), rnd, field(sig))).encode()
+
+
+def pack(rows, lead=b""):
+    """Rows back to back behind `lead`: (buffer, offsets, lengths)."""
+    ln = np.array([len(r) for r in rows], dtype=np.uint32)
+    off = (len(lead) + np.concatenate([[0], np.cumsum(ln, dtype=np.uint64)[:-1]])).astype(np.uint64)
+    return np.frombuffer(lead + b"".join(rows), dtype=np.uint8).copy(), off, ln
 
 
 def _mixed(h):

@@ -14,6 +14,14 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(dgpu_[a-z0-9_]+)\s*\(", txt)))
 
 
+def declared_params(name):
+    """Parameter list of `name`'s declaration in the header (comments cut, blanks folded)."""
+    txt = open(os.path.join(ROOT, "include", "drand_gpu.h")).read()
+    m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*?)\)\s*;", txt, re.S)
+    assert m, f"{name} is not declared in include/drand_gpu.h"
+    return [" ".join(p.split()) for p in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(",")]
+
+
 def test_header_and_binding_agree():
     from drand_amd import _lib
     assert sorted(n for n, _, _ in _lib.SYMBOLS) == declared_symbols()

@@ -13,6 +13,8 @@ per-round verdicts of test_gpu_parity.py:
   * the multi-GPU handle (dgpu_verify_multi) with one device equals the
     single-context verdicts (RCCL all-gathers over one rank).
 Marked gpu."""
+import contextlib
+
 import numpy as np
 import pytest
 
@@ -41,7 +43,7 @@ def test_sign_and_verify_recovered_any_length(name, gpu_ctx):
     """AuthScheme.Sign -> VerifyRecovered round trip over raw messages of many
     lengths; a signature of another message, a wrong key and an empty
     signature fail; signatures equal the oracle's sk * H(msg)."""
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     from drand_amd.chain import sign, verify_recovered
     from drand_amd.synth import derive_secret
     sch = _sch(name)
@@ -51,10 +53,7 @@ def test_sign_and_verify_recovered_any_length(name, gpu_ctx):
     sigs = sign(sk, msgs, sch)
     code = _lib.SCHEME_UNCHAINED_G1 if name == "bls-unchained-on-g1" else (
         _lib.SCHEME_G1_RFC9380 if on_g1 else _lib.SCHEME_CHAINED)
-    pk = np.zeros(96 if on_g1 else 48, dtype=np.uint8)
-    skb = np.frombuffer(sk.to_bytes(32, "big"), dtype=np.uint8).copy()
-    _lib.check(gpu_ctx.lib.dgpu_derive_pubkey(gpu_ctx.handle, code, _lib.ptr(skb), _lib.ptr(pk), pk.size))
-    pk = bytes(pk)
+    pk = calls.derive_pubkey(gpu_ctx, code, sk)
     assert verify_recovered(sch, pk, msgs, sigs).tolist() == [0] * len(msgs)
     swapped = sigs[1:] + sigs[:1]
     assert verify_recovered(sch, pk, msgs, swapped).tolist() == [3] * len(msgs)
@@ -106,7 +105,7 @@ def test_reference_legacy_encodings_decode_on_gpu(gpu_ctx):
     Decode only: test.json's message and hash predate RFC 9380 (its signature
     verifies under none of SHA-256(prev||round), SHA-256(round) with either
     RFC 9380 DST), so no verdict is asserted."""
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     from drand_amd.chain import decode_pubkey, decode_signatures
     cases = load_golden("reference_legacy_encodings.json")["cases"]
     for grp, sig_schemes, key_schemes in (
@@ -134,8 +133,7 @@ def test_reference_legacy_encodings_decode_on_gpu(gpu_ctx):
                         decode_pubkey(_sch(name), r)
     # the stored test.json key installs as an on-G1 scheme's key (line table built)
     pub = next(c for c in cases if c["kind"] == "as_stored" and c["group"] == "g2")
-    pkb = np.frombuffer(bytes.fromhex(pub["hex"]), dtype=np.uint8).copy()
-    _lib.check(gpu_ctx.lib.dgpu_set_pubkey(gpu_ctx.handle, _lib.SCHEME_UNCHAINED_G1, _lib.ptr(pkb), 96))
+    calls.set_pubkey(gpu_ctx, _lib.SCHEME_UNCHAINED_G1, bytes.fromhex(pub["hex"]))
 
 
 def test_two_chains_two_keys_one_context(gpu_ctx):
@@ -198,19 +196,15 @@ def test_rlc_localize_then_confirm_and_fallback(gpu_ctx):
     one node) slip past the localization: the confirmation fails and the
     random-coefficient tree finds them -- verdicts equal per-round mode either
     way."""
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     from drand_amd.chain import Beacon, Verifier
     from drand_amd.synth import corrupt, make_chain
     v = Verifier(_sch("pedersen-bls-chained"))
-    lib = v.ctx.lib
 
     def rlc_stages(beacons, pk):
-        _lib.check(lib.dgpu_set_profiling(v.ctx.handle, 1))
-        try:
+        with calls.profiled(v.ctx) as stage_times:
             got = v.verify_reasons(beacons, pk, _lib.MODE_RLC)
-            return got, set(_lib.stage_times(v.ctx))
-        finally:
-            _lib.check(lib.dgpu_set_profiling(v.ctx.handle, 0))
+            return got, set(stage_times())
 
     c = make_chain(45, 4000, _lib.SCHEME_CHAINED, seg_len=64)
     corrupt(c, 45, rate=3e-3)
@@ -238,20 +232,16 @@ def test_rlc_localize_then_confirm_and_fallback(gpu_ctx):
 def test_rlc_root_first_clean_and_single_bad(gpu_ctx):
     """A clean batch passes with the root check alone; one bad round among
     70k is found (descent from the root) -- verdicts equal per-round mode."""
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     from drand_amd.chain import Verifier
     from drand_amd.synth import corrupt, make_chain
     import ctypes
     v = Verifier(_sch("pedersen-bls-chained"))
     c = make_chain(43, 70000, _lib.SCHEME_CHAINED, seg_len=64)
     beacons = [c.beacon(i) for i in range(len(c))]
-    lib = v.ctx.lib
-    _lib.check(lib.dgpu_set_profiling(v.ctx.handle, 1))
-    try:
+    with calls.profiled(v.ctx) as stage_times:
         assert not v.verify_reasons(beacons, c.pk, _lib.MODE_RLC).any()
-        stages = set(_lib.stage_times(v.ctx))
-    finally:
-        _lib.check(lib.dgpu_set_profiling(v.ctx.handle, 0))
+        stages = set(stage_times())
     # the bucket-MSM root (rlc_msm.cuh) equals the tree's: a clean batch
     # passes on it alone, without building the leaves
     assert "rlc_root_msm" in stages and "rlc_leaves_tree" not in stages, stages
@@ -266,9 +256,8 @@ def test_device_record_over_stride_fails_without_overrun(gpu_ctx):
     """dgpu_verify_beacons_device with prev_len[i] > prev_stride: round i is
     not read past its stride and fails (DGPU_REASON_DECODE); the others keep
     their verdicts."""
-    import ctypes
     import torch
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     from drand_amd.synth import make_chain
     c = make_chain(51, 64, _lib.SCHEME_CHAINED, seg_len=64)
     n = len(c)
@@ -281,18 +270,13 @@ def test_device_record_over_stride_fails_without_overrun(gpu_ctx):
                                                       ("pl", prev_len.view(np.int32)))}
     bits = torch.zeros((n + 7) // 8, dtype=torch.uint8, device=dev)
     reason = torch.zeros(n, dtype=torch.uint8, device=dev)
-    pk = np.frombuffer(c.pk, dtype=np.uint8).copy()
-    stream = torch.cuda.current_stream(dev)
-    _lib.check(gpu_ctx.lib.dgpu_verify_beacons_device(
-        gpu_ctx.handle, _lib.SCHEME_CHAINED, _lib.ptr(pk), pk.size, n, t["r"].data_ptr(), t["s"].data_ptr(), 96,
-        t["sl"].data_ptr(), t["p"].data_ptr(), 96, t["pl"].data_ptr(), _lib.MODE_PER_ROUND, 0, bits.data_ptr(),
-        reason.data_ptr(), ctypes.c_void_p(stream.cuda_stream)))
+    calls.verify_beacons_device(gpu_ctx, _lib.SCHEME_CHAINED, c.pk, t["r"], t["s"], t["sl"], t["p"], t["pl"],
+                                _lib.MODE_PER_ROUND, 0, bits, reason, torch.cuda.current_stream(dev))
     torch.cuda.synchronize()
-    r = reason.cpu().numpy()
+    r = calls.check_bitmap(bits.cpu().numpy(), reason.cpu().numpy())
     expect = np.zeros(n, dtype=np.uint8)
     expect[[5, 9]] = 1
     assert r.tolist() == expect.tolist()
-    assert np.array_equal(np.unpackbits(bits.cpu().numpy(), bitorder="little")[:n].astype(bool), r == 0)
 
 
 def test_unpinned_x_ge_p_rejected(gpu_ctx):
@@ -339,9 +323,8 @@ def test_async_calls_on_two_streams_are_ordered(gpu_ctx):
     """Two dgpu_verify_beacons_device calls on different streams share the
     context's scratch; the second is ordered after the first on the device
     (ADVICE r01), so both verdict sets are right."""
-    import ctypes
     import torch
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     from drand_amd.synth import corrupt, make_chain
     dev = torch.device("cuda", 0)
     chains = [make_chain(71 + k, 40000, _lib.SCHEME_CHAINED, seg_len=64) for k in range(2)]
@@ -361,10 +344,7 @@ def test_async_calls_on_two_streams_are_ordered(gpu_ctx):
             bits = torch.zeros((len(c) + 7) // 8, dtype=torch.uint8, device=dev)
         pk = np.frombuffer(c.pk, dtype=np.uint8).copy()
         keep.append((t, pk))
-        _lib.check(gpu_ctx.lib.dgpu_verify_beacons_device(
-            gpu_ctx.handle, _lib.SCHEME_CHAINED, _lib.ptr(pk), pk.size, len(c), t[0].data_ptr(), t[1].data_ptr(), 96,
-            t[2].data_ptr(), t[3].data_ptr(), 96, t[4].data_ptr(), _lib.MODE_PER_ROUND, 0, bits.data_ptr(), None,
-            ctypes.c_void_p(st.cuda_stream)))
+        calls.verify_beacons_device(gpu_ctx, _lib.SCHEME_CHAINED, pk, *t, _lib.MODE_PER_ROUND, 0, bits, None, st)
         outs.append(bits)
     torch.cuda.synchronize()
     for c, bad, bits in zip(chains, bads, outs):
@@ -383,9 +363,8 @@ def test_null_stream_is_the_default_stream(mode, gpu_ctx):
     packing never leaves (0xA5), inputs are copied with non_blocking H2D on
     the default stream; per-round and RLC mode (a 70k batch, above the RLC
     threshold), verdicts and reasons equal construction."""
-    import ctypes
     import torch
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     from drand_amd.synth import corrupt, make_chain
     dev = torch.device("cuda", 0)
     assert torch.cuda.current_stream(dev).cuda_stream == 0
@@ -396,11 +375,7 @@ def test_null_stream_is_the_default_stream(mode, gpu_ctx):
          for a in (c.rounds.view(np.int64), c.sigs, c.sig_len.view(np.int32), c.prev, c.prev_len.view(np.int32))]
     bits = torch.full(((n + 7) // 8,), 0xA5, dtype=torch.uint8, device=dev)
     reason = torch.full((n,), 0xA5, dtype=torch.uint8, device=dev)
-    pk = np.frombuffer(c.pk, dtype=np.uint8).copy()
-    _lib.check(gpu_ctx.lib.dgpu_verify_beacons_device(
-        gpu_ctx.handle, _lib.SCHEME_CHAINED, _lib.ptr(pk), pk.size, n, t[0].data_ptr(), t[1].data_ptr(), 96,
-        t[2].data_ptr(), t[3].data_ptr(), 96, t[4].data_ptr(), mode, 12345, bits.data_ptr(), reason.data_ptr(),
-        ctypes.c_void_p(None)))
+    calls.verify_beacons_device(gpu_ctx, _lib.SCHEME_CHAINED, c.pk, *t, mode, 12345, bits, reason)
     got = np.unpackbits(bits.cpu().numpy(), bitorder="little")[:n].astype(bool)
     r = reason.cpu().numpy()
     expect = np.ones(n, dtype=bool)
@@ -408,7 +383,7 @@ def test_null_stream_is_the_default_stream(mode, gpu_ctx):
     assert np.array_equal(got, expect)
     assert np.array_equal(r == 0, expect) and set(np.unique(r)) <= {0, 1, 2, 3, 4}
     # dgpu_synchronize: the host-side wait a caller without HIP (cgo) uses
-    _lib.check(gpu_ctx.lib.dgpu_synchronize(gpu_ctx.handle))
+    calls.synchronize(gpu_ctx)
 
 
 def test_engine_chunk_retry_after_out_of_memory(gpu_ctx):
@@ -418,27 +393,16 @@ def test_engine_chunk_retry_after_out_of_memory(gpu_ctx):
     20,000 rounds.  The call succeeds with the verdicts of an unconstrained
     context and leaves no stale error message; a later call on the context
     still works."""
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     from drand_amd.synth import corrupt, make_chain
     n = 40000
     c = make_chain(71, n, _lib.SCHEME_CHAINED, seg_len=64)
     bad = corrupt(c, 71, rate=1e-3)
-    ctx = open_ctx({"DGPU_TEST_ALLOC_CAP": str(1 << 30)})
-    try:
+    with contextlib.closing(open_ctx({"DGPU_TEST_ALLOC_CAP": str(1 << 30)})) as ctx:
         got = []
         for _ in range(2):
-            bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-            reason = np.zeros(n, dtype=np.uint8)
-            pk = np.frombuffer(c.pk, dtype=np.uint8).copy()
-            _lib.check(ctx.lib.dgpu_verify_beacons(ctx.handle, _lib.SCHEME_CHAINED, _lib.ptr(pk), pk.size, n,
-                                                   _lib.ptr(c.rounds), _lib.ptr(c.sigs), c.sigs.shape[1],
-                                                   _lib.ptr(c.sig_len), _lib.ptr(c.prev), c.prev.shape[1],
-                                                   _lib.ptr(c.prev_len), _lib.MODE_PER_ROUND, 0, _lib.ptr(bits),
-                                                   _lib.ptr(reason)), ctx.lib)
+            got.append(calls.verify_beacons(ctx, _lib.SCHEME_CHAINED, c.pk, *c.records(), fill=0xEE))
             assert ctx.lib.dgpu_last_error() == b""
-            got.append(reason)
-    finally:
-        ctx.close()
     expect = np.ones(n, dtype=bool)
     expect[list(bad.keys())] = False
     assert np.array_equal(got[0] == 0, expect) and got[0].tolist() == got[1].tolist()
@@ -455,23 +419,20 @@ def test_host_records_staged_through_the_ring(n, scheme, gpu_ctx):
     construction), and the caller's buffers are free to reuse after the
     call (they are overwritten and verified again)."""
     import torch
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     from drand_amd.synth import corrupt, make_chain
     code = getattr(_lib, scheme)
     c = make_chain(73, n, code, seg_len=64)
     pristine = {k: getattr(c, k).copy() for k in ("sigs", "sig_len", "prev", "prev_len")}
     bad = corrupt(c, 73, rate=1e-3)
-    pk = np.frombuffer(c.pk, dtype=np.uint8).copy()
-    lib, h = gpu_ctx.lib, gpu_ctx.handle
 
     def host_call():
-        bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-        reason = np.zeros(n, dtype=np.uint8)
-        _lib.check(lib.dgpu_verify_beacons(h, code, _lib.ptr(pk), pk.size, n, _lib.ptr(c.rounds), _lib.ptr(c.sigs),
-                                           c.sigs.shape[1], _lib.ptr(c.sig_len), _lib.ptr(c.prev), c.prev.shape[1],
-                                           _lib.ptr(c.prev_len), _lib.MODE_PER_ROUND, 0, _lib.ptr(bits),
-                                           _lib.ptr(reason)))
-        return reason
+        return calls.verify_beacons(gpu_ctx, code, c.pk, *c.records(), fill=0xEE)
+
+    def device_call():
+        calls.verify_beacons_device(gpu_ctx, code, c.pk, *(dev[k] for k in ("rounds", "sigs", "sig_len", "prev", "prev_len")),
+                                    _lib.MODE_PER_ROUND, 0, dbits, dreason)
+        torch.cuda.synchronize()
 
     got = host_call()
     ms, host_ms, nbytes = _lib.staging_stats(gpu_ctx)
@@ -481,11 +442,7 @@ def test_host_records_staged_through_the_ring(n, scheme, gpu_ctx):
            for k in ("rounds", "sigs", "sig_len", "prev", "prev_len")}
     dbits = torch.zeros((n + 7) // 8, dtype=torch.uint8, device="cuda")
     dreason = torch.zeros(n, dtype=torch.uint8, device="cuda")
-    _lib.check(lib.dgpu_verify_beacons_device(h, code, _lib.ptr(pk), pk.size, n, _lib.ptr(dev["rounds"]),
-                                              _lib.ptr(dev["sigs"]), c.sigs.shape[1], _lib.ptr(dev["sig_len"]),
-                                              _lib.ptr(dev["prev"]), c.prev.shape[1], _lib.ptr(dev["prev_len"]),
-                                              _lib.MODE_PER_ROUND, 0, _lib.ptr(dbits), _lib.ptr(dreason), None))
-    torch.cuda.synchronize()
+    device_call()
     assert dreason.cpu().numpy().tolist() == got.tolist()
     expect = np.ones(n, dtype=bool)
     expect[list(bad.keys())] = False
@@ -503,11 +460,7 @@ def test_host_records_staged_through_the_ring(n, scheme, gpu_ctx):
     try:
         again = host_call()
         dev["sigs"].copy_(torch.from_numpy(c.sigs))
-        _lib.check(lib.dgpu_verify_beacons_device(h, code, _lib.ptr(pk), pk.size, n, _lib.ptr(dev["rounds"]),
-                                                  _lib.ptr(dev["sigs"]), c.sigs.shape[1], _lib.ptr(dev["sig_len"]),
-                                                  _lib.ptr(dev["prev"]), c.prev.shape[1], _lib.ptr(dev["prev_len"]),
-                                                  _lib.MODE_PER_ROUND, 0, _lib.ptr(dbits), _lib.ptr(dreason), None))
-        torch.cuda.synchronize()
+        device_call()
     finally:
         c.sigs[:] = keep
     assert dreason.cpu().numpy().tolist() == again.tolist()
@@ -540,29 +493,21 @@ def test_raw_messages_tail_bytes_reach_the_device(n, scheme, gpu_ctx):
     tests/test_copy_pool.py is the host check).  Those bytes are the end of
     the last message: its verdict must follow them.  The signatures come from
     dgpu_sign, which stages with plain hipMemcpyAsync and never uses the ring."""
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     from drand_amd.synth import derive_secret
     code = getattr(_lib, scheme)
-    lib, h = gpu_ctx.lib, gpu_ctx.handle
     width = 48 if code == _lib.SCHEME_UNCHAINED_G1 else 96
     stride = 97
     msgs = np.random.default_rng(9700 + n).integers(0, 256, size=(n, stride), dtype=np.uint8)
     msg_len = np.full(n, stride, dtype=np.uint32)
-    skb = np.frombuffer(derive_secret(97).to_bytes(32, "big"), dtype=np.uint8).copy()
-    pk = np.zeros(144 - width, dtype=np.uint8)
-    _lib.check(lib.dgpu_derive_pubkey(h, code, _lib.ptr(skb), _lib.ptr(pk), pk.size))
-    sigs = np.zeros((n, width), dtype=np.uint8)
+    sk = derive_secret(97)
+    pk = calls.derive_pubkey(gpu_ctx, code, sk)
+    sigs = calls.sign(gpu_ctx, code, sk, msgs, msg_len)
     sig_len = np.full(n, width, dtype=np.uint32)
-    _lib.check(lib.dgpu_sign(h, code, _lib.ptr(skb), n, _lib.ptr(msgs), stride, _lib.ptr(msg_len), _lib.ptr(sigs)))
+    assert sigs.shape == (n, width)
 
     def verify():
-        bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-        reason = np.full(n, 0xEE, dtype=np.uint8)
-        _lib.check(lib.dgpu_verify_recovered(h, code, _lib.ptr(pk), pk.size, n, _lib.ptr(msgs), stride,
-                                             _lib.ptr(msg_len), _lib.ptr(sigs), width, _lib.ptr(sig_len),
-                                             _lib.MODE_PER_ROUND, 0, _lib.ptr(bits), _lib.ptr(reason)))
-        assert np.array_equal(np.unpackbits(bits, bitorder="little")[:n].astype(bool), reason == 0)
-        return reason
+        return calls.verify_recovered(gpu_ctx, code, pk, msgs, msg_len, sigs, sig_len, fill=0xEE)
 
     expect = np.zeros(n, dtype=np.uint8)
     assert np.array_equal(verify(), expect)
@@ -571,8 +516,7 @@ def test_raw_messages_tail_bytes_reach_the_device(n, scheme, gpu_ctx):
     expect[n - 1] = _lib.REASON_PAIRING
     assert np.array_equal(verify(), expect)
     # ... and it is signed again
-    _lib.check(lib.dgpu_sign(h, code, _lib.ptr(skb), 1, _lib.ptr(msgs[n - 1:]), stride, _lib.ptr(msg_len[n - 1:]),
-                             _lib.ptr(sigs[n - 1:])))
+    sigs[n - 1:] = calls.sign(gpu_ctx, code, sk, msgs[n - 1:], msg_len[n - 1:])
     expect[n - 1] = 0
     assert np.array_equal(verify(), expect)
 
@@ -601,16 +545,14 @@ def test_length_array_tail_reaches_the_device(gpu_ctx):
     for 1).  Reasons equal the device-resident entry point's on the same
     records, and the construction."""
     import torch
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     from drand_amd.synth import corrupt, make_chain
     n = 1048641
     code = _lib.SCHEME_UNCHAINED_G1
-    lib, h = gpu_ctx.lib, gpu_ctx.handle
     c = make_chain(1048641, n, code, seg_len=256)
     bad = corrupt(c, 1048641, rate=1e-4)
     assert n - 1 not in bad and c.sig_len[n - 1] == 48
     assert c.sigs.shape[1] == 96 and not c.sigs[:, 48:].any()
-    pk = np.frombuffer(c.pk, dtype=np.uint8).copy()
     dev = {k: torch.from_numpy(np.ascontiguousarray(getattr(c, k))).cuda()
            for k in ("rounds", "sigs", "sig_len", "prev", "prev_len")}
     dbits = torch.zeros((n + 7) // 8, dtype=torch.uint8, device="cuda")
@@ -619,22 +561,14 @@ def test_length_array_tail_reaches_the_device(gpu_ctx):
     expect[list(bad.keys())] = False
 
     def check(last_reason):
-        bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-        got = np.full(n, 0xEE, dtype=np.uint8)
-        _lib.check(lib.dgpu_verify_beacons(h, code, _lib.ptr(pk), pk.size, n, _lib.ptr(c.rounds), _lib.ptr(c.sigs),
-                                           c.sigs.shape[1], _lib.ptr(c.sig_len), _lib.ptr(c.prev), c.prev.shape[1],
-                                           _lib.ptr(c.prev_len), _lib.MODE_PER_ROUND, 0, _lib.ptr(bits),
-                                           _lib.ptr(got)))
+        got = calls.verify_beacons(gpu_ctx, code, c.pk, *c.records(), fill=0xEE)
         dev["sigs"].copy_(torch.from_numpy(c.sigs))
         dev["sig_len"].copy_(torch.from_numpy(c.sig_len))
-        _lib.check(lib.dgpu_verify_beacons_device(h, code, _lib.ptr(pk), pk.size, n, _lib.ptr(dev["rounds"]),
-                                                  _lib.ptr(dev["sigs"]), c.sigs.shape[1], _lib.ptr(dev["sig_len"]),
-                                                  _lib.ptr(dev["prev"]), c.prev.shape[1], _lib.ptr(dev["prev_len"]),
-                                                  _lib.MODE_PER_ROUND, 0, _lib.ptr(dbits), _lib.ptr(dreason), None))
+        calls.verify_beacons_device(gpu_ctx, code, c.pk, *(dev[k] for k in ("rounds", "sigs", "sig_len", "prev", "prev_len")),
+                                    _lib.MODE_PER_ROUND, 0, dbits, dreason)
         torch.cuda.synchronize()
         assert got[n - 1] == last_reason
         assert np.array_equal(dreason.cpu().numpy(), got)
-        assert np.array_equal(np.unpackbits(bits, bitorder="little")[:n].astype(bool), got == 0)
         assert np.array_equal(got == 0, expect)
 
     check(_lib.REASON_OK)
@@ -650,35 +584,25 @@ def test_alloc_cap_is_reset_by_the_next_open():
     the cap a closed context left, so a test's result does not depend on the
     tests before it.  The cap is a host-side check in front of hipMalloc:
     nothing on the device fails."""
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     from drand_amd.synth import make_chain
     n = 64
     c = make_chain(74, n, _lib.SCHEME_CHAINED, seg_len=64)
-    pk = np.frombuffer(c.pk, dtype=np.uint8).copy()
 
     def verify(ctx):
-        bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-        reason = np.full(n, 0xEE, dtype=np.uint8)
-        rc = ctx.lib.dgpu_verify_beacons(ctx.handle, _lib.SCHEME_CHAINED, _lib.ptr(pk), pk.size, n, _lib.ptr(c.rounds),
-                                         _lib.ptr(c.sigs), c.sigs.shape[1], _lib.ptr(c.sig_len), _lib.ptr(c.prev),
-                                         c.prev.shape[1], _lib.ptr(c.prev_len), _lib.MODE_PER_ROUND, 0, _lib.ptr(bits),
-                                         _lib.ptr(reason))
-        return rc, reason
+        try:
+            return _lib.DGPU_OK, calls.verify_beacons(ctx, _lib.SCHEME_CHAINED, c.pk, *c.records(), fill=0xEE)
+        except _lib.DrandGPUError as e:
+            return e.code, None
 
     # 64 KiB: the context's constants fit (dgpu_open succeeds), the engine's buffers for 64 rounds do not
-    ctx = open_ctx({"DGPU_TEST_ALLOC_CAP": "65536"})
-    try:
+    with contextlib.closing(open_ctx({"DGPU_TEST_ALLOC_CAP": "65536"})) as ctx:
         rc, _ = verify(ctx)
         assert rc == _lib.DGPU_ENOMEM and b"test cap 65536" in ctx.lib.dgpu_last_error()
-    finally:
-        ctx.close()
-    ctx = open_ctx({"DGPU_DEC_OVERLAP": "0"})  # another A/B knob: the same build, no cap
-    try:
+    with contextlib.closing(open_ctx({"DGPU_DEC_OVERLAP": "0"})) as ctx:  # another A/B knob: the same build, no cap
         rc, reason = verify(ctx)
         assert rc == _lib.DGPU_OK and ctx.lib.dgpu_last_error() == b""
         assert not reason.any()
-    finally:
-        ctx.close()
 
 
 def test_empty_batches_are_no_ops(gpu_ctx):
@@ -686,7 +610,7 @@ def test_empty_batches_are_no_ops(gpu_ctx):
     an empty tryNode window): DGPU_OK, nothing written, NULL record arrays
     accepted.  G2 and G1 schemes, per-round and RLC, host and device entry
     points, raw-message verify and recovery with zero rounds."""
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     from drand_amd.synth import make_chain
     lib, h = gpu_ctx.lib, gpu_ctx.handle
     bits = np.full(2, 0xAB, dtype=np.uint8)
@@ -695,13 +619,12 @@ def test_empty_batches_are_no_ops(gpu_ctx):
         pk = np.frombuffer(make_chain(72, 2, code, seg_len=2).pk, dtype=np.uint8).copy()
         for mode in (_lib.MODE_PER_ROUND, _lib.MODE_RLC):
             _lib.check(lib.dgpu_verify_beacons(h, code, _lib.ptr(pk), pk.size, 0, None, None, 96, None, None, 96, None,
-                                               mode, 7, _lib.ptr(bits), _lib.ptr(reason)))
+                                               mode, 7, _lib.ptr(bits), _lib.ptr(reason)), lib)
             _lib.check(lib.dgpu_verify_beacons_device(h, code, _lib.ptr(pk), pk.size, 0, None, None, 96, None, None, 96,
-                                                      None, mode, 7, None, None, None))
+                                                      None, mode, 7, None, None, None), lib)
             _lib.check(lib.dgpu_verify_recovered(h, code, _lib.ptr(pk), pk.size, 0, None, 32, None, None, 96, None,
-                                                 mode, 7, _lib.ptr(bits), _lib.ptr(reason)))
+                                                 mode, 7, _lib.ptr(bits), _lib.ptr(reason)), lib)
     g = load_golden("recover_t3_n8.json")
-    commits = np.frombuffer(b"".join(bytes.fromhex(x) for x in g["commits"]), dtype=np.uint8).copy()
-    _lib.check(lib.dgpu_set_group(h, len(g["commits"]), g["n"], _lib.ptr(commits)))
-    _lib.check(lib.dgpu_recover_batch(h, 0, None, 8, None, 96, None, None, _lib.ptr(bits), None))
+    calls.set_group(gpu_ctx, _lib.SCHEME_CHAINED, len(g["commits"]), g["n"], [bytes.fromhex(x) for x in g["commits"]])
+    _lib.check(lib.dgpu_recover_batch(h, 0, None, 8, None, 96, None, None, _lib.ptr(bits), None), lib)
     assert bits.tolist() == [0xAB, 0xAB] and reason.tolist() == [0xCD, 0xCD]

@@ -7,6 +7,7 @@ drand_amd/csrc/check_rows.cuh restated in numpy over synthetic arrays; for
 dgpu_check_rows, that rule applied to dgpu_verify_rows' outputs on the same
 rows and a list written out by hand; for the loop, replay="host" with either
 decoder."""
+import contextlib
 import json
 import os
 
@@ -15,7 +16,7 @@ import pytest
 
 from bolt_writer import write_bolt
 from conftest import load_golden, open_ctx
-from ingest_rows_corpus import marshal
+from ingest_rows_corpus import marshal, pack
 
 pytestmark = pytest.mark.gpu
 BLOCK = 256  # CHECK_BLOCK: positions per block, block counts per pass of the scan (check_rows.cuh)
@@ -151,20 +152,9 @@ def test_device_stage_empty_range_and_bad_arguments(gpu_ctx):
 
 
 # ---------------------------------------------------------------- dgpu_check_rows
-def pack(rows, lead=b""):
-    ln = np.array([len(r) for r in rows], dtype=np.uint32)
-    off = (len(lead) + np.concatenate([[0], np.cumsum(ln, dtype=np.uint64)[:-1]])).astype(np.uint64)
-    return np.frombuffer(lead + b"".join(rows), dtype=np.uint8).copy(), off, ln
-
-
 def verify_rows(ctx, code, pk, buf, off, ln, ss, ps, mode, seed):
-    from drand_amd import _lib
-    n = len(off)
-    bits, reason = np.zeros((n + 7) // 8, dtype=np.uint8), np.full(n, 0xEE, dtype=np.uint8)
-    ok, rounds = np.full(n, 0xEE, dtype=np.uint8), np.full(n, 0xEEEE, dtype=np.uint64)
-    _lib.check(ctx.lib.dgpu_verify_rows(ctx.handle, code, _lib.ptr(pk), pk.size, n, _lib.ptr(buf), _lib.ptr(off),
-                                        _lib.ptr(ln), ss, ps, mode, seed, _lib.ptr(rounds), _lib.ptr(ok), _lib.ptr(bits),
-                                        _lib.ptr(reason)), ctx.lib)
+    from drand_amd import calls
+    reason, ok, rounds = calls.verify_rows(ctx, code, pk, buf, off, ln, ss, ps, mode, seed, fill=0xEE)
     return rounds, ok, reason
 
 
@@ -328,8 +318,7 @@ def test_check_rows_golden_fixtures(name, scheme, strides, mode):
     from drand_amd import _lib
     pk, rows, keys, end = fixture_rows(name, 600)
     buf, off, ln = pack(rows, lead=b"\0" * 3)
-    ctx = open_ctx({"DGPU_RLC_MIN": "0"})
-    try:
+    with contextlib.closing(open_ctx({"DGPU_RLC_MIN": "0"})) as ctx:
         code, m = getattr(_lib, scheme), getattr(_lib, mode)
         rounds, ok, reason = verify_rows(ctx, code, pk, buf, off, ln, *strides, m, 0x1234)
         first, count = 498, end + 3 - 498  # missing rounds in front of the first key and behind the last
@@ -340,8 +329,6 @@ def test_check_rows_golden_fixtures(name, scheme, strides, mode):
         assert np.array_equal(rs, reason) and (reason == 0).any() and len(set(reason.tolist())) >= 3
         assert len(left) > 10 and 20 < len(pos) < count and (val != first + pos).any()
         assert pos[:2].tolist() == [0, 1] and pos[-1] == count - 1
-    finally:
-        ctx.close()
 
 
 def test_check_rows_argument_errors_leave_the_context_working(gpu_ctx):

@@ -53,19 +53,9 @@ def _mutate(c, rng, width):
 
 
 def _gpu_reasons(code, c, mode):
-    from drand_amd import _lib
+    from drand_amd import calls
     from drand_amd.chain import get_context
-    ctx = get_context(0)
-    n = len(c)
-    bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-    reason = np.zeros(n, dtype=np.uint8)
-    pk = np.frombuffer(c.pk, dtype=np.uint8).copy()
-    _lib.check(ctx.lib.dgpu_verify_beacons(ctx.handle, code, _lib.ptr(pk), pk.size, n, _lib.ptr(c.rounds),
-                                           _lib.ptr(c.sigs), c.sigs.shape[1], _lib.ptr(c.sig_len), _lib.ptr(c.prev),
-                                           c.prev.shape[1], _lib.ptr(c.prev_len), mode, 0xFACE, _lib.ptr(bits),
-                                           _lib.ptr(reason)))
-    assert np.array_equal(np.unpackbits(bits, bitorder="little")[:n].astype(bool), reason == 0)
-    return reason
+    return calls.verify_beacons(get_context(0), code, c.pk, *c.records(), mode, 0xFACE, fill=0xEE)
 
 
 @pytest.mark.parametrize("code_name", ["SCHEME_CHAINED", "SCHEME_UNCHAINED_G1"])

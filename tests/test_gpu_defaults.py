@@ -21,16 +21,14 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, open_ctx
+from segment_helpers import DEFAULTS
 
 pytestmark = pytest.mark.gpu
 
-DEFAULTS = {"DGPU_THR_MIN": "65536", "DGPU_RLC_MIN": "131072", "DGPU_COF_ENGINE_MAX": "16384",
-            "DGPU_FE_GS_MAX": "16384"}
 
 
 @contextlib.contextmanager
 def _default_ctx(extra=None):
-    from drand_amd import _lib
     ctx = open_ctx(dict(DEFAULTS, **(extra or {})))
     try:
         yield ctx
@@ -39,17 +37,8 @@ def _default_ctx(extra=None):
 
 
 def _verify(ctx, code, c, mode, seed=777):
-    from drand_amd import _lib
-    n = len(c)
-    bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-    reason = np.zeros(n, dtype=np.uint8)
-    pk = np.frombuffer(c.pk, dtype=np.uint8).copy()
-    _lib.check(ctx.lib.dgpu_verify_beacons(ctx.handle, code, _lib.ptr(pk), pk.size, n, _lib.ptr(c.rounds),
-                                           _lib.ptr(c.sigs), c.sigs.shape[1], _lib.ptr(c.sig_len), _lib.ptr(c.prev),
-                                           c.prev.shape[1], _lib.ptr(c.prev_len), mode, seed, _lib.ptr(bits),
-                                           _lib.ptr(reason)))
-    assert np.array_equal(np.unpackbits(bits, bitorder="little")[:n].astype(bool), reason == 0)
-    return reason
+    from drand_amd import calls
+    return calls.verify_beacons(ctx, code, c.pk, *c.records(), mode, seed, fill=0xEE)
 
 
 @pytest.mark.parametrize("code_name", ["SCHEME_UNCHAINED_G1", "SCHEME_G1_RFC9380"])
@@ -96,22 +85,12 @@ def test_recover_at_defaults(name):
     VerifyPartial / VerifyRecovered pairings are small batches, so they run on
     the lane kernels): recovered signatures and per-partial statuses equal the
     golden fixtures."""
-    from drand_amd import _lib
-    from drand_amd.threshold import pack_partials, unpack_recovered
+    from drand_amd.threshold import ThresholdGroup
     g = load_golden(name)
-    commits = np.frombuffer(b"".join(bytes.fromhex(x) for x in g["commits"]), dtype=np.uint8).copy()
     msgs = [bytes.fromhex(c["msg"]) for c in g["cases"]]
     partials = [[bytes.fromhex(p) for p in c["partials"]] for c in g["cases"]]
-    mb, buf, plen, m, stride = pack_partials(msgs, partials)
-    nr = len(msgs)
-    out = np.zeros(nr * 96, dtype=np.uint8)
-    ok = np.zeros((nr + 7) // 8, dtype=np.uint8)
-    pv = np.zeros(nr * m, dtype=np.uint8)
     with _default_ctx() as ctx:
-        _lib.check(ctx.lib.dgpu_set_group(ctx.handle, len(g["commits"]), g["n"], _lib.ptr(commits)))
-        _lib.check(ctx.lib.dgpu_recover_batch(ctx.handle, nr, _lib.ptr(mb), m, _lib.ptr(buf), stride, _lib.ptr(plen),
-                                              _lib.ptr(out), _lib.ptr(ok), _lib.ptr(pv)))
-    sigs, valid = unpack_recovered(out, ok, pv, partials, m)
+        sigs, valid = ThresholdGroup([bytes.fromhex(x) for x in g["commits"]], g["n"], ctx=ctx).recover_batch(msgs, partials)
     for c, s, v in zip(g["cases"], sigs, valid):
         assert v == c["valid"], c["kind"]
         assert (s.hex() if s else None) == c["recovered"], c["kind"]
@@ -123,23 +102,15 @@ def test_recover_batched_check_table_layouts(rows):
     window tables gathered from SoA planes or from 224-byte rows
     (DGPU_RECOVER_ROWS): recovered signatures equal the t=17-of-32 and
     t=12-of-20 fixtures case by case."""
-    from drand_amd import _lib
-    from drand_amd.threshold import pack_partials, unpack_recovered
+    from drand_amd.threshold import ThresholdGroup
     for name in ("recover_t17_n32.json", "recover_t12_n20.json"):
         g = load_golden(name)
-        commits = np.frombuffer(b"".join(bytes.fromhex(x) for x in g["commits"]), dtype=np.uint8).copy()
         msgs = [bytes.fromhex(c["msg"]) for c in g["cases"]]
         partials = [[bytes.fromhex(p) for p in c["partials"]] for c in g["cases"]]
-        mb, buf, plen, m, stride = pack_partials(msgs, partials)
-        nr = len(msgs)
-        out = np.zeros(nr * 96, dtype=np.uint8)
-        ok = np.zeros((nr + 7) // 8, dtype=np.uint8)
         # the SoA layout is an A/B variant: only the A/B build reads the knob
         with _default_ctx({"DGPU_RECOVER_ROWS": rows} if rows == "0" else None) as ctx:
-            _lib.check(ctx.lib.dgpu_set_group(ctx.handle, len(g["commits"]), g["n"], _lib.ptr(commits)))
-            _lib.check(ctx.lib.dgpu_recover_batch(ctx.handle, nr, _lib.ptr(mb), m, _lib.ptr(buf), stride,
-                                                  _lib.ptr(plen), _lib.ptr(out), _lib.ptr(ok), None))
-        sigs, _ = unpack_recovered(out, ok, None, partials, m)
+            grp = ThresholdGroup([bytes.fromhex(x) for x in g["commits"]], g["n"], ctx=ctx)
+            sigs, _ = grp.recover_batch(msgs, partials, statuses=False)
         assert [s.hex() if s else None for s in sigs] == [c["recovered"] for c in g["cases"]], name
 
 

@@ -13,7 +13,8 @@ golden chained chain's first 9 rounds:
   verdicts equal the single call's.
 
 Marked gpu."""
-import ctypes
+
+import contextlib
 
 import numpy as np
 import pytest
@@ -79,17 +80,16 @@ def test_empty_rlc_shard_over_the_handle(which, records, monkeypatch):
 @pytest.mark.parametrize("which", ["clean", "bad"])
 def test_empty_shard_in_the_rank_protocol(which, records, gpu_ctx):
     import torch
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     from drand_amd.dist import rank_seed
     pk, _, recs, single = records
     rounds, sigs, sig_len, prev, prev_len = recs[which]
     pkb = np.frombuffer(pk, dtype=np.uint8).copy()
     code = _lib.SCHEME_CHAINED
     dev = torch.device("cuda", 0)
-    other = open_ctx({})
-    try:
+    with contextlib.closing(open_ctx({})) as other:
         ranks = [(gpu_ctx, N), (other, 0)]  # rank 0 holds every round, rank 1 none
-        rb = gpu_ctx.lib.dgpu_rlc_root_bytes(code)
+        rb = calls.rlc_root_bytes(gpu_ctx, code)
         assert rb > 0
         held, roots = [], []
         for r, (ctx, n) in enumerate(ranks):
@@ -97,10 +97,7 @@ def test_empty_shard_in_the_rank_protocol(which, records, gpu_ctx):
                  for a in (rounds.view(np.int64), sigs, sig_len.view(np.int32), prev, prev_len.view(np.int32))]
             root = torch.full((rb,), 0xA5, dtype=torch.uint8, device=dev)
             # the NULL stream is the legacy default stream, torch's: the concatenation below is ordered behind it
-            _lib.check(ctx.lib.dgpu_rlc_root_device(ctx.handle, code, _lib.ptr(pkb), pkb.size, n, t[0].data_ptr(),
-                                                    t[1].data_ptr(), sigs.shape[1], t[2].data_ptr(), t[3].data_ptr(),
-                                                    prev.shape[1], t[4].data_ptr(), rank_seed(1000, r, 2),
-                                                    root.data_ptr(), None))
+            calls.rlc_root_device(ctx, code, pkb, *t, rank_seed(1000, r, 2), root)
             held.append(t)
             roots.append(root)
         all_roots = torch.cat(roots)
@@ -109,8 +106,7 @@ def test_empty_shard_in_the_rank_protocol(which, records, gpu_ctx):
         # the empty rank: nothing to write, NULL outputs
         rc = other.lib.dgpu_rlc_finish_device(other.handle, 2, all_roots.data_ptr(), None, None, None)
         assert rc == _lib.DGPU_OK, other.lib.dgpu_last_error()
-        _lib.check(gpu_ctx.lib.dgpu_rlc_finish_device(gpu_ctx.handle, 2, all_roots.data_ptr(), d_bits.data_ptr(),
-                                                      d_reason.data_ptr(), None))
+        calls.rlc_finish_device(gpu_ctx, 2, all_roots, d_bits, d_reason)
         reasons = d_reason.cpu().numpy()
         bits = np.unpackbits(d_bits.cpu().numpy(), bitorder="little")[:N].astype(bool)
         assert reasons.tolist() == single[which, _lib.MODE_PER_ROUND].tolist()
@@ -118,5 +114,3 @@ def test_empty_shard_in_the_rank_protocol(which, records, gpu_ctx):
         # the empty rank's root is the identity pair (Z = 0 in both points): not the fill pattern, and
         # summing it changed nothing -- a clean node passed, a bad one failed on rank 0's round alone
         assert not bool((roots[1] == 0xA5).all())
-    finally:
-        other.close()

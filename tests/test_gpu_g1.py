@@ -45,7 +45,7 @@ def test_g1_chain_fixture_verdicts(name):
 @pytest.mark.parametrize("code_name", ["SCHEME_UNCHAINED_G1", "SCHEME_G1_RFC9380"])
 def test_g1_synthetic_chain_with_corruptions(code_name):
     import numpy as np
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     from drand_amd.chain import get_context
     from drand_amd.synth import corrupt, make_chain
     from oracle import bls12381 as B
@@ -59,11 +59,11 @@ def test_g1_synthetic_chain_with_corruptions(code_name):
     bad = corrupt(ch, 9, rate=0.01)
     ctx = get_context(0)
     n = len(ch)
-    _lib.check(ctx.lib.dgpu_set_pubkey(ctx.handle, code, ch.pk, 96))
+    calls.set_pubkey(ctx, code, ch.pk)
     bits = np.zeros((n + 7) // 8, dtype=np.uint8)
     _lib.check(ctx.lib.dgpu_verify_batch(ctx.handle, code, n, _lib.ptr(ch.rounds), _lib.ptr(ch.sigs), 96,
                                          _lib.ptr(ch.sig_len), None, 0, None, _lib.MODE_PER_ROUND, 0,
-                                         _lib.ptr(bits), None))
+                                         _lib.ptr(bits), None), ctx.lib)
     valid = np.unpackbits(bits, bitorder="little")[:n].astype(bool)
     expect = np.ones(n, dtype=bool)
     expect[list(bad)] = False
@@ -86,7 +86,7 @@ def test_g1_rlc_equals_per_round_fixture(name):
     root, the key's fixed-Q lines for every node check, leaves + tree only
     when the root fails) gives the per-round reasons on the fixture and its
     corruption catalog, and a clean batch passes on the root alone."""
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     from drand_amd.chain import Beacon, new_verifier
     g = load_golden(name)
     v = new_verifier(_scheme(g))
@@ -96,13 +96,9 @@ def test_g1_rlc_equals_per_round_fixture(name):
     expect = [0] * len(g["rounds"]) + [c["reason"] for c in g["corrupted"]]
     for seed in (1, 2, 0xFFFFFFFFFFFFFFFF):
         assert v.verify_reasons(beacons, pk, _lib.MODE_RLC, rlc_seed=seed).tolist() == expect
-    lib = v.ctx.lib
-    _lib.check(lib.dgpu_set_profiling(v.ctx.handle, 1))
-    try:
+    with calls.profiled(v.ctx) as stage_times:
         assert not v.verify_reasons(clean, pk, _lib.MODE_RLC).any()
-        stages = set(_lib.stage_times(v.ctx))
-    finally:
-        _lib.check(lib.dgpu_set_profiling(v.ctx.handle, 0))
+        stages = set(stage_times())
     assert {"rlc_hash_to_g1_raw", "decode_g1", "rlc_root_msm"} <= stages and "rlc_leaves_tree" not in stages, stages
     # one round alone: its leaf is the root
     assert v.verify_reasons(beacons[-1:], pk, _lib.MODE_RLC).tolist() == expect[-1:]
@@ -118,7 +114,7 @@ def test_g1_rlc_large_chain_every_corruption_kind(code_name):
     them whenever the coefficient is 0 mod 3): RLC reasons == per-round
     reasons == construction."""
     import numpy as np
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     from drand_amd.chain import get_context
     from drand_amd.synth import corrupt, make_chain
     from oracle import bls12381 as B
@@ -133,14 +129,14 @@ def test_g1_rlc_large_chain_every_corruption_kind(code_name):
         s = B.g1_decompress(bytes(ch.sigs[i, :48]))
         ch.sigs[i, :48] = np.frombuffer(B.g1_compress(B.g1_add(s, T3)), dtype=np.uint8)
     ctx = get_context(0)
-    _lib.check(ctx.lib.dgpu_set_pubkey(ctx.handle, code, ch.pk, 96))
+    calls.set_pubkey(ctx, code, ch.pk)
 
     def run(mode, seed=0):
         bits = np.zeros((n + 7) // 8, dtype=np.uint8)
         reason = np.zeros(n, dtype=np.uint8)
         _lib.check(ctx.lib.dgpu_verify_batch(ctx.handle, code, n, _lib.ptr(ch.rounds), _lib.ptr(ch.sigs), 96,
                                              _lib.ptr(ch.sig_len), None, 0, None, mode, seed, _lib.ptr(bits),
-                                             _lib.ptr(reason)))
+                                             _lib.ptr(reason)), ctx.lib)
         return reason
 
     per = run(_lib.MODE_PER_ROUND)

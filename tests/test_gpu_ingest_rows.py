@@ -6,6 +6,7 @@ ingest.decode's beacon_unmarshal pass): the device decoder's records equal its
 records byte for byte, dgpu_verify_rows equals dgpu_verify_beacons on the
 arrays it writes, and the check-chain loop over a bolt file returns the same
 faulty rounds and makes the same callbacks whichever side decodes."""
+import contextlib
 import json
 import os
 import struct
@@ -15,7 +16,7 @@ import pytest
 
 from bolt_writer import write_bolt
 from conftest import load_golden, open_ctx
-from ingest_rows_corpus import corpus, marshal
+from ingest_rows_corpus import corpus, marshal, pack
 
 pytestmark = pytest.mark.gpu
 SLOT = 16 << 20  # the pinned ring's slot (include/drand_gpu.h, dgpu_verify_rows)
@@ -37,13 +38,6 @@ def native_decode(buf, off, ln, sig_stride, prev_stride):
                              sig_stride, sig_len.ctypes.data, prev.ctypes.data, prev_stride, prev_len.ctypes.data,
                              ok.ctypes.data)
     return rounds, sigs, sig_len, prev, prev_len, ok
-
-
-def pack(rows, lead=b""):
-    """Rows back to back behind `lead`: (buffer, offsets, lengths)."""
-    ln = np.array([len(r) for r in rows], dtype=np.uint32)
-    off = (len(lead) + np.concatenate([[0], np.cumsum(ln, dtype=np.uint64)[:-1]])).astype(np.uint64)
-    return np.frombuffer(lead + b"".join(rows), dtype=np.uint8).copy(), off, ln
 
 
 @pytest.fixture(scope="module")
@@ -72,7 +66,7 @@ def device_decode(gpu_ctx, buf, off, ln, sig_stride, prev_stride, shift=0):
     """dgpu_decode_rows_device on a device copy of buf that starts `shift`
     bytes into its allocation; the record arrays carry 64 guard bytes."""
     import torch
-    from drand_amd import _lib
+    from drand_amd import calls
     n = len(off)
     G = 64
     whole = torch.zeros(buf.size + shift, dtype=torch.uint8, device="cuda")
@@ -82,10 +76,8 @@ def device_decode(gpu_ctx, buf, off, ln, sig_stride, prev_stride, shift=0):
     out = {k: torch.full((size + G,), 0xA5, dtype=torch.uint8, device="cuda")
            for k, size in (("rounds", 8 * n), ("sigs", n * sig_stride), ("sig_len", 4 * n), ("prev", n * prev_stride),
                            ("prev_len", 4 * n), ("ok", n))}
-    _lib.check(gpu_ctx.lib.dgpu_decode_rows_device(
-        gpu_ctx.handle, n, _lib.ptr(d_rows), buf.size, _lib.ptr(d_off), _lib.ptr(d_len), _lib.ptr(out["rounds"]),
-        _lib.ptr(out["sigs"]), sig_stride, _lib.ptr(out["sig_len"]), _lib.ptr(out["prev"]), prev_stride,
-        _lib.ptr(out["prev_len"]), _lib.ptr(out["ok"]), None), gpu_ctx.lib)
+    calls.decode_rows_device(gpu_ctx, d_rows, d_off, d_len, out["rounds"], out["sigs"], out["sig_len"], out["prev"],
+                             out["prev_len"], out["ok"], sig_stride=sig_stride, prev_stride=prev_stride)
     torch.cuda.synchronize()
     host = {k: v.cpu().numpy() for k, v in out.items()}
     for k, v in host.items():
@@ -164,31 +156,16 @@ def test_device_decoder_empty_call(gpu_ctx):
 
 # ---------------------------------------------------------------- dgpu_verify_rows
 def verify_rows(ctx, code, pk, buf, off, ln, sig_stride, prev_stride, mode, seed):
-    from drand_amd import _lib
-    n = len(off)
-    bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-    reason = np.full(n, 0xEE, dtype=np.uint8)
-    ok = np.full(n, 0xEE, dtype=np.uint8)
-    rounds = np.full(n, 0xEEEE, dtype=np.uint64)
-    _lib.check(ctx.lib.dgpu_verify_rows(ctx.handle, code, _lib.ptr(pk), pk.size, n, _lib.ptr(buf), _lib.ptr(off),
-                                        _lib.ptr(ln), sig_stride, prev_stride, mode, seed, _lib.ptr(rounds),
-                                        _lib.ptr(ok), _lib.ptr(bits), _lib.ptr(reason)), ctx.lib)
-    return rounds, ok, bits, reason
+    """(rounds, row_ok, reasons) of dgpu_verify_rows, every output sentinel-filled before the call."""
+    from drand_amd import calls
+    reason, ok, rounds = calls.verify_rows(ctx, code, pk, buf, off, ln, sig_stride, prev_stride, mode, seed, fill=0xEE)
+    return rounds, ok, reason
 
 
 def verify_records(ctx, code, pk, rec, mode, seed):
     """dgpu_verify_beacons on native_decode's arrays."""
-    from drand_amd import _lib
-    rounds, sigs, sig_len, prev, prev_len, _ = rec
-    n = len(rounds)
-    bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-    reason = np.full(n, 0xEE, dtype=np.uint8)
-    if prev.shape[1] == 0:
-        prev = np.zeros((n, 1), dtype=np.uint8)
-    _lib.check(ctx.lib.dgpu_verify_beacons(ctx.handle, code, _lib.ptr(pk), pk.size, n, _lib.ptr(rounds), _lib.ptr(sigs),
-                                           sigs.shape[1], _lib.ptr(sig_len), _lib.ptr(prev), rec[3].shape[1],
-                                           _lib.ptr(prev_len), mode, seed, _lib.ptr(bits), _lib.ptr(reason)), ctx.lib)
-    return bits, reason
+    from drand_amd import calls
+    return calls.verify_beacons(ctx, code, pk, *rec[:5], mode, seed, fill=0xEE)
 
 
 def fixture_rows(name, total):
@@ -227,10 +204,10 @@ def check_rows_against_records(ctx, code, pk, rows, expect, sig_stride, prev_str
     from drand_amd import _lib
     buf, off, ln = pack(rows, lead=b"\0" * 7)
     rec = native_decode(buf, off, ln, sig_stride, prev_stride)
-    w_bits, w_reason = verify_records(ctx, code, pk, rec, mode, seed)
-    rounds, ok, bits, reason = verify_rows(ctx, code, pk, buf, off, ln, sig_stride, prev_stride, mode, seed)
+    w_reason = verify_records(ctx, code, pk, rec, mode, seed)
+    rounds, ok, reason = verify_rows(ctx, code, pk, buf, off, ln, sig_stride, prev_stride, mode, seed)
     assert np.array_equal(ok, rec[5]) and np.array_equal(rounds, rec[0])
-    assert np.array_equal(reason, w_reason) and np.array_equal(bits, w_bits)
+    assert np.array_equal(reason, w_reason)  # (the bitmaps too: each call checks its own against its reasons)
     # and the verdicts are the fixture's: a row that is not canonical is a decode failure
     want = [_lib.REASON_DECODE if e is None else e for e in expect]
     canon = [e is not None for e in expect]
@@ -248,12 +225,9 @@ def test_verify_rows_equals_verify_beacons_chained(mode):
     (DGPU_RLC_MIN lowered on a context of its own)."""
     from drand_amd import _lib
     pk, rows, expect = fixture_rows("chain_chained_s1.json", 1000)
-    ctx = open_ctx({"DGPU_RLC_MIN": "0"})
-    try:
+    with contextlib.closing(open_ctx({"DGPU_RLC_MIN": "0"})) as ctx:
         reason = check_rows_against_records(ctx, _lib.SCHEME_CHAINED, pk, rows, expect, 96, 96, getattr(_lib, mode))
         assert (reason == 0).sum() > 500 and len(set(reason.tolist())) == 5
-    finally:
-        ctx.close()
 
 
 @pytest.mark.parametrize("name,scheme,strides", [("chain_unchained_s1.json", "SCHEME_UNCHAINED", (96, 48)),
@@ -326,13 +300,12 @@ def test_verify_rows_across_ring_pieces(gpu_ctx):
     rows[long_row] = rows[long_row][:-2] + b"0" * 2000 + b'"}'
     c.sigs[long_row], c.sig_len[long_row], c.prev[long_row], c.prev_len[long_row], c.rounds[long_row] = 0, 0, 0, 0, 0
     buf, off, ln = pack(rows, lead=b"\0" * 5)
-    rounds, ok, bits, reason = verify_rows(gpu_ctx, _lib.SCHEME_CHAINED, pk, buf, off, ln, 96, 96, _lib.MODE_PER_ROUND, 0)
+    rounds, ok, reason = verify_rows(gpu_ctx, _lib.SCHEME_CHAINED, pk, buf, off, ln, 96, 96, _lib.MODE_PER_ROUND, 0)
     ms, host_ms, nbytes = _lib.staging_stats(gpu_ctx)
     _, staged = piece_cuts(ln, 64 + 2 * (96 + 96))
     assert nbytes == staged + 12 * n and staged == int(ln.sum()) - int(ln[long_row]) and ms > 0 and host_ms > 0
-    w_bits, w_reason = verify_records(gpu_ctx, _lib.SCHEME_CHAINED, pk,
-                                      (c.rounds, c.sigs, c.sig_len, c.prev, c.prev_len, None), _lib.MODE_PER_ROUND, 0)
-    assert np.array_equal(reason, w_reason) and np.array_equal(bits, w_bits)
+    w_reason = verify_records(gpu_ctx, _lib.SCHEME_CHAINED, pk, c.records(), _lib.MODE_PER_ROUND, 0)
+    assert np.array_equal(reason, w_reason)
     assert np.array_equal(rounds, c.rounds)
     expect_ok = np.ones(n, dtype=np.uint8)
     expect_ok[long_row] = 0

@@ -11,6 +11,7 @@ The suite runs with DGPU_RLC_MIN=0 (conftest.py), so every DGPU_MODE_RLC call
 below takes the per-key combination (keyed.cuh) whatever its size; its
 verdicts and reasons must equal per-record mode's.
 """
+import contextlib
 import sys
 
 import numpy as np
@@ -19,7 +20,7 @@ import pytest
 from conftest import ROOT, load_golden, open_ctx
 
 sys.path.insert(0, ROOT)
-from drand_amd import _lib, chain, identity, synth  # noqa: E402
+from drand_amd import _lib, calls, chain, identity, synth  # noqa: E402
 from drand_amd.scheme import get_scheme_by_id_with_default, list_schemes, scheme_code  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -40,13 +41,6 @@ def _scheme(name):
 
 def _is_g1(name):
     return _scheme(name).sigs_on_g1
-
-
-def _pubkey(ctx, code, sk):
-    pk = np.zeros(96 if code in (_lib.SCHEME_UNCHAINED_G1, _lib.SCHEME_G1_RFC9380) else 48, dtype=np.uint8)
-    skb = np.frombuffer(sk.to_bytes(32, "big"), dtype=np.uint8).copy()
-    _lib.check(ctx.lib.dgpu_derive_pubkey(ctx.handle, code, _lib.ptr(skb), _lib.ptr(pk), pk.size))
-    return bytes(pk)
 
 
 def _msg(i, length):
@@ -70,7 +64,7 @@ class Batch:
         self.idx = list(idx)
         # a large table derives the keys in use only; an entry no record names repeats the first of them
         used = sorted(set(self.idx)) if n_keys > 64 else list(range(n_keys))
-        derived = {j: _pubkey(ctx, self.code, self.sks[j]) for j in used}
+        derived = {j: calls.derive_pubkey(ctx, self.code, self.sks[j]) for j in used}
         self.keys = [derived.get(j, derived[used[0]]) for j in range(n_keys)]
         self.msgs = [_msg(i + 31 * seed, MSG_LENS[i % len(MSG_LENS)]) for i in range(len(self.idx))]
         self.sigs = [None] * len(self.idx)
@@ -201,7 +195,7 @@ def test_every_scheme_id(name):
         b.check_expect(b.run(mode))
 
 
-def _device_call(ctx, b, idx, n_keys=None, mode=_lib.MODE_PER_ROUND):
+def _device_call(ctx, b, idx, mode=_lib.MODE_PER_ROUND):
     """The device form over torch buffers on a non-default stream; nothing
     synchronises between the call and the read-back but the stream itself."""
     import torch
@@ -211,22 +205,16 @@ def _device_call(ctx, b, idx, n_keys=None, mode=_lib.MODE_PER_ROUND):
     dev = torch.device("cuda:0")
     stream = torch.cuda.Stream(device=dev)
     with torch.cuda.stream(stream):
-        t = [torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to(dev, non_blocking=True)
+        t = [torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(dev, non_blocking=True)
              for a in (kidx, mb, ml, sb, sl)]
         bits = torch.zeros((n + 7) // 8, dtype=torch.uint8, device=dev)
         reason = torch.full((n,), 255, dtype=torch.uint8, device=dev)
-        rc = ctx.lib.dgpu_verify_keyed_device(ctx.handle, b.code, len(b.keys) if n_keys is None else n_keys,
-                                              _lib.ptr(kb), key_len, n, t[0].data_ptr(), t[1].data_ptr(), mb.shape[1],
-                                              t[2].data_ptr(), t[3].data_ptr(), sb.shape[1], t[4].data_ptr(), mode, 5,
-                                              bits.data_ptr(), reason.data_ptr(), stream.cuda_stream)
-        _lib.check(rc, ctx.lib)
+        calls.verify_keyed_device(ctx, b.code, kb, key_len, *t, mode, 5, bits, reason, stream)
         kb[:] = 0  # the table was copied before the call returned
         h_reason = reason.cpu()
         h_bits = bits.cpu()
     stream.synchronize()
-    valid = np.unpackbits(h_bits.numpy(), bitorder="little")[:n].astype(bool)
-    assert np.array_equal(valid, h_reason.numpy() == 0)
-    return h_reason.numpy().tolist()
+    return calls.check_bitmap(h_bits.numpy(), h_reason.numpy()).tolist()
 
 
 @pytest.mark.parametrize("name", BOTH)
@@ -358,12 +346,8 @@ def short_ranges():
 
 
 def _profiled(ctx, fn):
-    _lib.check(ctx.lib.dgpu_set_profiling(ctx.handle, 1))
-    try:
-        out = fn()
-        return out, _lib.stage_times(ctx)  # raises above DGPU_MAX_STAGES
-    finally:
-        _lib.check(ctx.lib.dgpu_set_profiling(ctx.handle, 0))
+    with calls.profiled(ctx) as stage_times:
+        return fn(), stage_times()  # raises above DGPU_MAX_STAGES
 
 
 @pytest.mark.parametrize("name", BOTH)
@@ -413,11 +397,8 @@ def test_rlc_below_the_threshold_runs_per_record(mixed, name):
     """Under the library's default DGPU_RLC_MIN a small DGPU_MODE_RLC batch
     takes the per-record path."""
     b = mixed[name]
-    ctx = open_ctx({"DGPU_RLC_MIN": "131072"})
-    try:
+    with contextlib.closing(open_ctx({"DGPU_RLC_MIN": "131072"})) as ctx:
         got, st = _profiled(ctx, lambda: b.run(_lib.MODE_RLC, ctx=ctx))
-    finally:
-        ctx.close()
     b.check_expect(got)
     assert "keyed_leaves" not in st and "keyed_gather" in st
 
@@ -447,12 +428,9 @@ def test_errors_that_cancel_in_a_plain_sum_are_caught(name):
 def test_staged_bytes_and_stage_count(mixed, gpu_ctx, name):
     b = mixed[name]
     _, _, _, mb, _, sb, _ = chain.pack_keyed(b.code, b.keys, b.idx, b.msgs, b.sigs)
-    _lib.check(gpu_ctx.lib.dgpu_set_profiling(gpu_ctx.handle, 1))
-    try:
+    with calls.profiled(gpu_ctx) as stage_times:
         for mode in MODES:
             b.run(mode)
             assert _lib.staging_stats(gpu_ctx)[2] == 300 * (mb.shape[1] + sb.shape[1] + 12)
-            stages = _lib.stage_times(gpu_ctx)  # raises above DGPU_MAX_STAGES
+            stages = stage_times()  # raises above DGPU_MAX_STAGES
             assert {"keyed_keys", "keyed_gather", "eng_miller", "pack_verdicts"} <= set(stages)
-    finally:
-        _lib.check(gpu_ctx.lib.dgpu_set_profiling(gpu_ctx.handle, 0))

@@ -112,6 +112,5 @@ def test_recover_multi_same_device_equals_single(ndev, monkeypatch):
         got = mg.recover_batch(msgs, parts)
     finally:
         mg.close()
-    ThresholdGroup._active = None
     assert got == single
     assert [s.hex() if s else None for s in got[0]] == [c["recovered"] for c in g["cases"]] * 5

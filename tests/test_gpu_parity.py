@@ -1,6 +1,7 @@
 """GPU parity: the HIP path through the C-ABI against the oracle and the
 committed golden fixtures (bit-exact), plus size-independent properties at
 larger sizes.  Marked gpu."""
+import contextlib
 import hashlib
 
 import numpy as np
@@ -48,11 +49,8 @@ def test_kat_on_device(gpu_ctx):
     sch = get_scheme_by_id_with_default("")
     assert sign(sk, [msg], sch) == [sig]
     assert verify_recovered(sch, pk, [msg, msg + b"!", b""], [sig, sig, sig]).tolist() == [0, 3, 3]
-    from drand_amd import _lib
-    out = np.zeros(48, dtype=np.uint8)
-    skb = np.frombuffer(sk, dtype=np.uint8).copy()
-    _lib.check(gpu_ctx.lib.dgpu_derive_pubkey(gpu_ctx.handle, _lib.SCHEME_CHAINED, _lib.ptr(skb), _lib.ptr(out), 48))
-    assert bytes(out) == pk
+    from drand_amd import _lib, calls
+    assert calls.derive_pubkey(gpu_ctx, _lib.SCHEME_CHAINED, sk) == pk
     h = B.g2_decompress(hash_to_curve([msg], sch)[0])
     inv = pow(int.from_bytes(sk, "big"), -1, R_ORDER)
     assert B.g2_compress(B.g2_mul(B.g2_decompress(sig), inv)) == B.g2_compress(h)
@@ -240,24 +238,11 @@ def test_rlc_small_batches_take_per_round_path():
 def _verify_with_env(c, env, mode=None):
     """Verify chain c on a fresh context opened under the environment `env`
     (the library reads its A/B and test knobs at dgpu_open); returns reasons."""
-    import os
-    from drand_amd import _lib
-    n = len(c.rounds)
-    ctx = open_ctx(env)
-    try:
-        lib = ctx.lib
-        _lib.check(lib.dgpu_set_pubkey(ctx.handle, _lib.SCHEME_CHAINED, c.pk, len(c.pk)))
-        bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-        reason = np.zeros(n, dtype=np.uint8)
-        _lib.check(lib.dgpu_verify_batch(ctx.handle, _lib.SCHEME_CHAINED, n, _lib.ptr(c.rounds),
-                                         _lib.ptr(c.sigs), c.sigs.shape[1], _lib.ptr(c.sig_len),
-                                         _lib.ptr(c.prev), c.prev.shape[1], _lib.ptr(c.prev_len),
-                                         _lib.MODE_PER_ROUND if mode is None else mode, 0, _lib.ptr(bits),
-                                         _lib.ptr(reason)))
-        assert np.array_equal(np.unpackbits(bits, bitorder="little")[:n].astype(bool), reason == 0)
-        return reason
-    finally:
-        ctx.close()
+    from drand_amd import _lib, calls
+    with contextlib.closing(open_ctx(env)) as ctx:
+        calls.set_pubkey(ctx, _lib.SCHEME_CHAINED, c.pk)
+        return calls.verify_batch(ctx, _lib.SCHEME_CHAINED, *c.records(), _lib.MODE_PER_ROUND if mode is None else mode,
+                                  0, fill=0xEE)
 
 
 def test_karabina_fe_equals_granger_scott_and_fallback():
@@ -440,7 +425,7 @@ def test_key_cache_eviction_reuses_slots_across_key_kinds():
     ten verify; then key 0 again (evicted: decoded into a reused slot) and key
     9 (still cached).  Reasons equal the construction every time: a stale or
     mixed-up key would fail every round with REASON_PAIRING."""
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     from drand_amd.synth import make_chain
     chains = []
     for k in range(10):
@@ -449,24 +434,11 @@ def test_key_cache_eviction_reuses_slots_across_key_kinds():
         c.sigs[k % 7, 0] ^= 0x20  # -sigma: a valid point, the pairing fails
         chains.append(c)
     assert len({c.pk for c in chains}) == 10
-    ctx = open_ctx({})
-    try:
+    with contextlib.closing(open_ctx({})) as ctx:
         def reasons(c):
-            n = len(c)
-            pk = np.frombuffer(c.pk, dtype=np.uint8).copy()
-            bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-            reason = np.full(n, 0xFF, dtype=np.uint8)
-            _lib.check(ctx.lib.dgpu_verify_beacons(ctx.handle, c.scheme_code, _lib.ptr(pk), pk.size, n,
-                                                   _lib.ptr(c.rounds), _lib.ptr(c.sigs), c.sigs.shape[1],
-                                                   _lib.ptr(c.sig_len), _lib.ptr(c.prev), c.prev.shape[1],
-                                                   _lib.ptr(c.prev_len), _lib.MODE_PER_ROUND, 0, _lib.ptr(bits),
-                                                   _lib.ptr(reason)), ctx.lib)
-            assert np.array_equal(np.unpackbits(bits, bitorder="little")[:n].astype(bool), reason == 0)
-            return reason.tolist()
+            return calls.verify_beacons(ctx, c.scheme_code, c.pk, *c.records(), fill=0xFF).tolist()
 
         for k in list(range(10)) + [0, 9]:
             expect = [_lib.REASON_OK] * 7
             expect[k % 7] = _lib.REASON_PAIRING
             assert reasons(chains[k]) == expect, k
-    finally:
-        ctx.close()

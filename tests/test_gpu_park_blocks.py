@@ -20,10 +20,10 @@ At n = 65 the A/B build's forced-exceptional hook (DGPU_TEST_FORCE_EXC=1)
 flags every round, so k_h2c_finish_redo recomputes each with the generic
 form from P, read back from slot 0 of the region through get(0): the
 verdicts must be the same.  Marked gpu."""
+import contextlib
 import functools
 import os
 
-import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -52,17 +52,8 @@ def _case(n):
 
 
 def _reasons(ctx, c):
-    from drand_amd import _lib
-    n = len(c)
-    bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-    reason = np.full(n, 0xEE, dtype=np.uint8)
-    pk = np.frombuffer(c.pk, dtype=np.uint8).copy()
-    _lib.check(ctx.lib.dgpu_verify_beacons(ctx.handle, _lib.SCHEME_CHAINED, _lib.ptr(pk), pk.size, n, _lib.ptr(c.rounds),
-                                           _lib.ptr(c.sigs), c.sigs.shape[1], _lib.ptr(c.sig_len), _lib.ptr(c.prev),
-                                           c.prev.shape[1], _lib.ptr(c.prev_len), _lib.MODE_PER_ROUND, 0, _lib.ptr(bits),
-                                           _lib.ptr(reason)), ctx.lib)
-    assert np.array_equal(np.unpackbits(bits, bitorder="little")[:n].astype(bool), reason == 0)
-    return reason
+    from drand_amd import _lib, calls
+    return calls.verify_beacons(ctx, _lib.SCHEME_CHAINED, c.pk, *c.records(), fill=0xEE)
 
 
 def _check_both_ways(ctx, n):
@@ -96,8 +87,5 @@ def test_park_block_edges_equal_c_restatement(gpu_ctx, n):
 def test_generic_redo_reads_slot_0_of_the_park_region():
     from conftest import open_ctx
     n = 65
-    ctx = open_ctx({"DGPU_TEST_FORCE_EXC": "1"})
-    try:
+    with contextlib.closing(open_ctx({"DGPU_TEST_FORCE_EXC": "1"})) as ctx:
         _check_both_ways(ctx, n)
-    finally:
-        ctx.close()

@@ -4,11 +4,13 @@ installed group, without a recovery (chain/beacon/node.go:117-125).
 The suite runs with DGPU_RLC_MIN=0 (conftest.py), so every DGPU_MODE_RLC call
 below takes the per-key combination with the share index as the key
 (keyed.cuh); test_constructed_batch asserts its stages are recorded."""
+import contextlib
+
 import numpy as np
 import pytest
 
 from conftest import load_golden
-from drand_amd import _lib, synth
+from drand_amd import _lib, calls, synth
 from drand_amd.threshold import ThresholdGroup
 
 pytestmark = pytest.mark.gpu
@@ -22,13 +24,8 @@ RLC_STAGES = {"keyed_leaves", "keyed_group", "keyed_sums", "keyed_prep"}
 
 
 def _profiled(grp, fn):
-    lib, h = grp.ctx.lib, grp.ctx.handle
-    _lib.check(lib.dgpu_set_profiling(h, 1))
-    try:
-        out = fn()
-        return out, _lib.stage_times(grp.ctx)  # raises above DGPU_MAX_STAGES
-    finally:
-        _lib.check(lib.dgpu_set_profiling(h, 0))
+    with calls.profiled(grp.ctx) as stage_times:
+        return fn(), stage_times()  # raises above DGPU_MAX_STAGES
 
 
 @pytest.mark.parametrize("name,scheme", FIXTURES)
@@ -131,8 +128,7 @@ def test_errors_that_cancel_inside_a_share_group_are_caught(scheme):
 
 
 def test_no_group_installed():
-    ctx = _lib.Context(0)
-    try:
+    with contextlib.closing(_lib.Context(0)) as ctx:
         msgs = np.zeros(32, dtype=np.uint8)
         parts = np.zeros(98, dtype=np.uint8)
         plen = np.full(1, 98, dtype=np.uint32)
@@ -144,5 +140,3 @@ def test_no_group_installed():
         assert ctx.lib.dgpu_verify_partials_device(ctx.handle, 1, _lib.ptr(msgs), 1, _lib.ptr(parts), 98,
                                                    _lib.ptr(plen), 0, 0, _lib.ptr(bits), None,
                                                    None) == _lib.DGPU_ENOKEY
-    finally:
-        ctx.close()

@@ -56,8 +56,8 @@ def ctx(request):
 
 @pytest.mark.parametrize("name", FIXTURES)
 def test_ragged_batches_verify_and_verify_recovered(name, ctx):
-    from drand_amd import _lib
-    from drand_amd.chain import _pack_msgs, pack_beacons, Beacon
+    from drand_amd import calls
+    from drand_amd.chain import pack_beacons, Beacon
     from drand_amd.scheme import get_scheme_by_id_with_default
     from drand_amd.chain import scheme_code
     g = load_golden(name)
@@ -66,29 +66,15 @@ def test_ragged_batches_verify_and_verify_recovered(name, ctx):
     chained = not sch.decouple_prev_sig
     items = _items(g)
     pk = np.frombuffer(bytes.fromhex(g["pk"]), dtype=np.uint8).copy()
-    lib = ctx.lib
     for n in SIZES:
         pick = [items[(n + i) % len(items)] for i in range(n)]  # the start moves with n
         expect = [it[3] for it in pick]
         beacons = [Beacon(p if chained else b"", r, s) for p, r, s, _ in pick]
         rounds, sigs, sig_len, prev, prev_len = pack_beacons(beacons)
-        bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-        reason = np.zeros(n, dtype=np.uint8)
-        _lib.check(lib.dgpu_verify_beacons(ctx.handle, code, _lib.ptr(pk), pk.size, n, _lib.ptr(rounds),
-                                           _lib.ptr(sigs), sigs.shape[1], _lib.ptr(sig_len), _lib.ptr(prev),
-                                           prev.shape[1], _lib.ptr(prev_len), _lib.MODE_PER_ROUND, 0,
-                                           _lib.ptr(bits), _lib.ptr(reason)))
+        reason = calls.verify_beacons(ctx, code, pk, rounds, sigs, sig_len, prev, prev_len, fill=0xEE)
         assert reason.tolist() == expect, (name, n)
-        assert np.array_equal(np.unpackbits(bits, bitorder="little")[:n].astype(bool), reason == 0)
         # the same items as raw VerifyRecovered(pk, DigestMessage(...), sig)
-        mb, ml = _pack_msgs([_digest(chained, p, r) for p, r, _, _ in pick])
-        sb, sl = _pack_msgs([s for _, _, s, _ in pick])
-        width = 96 if code in (_lib.SCHEME_CHAINED, _lib.SCHEME_UNCHAINED) else 48
-        if sb.shape[1] < width:
-            sb = np.pad(sb, ((0, 0), (0, width - sb.shape[1])))
-        reason2 = np.zeros(n, dtype=np.uint8)
-        bits[:] = 0
-        _lib.check(lib.dgpu_verify_recovered(ctx.handle, code, _lib.ptr(pk), pk.size, n, _lib.ptr(mb), mb.shape[1],
-                                             _lib.ptr(ml), _lib.ptr(sb), sb.shape[1], _lib.ptr(sl),
-                                             _lib.MODE_PER_ROUND, 0, _lib.ptr(bits), _lib.ptr(reason2)))
+        mb, ml = calls.pack_msgs([_digest(chained, p, r) for p, r, _, _ in pick])
+        sb, sl = calls.pack_msgs([s for _, _, s, _ in pick], calls.sig_width(code))
+        reason2 = calls.verify_recovered(ctx, code, pk, mb, ml, sb, sl, fill=0xEE)
         assert reason2.tolist() == expect, (name, n, "recovered")

@@ -32,16 +32,9 @@ def ctxs():
 
 
 def _reasons(ctx, scheme, pk, rounds, sigs, sig_len, prev, prev_len, mode):
-    from drand_amd import _lib
-    n = len(rounds)
-    _lib.check(ctx.lib.dgpu_set_pubkey(ctx.handle, scheme, pk, len(pk)), ctx.lib)
-    bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-    reason = np.zeros(n, dtype=np.uint8)
-    _lib.check(ctx.lib.dgpu_verify_batch(ctx.handle, scheme, n, _lib.ptr(rounds), _lib.ptr(sigs), sigs.shape[1],
-                                         _lib.ptr(sig_len), _lib.ptr(prev), prev.shape[1], _lib.ptr(prev_len), mode, 7,
-                                         _lib.ptr(bits), _lib.ptr(reason)), ctx.lib)
-    assert np.array_equal(np.unpackbits(bits, bitorder="little")[:n].astype(bool), reason == 0)
-    return reason.tolist()
+    from drand_amd import calls
+    calls.set_pubkey(ctx, scheme, pk)
+    return calls.verify_batch(ctx, scheme, rounds, sigs, sig_len, prev, prev_len, mode, 7, fill=0xEE).tolist()
 
 
 def _pack(beacons):
@@ -102,22 +95,12 @@ def test_golden_chain_forms_agree(ctxs, name, mode):
 def test_recover_smallest_fixture_forms_agree(ctxs):
     """Threshold recovery of the t = 3 fixture: the recovered bytes and the
     failures equal the fixture's in both forms and builds."""
-    from drand_amd import _lib
-    from drand_amd.threshold import pack_partials, unpack_recovered
+    from drand_amd.threshold import ThresholdGroup
     g = load_golden("recover_t3_n8.json")
     commits = [bytes.fromhex(c) for c in g["commits"]]
     msgs = [bytes.fromhex(c["msg"]) for c in g["cases"]]
     parts = [[bytes.fromhex(p) for p in c["partials"]] for c in g["cases"]]
     for k, ctx in ctxs.items():
-        buf = np.frombuffer(b"".join(commits), dtype=np.uint8).copy()
-        _lib.check(ctx.lib.dgpu_set_group(ctx.handle, len(commits), g["n"], _lib.ptr(buf)), ctx.lib)
-        mb, pb, plen, m, stride = pack_partials(msgs, parts)
-        nr = len(msgs)
-        out = np.zeros(nr * 96, dtype=np.uint8)
-        ok = np.zeros((nr + 7) // 8, dtype=np.uint8)
-        pv = np.zeros(nr * m, dtype=np.uint8)
-        _lib.check(ctx.lib.dgpu_recover_batch(ctx.handle, nr, _lib.ptr(mb), m, _lib.ptr(pb), stride, _lib.ptr(plen),
-                                              _lib.ptr(out), _lib.ptr(ok), _lib.ptr(pv)), ctx.lib)
-        sigs, valid = unpack_recovered(out, ok, pv, parts, m)
+        sigs, valid = ThresholdGroup(commits, g["n"], ctx=ctx).recover_batch(msgs, parts)
         assert [s.hex() if s else None for s in sigs] == [c["recovered"] for c in g["cases"]], k
         assert [v for v in valid] == [c["valid"] for c in g["cases"]], k

@@ -32,23 +32,10 @@ def _ctx(seg):
 
 
 def _reasons(ctx, code, c, mode, profile=False):
-    from drand_amd import _lib
-    n = len(c)
-    bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-    reason = np.zeros(n, dtype=np.uint8)
-    pk = np.frombuffer(c.pk, dtype=np.uint8).copy()
-    if profile:
-        _lib.check(ctx.lib.dgpu_set_profiling(ctx.handle, 1))
-    try:
-        _lib.check(ctx.lib.dgpu_verify_beacons(ctx.handle, code, _lib.ptr(pk), pk.size, n, _lib.ptr(c.rounds),
-                                               _lib.ptr(c.sigs), c.sigs.shape[1], _lib.ptr(c.sig_len),
-                                               _lib.ptr(c.prev), c.prev.shape[1], _lib.ptr(c.prev_len), mode, 0x5EED,
-                                               _lib.ptr(bits), _lib.ptr(reason)))
-        stages = set(_lib.stage_times(ctx)) if profile else set()
-    finally:
-        if profile:
-            _lib.check(ctx.lib.dgpu_set_profiling(ctx.handle, 0))
-    return reason, stages
+    from drand_amd import calls
+    with calls.profiled(ctx) if profile else contextlib.nullcontext() as stage_times:
+        reason = calls.verify_beacons(ctx, code, c.pk, *c.records(), mode, 0x5EED, fill=0xEE)
+        return reason, set(stage_times()) if profile else set()
 
 
 @pytest.mark.parametrize("seg", ["1", "0"])

@@ -15,13 +15,11 @@ corruption of the explicit PreviousSig column has no array in the linked form:
 those rounds stay valid here.  No shard boundary is a multiple of 64 (asserted),
 so the first item of every later shard verifies only through a correct halo.
 Marked gpu."""
-import hashlib
-import types
-
 import numpy as np
 import pytest
 
 from conftest import load_golden
+from segment_helpers import check_randomness as _check_randomness
 
 pytestmark = pytest.mark.gpu
 
@@ -32,13 +30,6 @@ SHARD = {2: 2504, 3: 1672, 8: 632}
 def _sch(name="pedersen-bls-chained"):
     from drand_amd.scheme import get_scheme_by_id_with_default
     return get_scheme_by_id_with_default(name)
-
-
-def _check_randomness(out, sigs, sig_len, reason):
-    """SHA-256 of the signature where the round verifies, zeros elsewhere."""
-    for i in range(len(reason)):
-        want = hashlib.sha256(bytes(sigs[i, :sig_len[i]])).digest() if reason[i] == 0 else bytes(32)
-        assert bytes(out[i]) == want, i
 
 
 def _linked_invalid(n, corrupted):
@@ -74,11 +65,8 @@ def chain5003():
 
 def _stats(mv, k):
     """dgpu_staging_stats of the handle's k-th context."""
-    import ctypes
     from drand_amd import _lib
-    h = ctypes.c_void_p()
-    _lib.check(mv.mctx.lib.dgpu_multi_context(mv.mctx.handle, k, ctypes.byref(h)))
-    return _lib.staging_stats(types.SimpleNamespace(lib=mv.mctx.lib, handle=h))
+    return _lib.staging_stats(mv._shard_verifiers()[k].ctx)
 
 
 @pytest.mark.parametrize("ndev", [2, 3, 8])

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from test_abi import declared_params as _declared_params
 
 NAMES = {"dgpu_verify_keyed": 17, "dgpu_verify_keyed_device": 18, "dgpu_verify_partials": 11,
          "dgpu_verify_partials_device": 12}
@@ -16,12 +17,6 @@ NAMES = {"dgpu_verify_keyed": 17, "dgpu_verify_keyed_device": 18, "dgpu_verify_p
 
 def _header():
     return open(os.path.join(ROOT, "include", "drand_gpu.h")).read()
-
-
-def _declared_params(name):
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*?)\)\s*;", _header(), re.S)
-    assert m, f"{name} is not declared in include/drand_gpu.h"
-    return [p.strip() for p in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(",")]
 
 
 def test_header_declares_the_entry_points_and_the_reason():

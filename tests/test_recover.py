@@ -6,6 +6,7 @@ the group secret's signature and verifies under the group key) on the
 committed fixtures, and the partial-index rule.  GPU: the batch C-ABI call
 reproduces every fixture bit-exactly (recovered bytes, failure verdicts,
 per-partial validity)."""
+import contextlib
 import struct
 
 import pytest
@@ -66,19 +67,15 @@ def test_gpu_recover_stage_count_within_max_stages():
     """The recovery pipeline records the most stages of any call (hash,
     decode, engine stages, MSM, verdicts): dgpu_stage_times' count (the
     count needed) stays within DGPU_MAX_STAGES (_lib.stage_times asserts it)."""
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     from drand_amd.threshold import ThresholdGroup
     g = load_golden("recover_t17_n32.json")
     grp = ThresholdGroup([bytes.fromhex(c) for c in g["commits"]], g["n"])
     msgs = [bytes.fromhex(c["msg"]) for c in g["cases"]]
     parts = [[bytes.fromhex(p) for p in c["partials"]] for c in g["cases"]]
-    lib = grp.ctx.lib
-    _lib.check(lib.dgpu_set_profiling(grp.ctx.handle, 1))
-    try:
+    with calls.profiled(grp.ctx) as stage_times:
         grp.recover_batch(msgs, parts)
-        st = _lib.stage_times(grp.ctx)
-    finally:
-        _lib.check(lib.dgpu_set_profiling(grp.ctx.handle, 0))
+        st = stage_times()
     assert 8 < len(st) <= _lib.MAX_STAGES, st
 
 
@@ -144,31 +141,24 @@ def test_gpu_recover_device_entry_point_bench_batch():
     """The bench's configs[4] workload at small size through
     dgpu_recover_batch_device: recovered == group signature on rounds with t
     good partials, failure (zeros) on rounds with one invalid partial."""
-    import ctypes
-    import numpy as np
     import torch
-    from drand_amd import _lib, synth
+    from drand_amd import calls, synth
     from drand_amd.chain import get_context
     grp = synth.make_group(4, 5, 8)
     msgs, parts, expect_ok = synth.make_recovery_batch(grp, 96, seed=1, bad_rate=0.25)
     assert 0 < int((~expect_ok).sum()) < 96
     expect = synth.group_signatures(grp, msgs)
     ctx = get_context(0)
-    cb = np.frombuffer(b"".join(grp.commits), dtype=np.uint8).copy()
-    _lib.check(ctx.lib.dgpu_set_group(ctx.handle, grp.t, grp.n, _lib.ptr(cb)))
-    from drand_amd.threshold import ThresholdGroup
-    ThresholdGroup._active = None  # group replaced behind ThresholdGroup's cache
+    calls.set_group(ctx, grp.scheme_code, grp.t, grp.n, grp.commits)  # (recorded on ctx: a ThresholdGroup sees it)
     n, m = parts.shape[:2]
     dev = torch.device("cuda", 0)
     d_msgs = torch.from_numpy(msgs).to(dev)
-    d_parts = torch.from_numpy(parts.reshape(n * m, 98).copy()).to(dev)
-    d_plen = torch.full((n * m,), 98, dtype=torch.int32, device=dev)
+    d_parts = torch.from_numpy(parts).to(dev)
+    d_plen = torch.full((n, m), 98, dtype=torch.int32, device=dev)
     d_out = torch.zeros((n, 96), dtype=torch.uint8, device=dev)
     d_ok = torch.zeros(n, dtype=torch.uint8, device=dev)
     d_st = torch.full((n * m,), 0xFF, dtype=torch.uint8, device=dev)
-    _lib.check(ctx.lib.dgpu_recover_batch_device(ctx.handle, n, d_msgs.data_ptr(), m, d_parts.data_ptr(), 98,
-                                                 d_plen.data_ptr(), d_out.data_ptr(), d_ok.data_ptr(),
-                                                 d_st.data_ptr(), ctypes.c_void_p(0)))
+    calls.recover_batch_device(ctx, d_msgs, d_parts, d_plen, d_out, d_ok, d_st)
     torch.cuda.synchronize()
     ok = d_ok.cpu().numpy().astype(bool)
     out = d_out.cpu().numpy()
@@ -259,27 +249,48 @@ def test_gpu_recover_generic_redo_paths_match_fixtures(name, statuses):
     (the generic mixed addition redoing each slice) -- recovered bytes and
     failures equal the fixture, per-partial statuses and batched check."""
     from conftest import open_ctx
-    from drand_amd import _lib
-    from drand_amd.threshold import pack_partials, unpack_recovered
-    import numpy as np
+    from drand_amd.threshold import ThresholdGroup
     g = load_golden(name)
     commits = [bytes.fromhex(c) for c in g["commits"]]
     msgs = [bytes.fromhex(c["msg"]) for c in g["cases"]]
     parts = [[bytes.fromhex(p) for p in c["partials"]] for c in g["cases"]]
-    ctx = open_ctx({"DGPU_TEST_FORCE_EXC": "1"})
-    try:
-        buf = np.frombuffer(b"".join(commits), dtype=np.uint8).copy()
-        _lib.check(ctx.lib.dgpu_set_group(ctx.handle, len(commits), g["n"], _lib.ptr(buf)))
-        mb, pb, plen, m, stride = pack_partials(msgs, parts)
-        nr = len(msgs)
-        out = np.zeros(nr * 96, dtype=np.uint8)
-        ok = np.zeros((nr + 7) // 8, dtype=np.uint8)
-        pv = np.zeros(nr * m, dtype=np.uint8) if statuses else None
-        _lib.check(ctx.lib.dgpu_recover_batch(ctx.handle, nr, _lib.ptr(mb), m, _lib.ptr(pb), stride, _lib.ptr(plen),
-                                              _lib.ptr(out), _lib.ptr(ok), _lib.ptr(pv)))
-        sigs, valid = unpack_recovered(out, ok, pv, parts, m)
-    finally:
-        ctx.close()
+    with contextlib.closing(open_ctx({"DGPU_TEST_FORCE_EXC": "1"})) as ctx:
+        sigs, valid = ThresholdGroup(commits, g["n"], ctx=ctx).recover_batch(msgs, parts, statuses=statuses)
     assert [s.hex() if s else None for s in sigs] == [c["recovered"] for c in g["cases"]]
     if statuses:
         assert [v for v in valid] == [c["valid"] for c in g["cases"]]
+
+
+@pytest.mark.gpu
+def test_gpu_groups_on_two_contexts_keep_their_own_group(gpu_ctx):
+    """Which group a context holds is the context's own state: the t = 3
+    fixture's group on the shared context and a generated group on a second
+    context, two rounds each, the calls interleaved -- every call returns its
+    own group's signatures.  A third object shares the first context with the
+    fixture's group: the two take turns there."""
+    from conftest import open_ctx
+    from drand_amd import synth
+    from drand_amd.threshold import ThresholdGroup
+    g = load_golden("recover_t3_n8.json")
+    cases = [c for c in g["cases"] if c["recovered"] is not None][:2]
+    a_msgs = [bytes.fromhex(c["msg"]) for c in cases]
+    a_parts = [[bytes.fromhex(p) for p in c["partials"]] for c in cases]
+    a_want = [bytes.fromhex(c["recovered"]) for c in cases]
+    other = synth.make_group(g["seed"] + 77, 4, 9)
+    assert other.commits[0] != bytes.fromhex(g["commits"][0])
+    msgs, parts, ok = synth.make_recovery_batch(other, 2, seed=5, bad_rate=0.0)
+    assert ok.all()
+    b_msgs = [bytes(m) for m in msgs]
+    b_parts = [[bytes(p) for p in row] for row in parts]
+    b_want = [bytes(s) for s in synth.group_signatures(other, msgs)]
+    assert len(a_want) == 2 and not set(a_want) & set(b_want)
+    with contextlib.closing(open_ctx({})) as second:
+        assert second is not gpu_ctx
+        a = ThresholdGroup([bytes.fromhex(c) for c in g["commits"]], g["n"], ctx=gpu_ctx)
+        b = ThresholdGroup(other.commits, other.n, ctx=second)
+        b_shared = ThresholdGroup(other.commits, other.n, ctx=gpu_ctx)
+        for _ in range(2):
+            assert a.recover_batch(a_msgs, a_parts)[0] == a_want
+            assert b.recover_batch(b_msgs, b_parts)[0] == b_want
+            assert b_shared.recover_batch(b_msgs, b_parts)[0] == b_want
+        assert second.installed_group == b._key != a._key

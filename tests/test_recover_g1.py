@@ -11,6 +11,7 @@ before touching the library.  GPU: every fixture bit-exactly on the exact
 per-partial path and on the batched check, reason codes, a 197-round
 property batch, the synthetic-partial tool, group switching on one context,
 error paths, the stage count and the multi-device loopback."""
+import contextlib
 import ctypes
 import hashlib
 import os
@@ -197,7 +198,7 @@ def test_gpu_recover_g1_reason_codes_device_entry_point():
     that offers a 98-byte (G2-signature) partial to the G1 group."""
     import numpy as np
     import torch
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     from drand_amd.threshold import pack_partials
     g = load_golden("recover_g1_on_g1_t3_n8.json")
     msgs, parts = _batch(g)
@@ -213,17 +214,15 @@ def test_gpu_recover_g1_reason_codes_device_entry_point():
     nr = len(msgs)
     dev = torch.device("cuda", 0)
     d_msgs = torch.from_numpy(mb).to(dev)
-    d_parts = torch.from_numpy(buf.reshape(nr * m, stride).copy()).to(dev)
-    d_plen = torch.from_numpy(plen.reshape(-1).astype(np.int32)).to(dev)
+    d_parts = torch.from_numpy(buf).to(dev)
+    d_plen = torch.from_numpy(plen.astype(np.int32)).to(dev)
     d_out = torch.full((nr, 48), 0xEE, dtype=torch.uint8, device=dev)
     d_ok = torch.zeros(nr, dtype=torch.uint8, device=dev)
     d_st = torch.full((nr * m,), 0xFF, dtype=torch.uint8, device=dev)
     from drand_amd.threshold import ThresholdGroup
     with ThresholdGroup._lock:
         grp._install()
-        _lib.check(grp.ctx.lib.dgpu_recover_batch_device(grp.ctx.handle, nr, d_msgs.data_ptr(), m, d_parts.data_ptr(),
-                                                         stride, d_plen.data_ptr(), d_out.data_ptr(), d_ok.data_ptr(),
-                                                         d_st.data_ptr(), ctypes.c_void_p(0)))
+        calls.recover_batch_device(grp.ctx, d_msgs, d_parts, d_plen, d_out, d_ok, d_st)
     torch.cuda.synchronize()
     st = d_st.cpu().numpy().reshape(nr, m)
     out = d_out.cpu().numpy()
@@ -376,20 +375,16 @@ def test_gpu_set_group_scheme_error_paths_keep_the_group():
 
 @pytest.mark.gpu
 def test_gpu_recover_g1_stage_count_within_max_stages():
-    from drand_amd import _lib
+    from drand_amd import _lib, calls
     g = load_golden("recover_g1_on_g1_t17_n32.json")
     grp = _group(g)
     msgs, parts = _batch(g)
-    lib = grp.ctx.lib
-    _lib.check(lib.dgpu_set_profiling(grp.ctx.handle, 1))
-    try:
+    with calls.profiled(grp.ctx) as stage_times:
         for statuses in (True, False):
             grp.recover_batch(msgs, parts, statuses=statuses)
-            st = _lib.stage_times(grp.ctx)
+            st = stage_times()
             assert 8 < len(st) <= _lib.MAX_STAGES, st
             assert "recover_msm" in st and "eng_lines" in st
-    finally:
-        _lib.check(lib.dgpu_set_profiling(grp.ctx.handle, 0))
 
 
 @pytest.mark.gpu
@@ -398,27 +393,15 @@ def test_gpu_recover_g1_library_defaults(statuses):
     """The shipped thresholds (the suite lowers them, conftest.py): a small
     call takes the Granger-Scott final exponentiation and the lane kernels'
     size class; the G1 form's lines kernel serves every size."""
-    import numpy as np
     from conftest import open_ctx
     from drand_amd import _lib
-    from drand_amd.threshold import pack_partials, unpack_recovered
+    from drand_amd.threshold import ThresholdGroup
     g = load_golden("recover_g1_rfc9380_t17_n32.json")
     msgs, parts = _batch(g)
-    commits = b"".join(bytes.fromhex(c) for c in g["commits"])
-    ctx = open_ctx({"DGPU_THR_MIN": "65536", "DGPU_FE_GS_MAX": "16384", "DGPU_COF_ENGINE_MAX": "16384"})
-    try:
-        buf = np.frombuffer(commits, dtype=np.uint8).copy()
-        _lib.check(ctx.lib.dgpu_set_group_scheme(ctx.handle, _lib.SCHEME_G1_RFC9380, g["t"], g["n"], _lib.ptr(buf), 96))
-        mb, pb, plen, m, stride = pack_partials(msgs, parts, _lib.SCHEME_G1_RFC9380)
-        nr = len(msgs)
-        out = np.zeros(nr * 48, dtype=np.uint8)
-        ok = np.zeros((nr + 7) // 8, dtype=np.uint8)
-        pv = np.zeros(nr * m, dtype=np.uint8) if statuses else None
-        _lib.check(ctx.lib.dgpu_recover_batch(ctx.handle, nr, _lib.ptr(mb), m, _lib.ptr(pb), stride, _lib.ptr(plen),
-                                              _lib.ptr(out), _lib.ptr(ok), _lib.ptr(pv)))
-        sigs, valid = unpack_recovered(out, ok, pv, parts, m, 48)
-    finally:
-        ctx.close()
+    assert len(g["commits"]) == g["t"]
+    with contextlib.closing(open_ctx({"DGPU_THR_MIN": "65536", "DGPU_FE_GS_MAX": "16384", "DGPU_COF_ENGINE_MAX": "16384"})) as ctx:
+        grp = ThresholdGroup([bytes.fromhex(c) for c in g["commits"]], g["n"], scheme=_lib.SCHEME_G1_RFC9380, ctx=ctx)
+        sigs, valid = grp.recover_batch(msgs, parts, statuses=statuses)
     assert [s.hex() if s else None for s in sigs] == [c["recovered"] for c in g["cases"]]
     if statuses:
         assert valid == [c["valid"] for c in g["cases"]]
@@ -429,7 +412,6 @@ def test_gpu_recover_g1_multi_same_device_equals_single(monkeypatch):
     """D = 2 contexts on one GPU, the 17/32 fixture padded to 21 rounds
     (shards 16 + 5): dgpu_recover_multi == the single-context call."""
     from drand_amd.multi import MultiThresholdGroup
-    from drand_amd.threshold import ThresholdGroup
     monkeypatch.setenv("DGPU_MULTI_ALLOW_SAME_DEVICE", "1")
     g = load_golden("recover_g1_on_g1_t17_n32.json")
     msgs, parts = _batch(g)
@@ -441,7 +423,6 @@ def test_gpu_recover_g1_multi_same_device_equals_single(monkeypatch):
         got_rlc = mg.recover_batch(msgs, parts, statuses=False)
     finally:
         mg.close()
-    ThresholdGroup._active = None
     assert got == single
     assert got_rlc[0] == single[0]
     assert [s.hex() if s else None for s in got[0]] == ([c["recovered"] for c in g["cases"]] * 3)[:21]

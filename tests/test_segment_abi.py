@@ -6,17 +6,9 @@ import os
 import re
 
 from conftest import ROOT
+from test_abi import declared_params as _declared_params
 
 NAMES = ("dgpu_verify_segment", "dgpu_verify_segment_device")
-
-
-def _declared_params(name):
-    """Parameter list of `name`'s declaration in the header (comments cut)."""
-    txt = open(os.path.join(ROOT, "include", "drand_gpu.h")).read()
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*?)\)\s*;", txt, re.S)
-    assert m, f"{name} is not declared in include/drand_gpu.h"
-    params = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    return [p.strip() for p in params.split(",")]
 
 
 def test_header_declares_the_segment_entry_points():

@@ -8,6 +8,7 @@ import os
 import re
 
 from conftest import ROOT
+from test_abi import declared_params as _declared_params
 
 PARAMS = {
     "dgpu_verify_segment_shard_device": [
@@ -23,15 +24,6 @@ PARAMS = {
 # positions of the 64-bit values (first_round, rlc_seed) and of the size_t ones (pk_len, n, strides, lengths)
 U64 = {"first_round", "rlc_seed"}
 SIZE_T = {"pk_len", "n", "sig_stride", "seed_prev_len"}
-
-
-def _declared_params(name):
-    """Parameter list of `name`'s declaration in the header (comments cut)."""
-    txt = open(os.path.join(ROOT, "include", "drand_gpu.h")).read()
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*?)\)\s*;", txt, re.S)
-    assert m, f"{name} is not declared in include/drand_gpu.h"
-    params = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    return [" ".join(p.split()) for p in params.split(",")]
 
 
 def test_header_declares_the_entry_points():

@@ -62,7 +62,7 @@ SETS = 8  # buffer sets a timing rotates over: together far beyond the 256 MB la
 
 def kernel_alone(ctx, rows, reps):
     import torch
-    from drand_amd import _lib
+    from drand_amd import calls
     n = len(rows)
     ln = np.array([len(r) for r in rows], dtype=np.uint32)
     off = np.concatenate([[0], np.cumsum(ln, dtype=np.uint64)[:-1]]).astype(np.uint64)
@@ -81,10 +81,8 @@ def kernel_alone(ctx, rows, reps):
     def launch():
         t = sets[turn[0] % SETS]
         turn[0] += 1
-        _lib.check(ctx.lib.dgpu_decode_rows_device(
-            ctx.handle, n, _lib.ptr(t["rows"]), buf.size, _lib.ptr(t["off"]), _lib.ptr(t["len"]), _lib.ptr(t["rounds"]),
-            _lib.ptr(t["sigs"]), 96, _lib.ptr(t["sig_len"]), _lib.ptr(t["prev"]), 96, _lib.ptr(t["prev_len"]),
-            _lib.ptr(t["ok"]), None), ctx.lib)
+        calls.decode_rows_device(ctx, t["rows"], t["off"], t["len"], t["rounds"], t["sigs"], t["sig_len"], t["prev"],
+                                 t["prev_len"], t["ok"], sig_stride=96, prev_stride=96)
 
     def copy():
         t = sets[turn[0] % SETS]

@@ -34,7 +34,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from drand_amd import _lib, identity, synth  # noqa: E402
+from drand_amd import _lib, calls, identity, synth  # noqa: E402
 from drand_amd.chain import get_context, sign, verify_recovered  # noqa: E402
 from drand_amd.scheme import get_scheme_by_id_with_default  # noqa: E402
 
@@ -44,13 +44,9 @@ GROUPS = (("G2 signatures", "pedersen-bls-unchained", _lib.SCHEME_UNCHAINED),
 
 
 def derive_keys(ctx, code, count):
-    klen = 96 if code == _lib.SCHEME_G1_RFC9380 else 48
     sks = [synth.derive_secret(90000 + j) for j in range(count)]
-    keys = np.zeros((count, klen), dtype=np.uint8)
-    for j, sk in enumerate(sks):
-        skb = np.frombuffer(sk.to_bytes(32, "big"), dtype=np.uint8).copy()
-        _lib.check(ctx.lib.dgpu_derive_pubkey(ctx.handle, code, _lib.ptr(skb), _lib.ptr(keys[j]), klen))
-    return sks, keys
+    keys = np.frombuffer(b"".join(calls.derive_pubkey(ctx, code, sk) for sk in sks), dtype=np.uint8)
+    return sks, keys.reshape(count, calls.key_width(code)).copy()
 
 
 def make_records(ctx, code, sks, n, K):
@@ -60,24 +56,17 @@ def make_records(ctx, code, sks, n, K):
     idx = (np.arange(n, dtype=np.uint64) * K // n).astype(np.uint32)
     signer = (idx % DISTINCT).astype(np.uint32)
     shares = np.frombuffer(b"".join(s.to_bytes(32, "big") for s in sks), dtype=np.uint8).copy()
-    slen = 48 if code == _lib.SCHEME_G1_RFC9380 else 96
-    out = np.zeros((n, 2 + slen), dtype=np.uint8)
-    zero = np.zeros(n, dtype=np.uint32)
-    _lib.check(ctx.lib.dgpu_make_partials_scheme(ctx.handle, code, n, _lib.ptr(msgs), 1, _lib.ptr(signer), _lib.ptr(zero),
-                                                 _lib.ptr(shares), len(sks), _lib.ptr(out)))
-    return msgs, np.ascontiguousarray(out[:, 2:]), idx
+    zero = np.zeros((n, 1), dtype=np.uint32)
+    out = calls.make_partials_scheme(ctx, code, msgs, signer.reshape(n, 1), zero, shares)
+    return msgs, np.ascontiguousarray(out[:, 0, 2:]), idx
 
 
 def keyed_call(ctx, code, table, idx, msgs, sigs, mode, seed):
     n = len(idx)
     ml = np.full(n, 32, dtype=np.uint32)
     sl = np.full(n, sigs.shape[1], dtype=np.uint32)
-    bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-    reason = np.zeros(n, dtype=np.uint8)
     t0 = time.perf_counter()
-    _lib.check(ctx.lib.dgpu_verify_keyed(ctx.handle, code, table.shape[0], _lib.ptr(table), table.shape[1], n,
-                                         _lib.ptr(idx), _lib.ptr(msgs), 32, _lib.ptr(ml), _lib.ptr(sigs), sigs.shape[1],
-                                         _lib.ptr(sl), mode, seed, _lib.ptr(bits), _lib.ptr(reason)), ctx.lib)
+    reason = calls.verify_keyed(ctx, code, table, table.shape[1], idx, msgs, ml, sigs, sl, mode, seed)
     return time.perf_counter() - t0, reason
 
 
@@ -88,19 +77,14 @@ def single_calls(ctx, code, table, idx, msgs, sigs, K, max_calls):
     picks = np.arange(K) if K <= max_calls else np.unique(np.linspace(0, K - 1, max_calls).astype(np.int64))
     ml = np.full(n, 32, dtype=np.uint32)
     sl = np.full(n, sigs.shape[1], dtype=np.uint32)
-    bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-    reason = np.zeros(n, dtype=np.uint8)
     bad = 0
     t0 = time.perf_counter()
     for j in picks:
         lo, hi = int(bounds[j]), int(bounds[j + 1])
         if hi == lo:
             continue
-        _lib.check(ctx.lib.dgpu_verify_recovered(ctx.handle, code, _lib.ptr(table[j]), table.shape[1], hi - lo,
-                                                 _lib.ptr(msgs[lo:hi]), 32, _lib.ptr(ml), _lib.ptr(sigs[lo:hi]),
-                                                 sigs.shape[1], _lib.ptr(sl), 0, 0, _lib.ptr(bits), _lib.ptr(reason)),
-                   ctx.lib)
-        bad += int(np.count_nonzero(reason[:hi - lo]))
+        bad += int(np.count_nonzero(calls.verify_recovered(ctx, code, table[j], msgs[lo:hi], ml[lo:hi], sigs[lo:hi],
+                                                            sl[lo:hi])))
     dt = time.perf_counter() - t0
     return dt * K / len(picks), len(picks), bad
 
@@ -148,21 +132,19 @@ def main():
             stages = {}
             note = ""
             for rep in range(args.reps):
-                _lib.check(ctx.lib.dgpu_set_profiling(ctx.handle, 0))
                 dt, made, bad = single_calls(ctx, code, table, idx, msgs, sigs, K, args.max_calls)
                 assert bad == 0
                 rows["calls"].append(dt)
                 if made < K:
                     note = f"  [(a) extrapolated from {made} of {K} calls]"
-                _lib.check(ctx.lib.dgpu_set_profiling(ctx.handle, 1))
-                for label, mode, s, expect in (("keyed", 0, sigs, None), ("rlc clean", 1, sigs, None),
-                                               ("rlc 0.1% bad", 1, dirty, expect_dirty)):
-                    dt, reason = keyed_call(ctx, code, table, idx, msgs, s, mode, 0x5EED0000 + rep)
-                    assert np.array_equal(reason, expect) if expect is not None else not reason.any(), label
-                    if not rows[label] or dt < min(rows[label]):
-                        stages[label] = _lib.stage_times(ctx)
-                    rows[label].append(dt)
-            _lib.check(ctx.lib.dgpu_set_profiling(ctx.handle, 0))
+                with calls.profiled(ctx) as stage_times:
+                    for label, mode, s, expect in (("keyed", 0, sigs, None), ("rlc clean", 1, sigs, None),
+                                                   ("rlc 0.1% bad", 1, dirty, expect_dirty)):
+                        dt, reason = keyed_call(ctx, code, table, idx, msgs, s, mode, 0x5EED0000 + rep)
+                        assert np.array_equal(reason, expect) if expect is not None else not reason.any(), label
+                        if not rows[label] or dt < min(rows[label]):
+                            stages[label] = stage_times()
+                        rows[label].append(dt)
             base = min(rows["calls"])
             for label, v in rows.items():
                 say(f"  {label:14s} " + " ".join(f"{x:9.4f}" for x in v) + f"   best {min(v):9.4f} s"
@@ -173,13 +155,7 @@ def main():
     # identities: one keyed call for the group file's nodes against one call per node
     auth = get_scheme_by_id_with_default("")
     sks = [synth.derive_secret(95000 + j) for j in range(args.nodes)]
-    keys = []
-    klen = 48
-    for sk in sks:
-        pk = np.zeros(klen, dtype=np.uint8)
-        skb = np.frombuffer(sk.to_bytes(32, "big"), dtype=np.uint8).copy()
-        _lib.check(ctx.lib.dgpu_derive_pubkey(ctx.handle, _lib.SCHEME_CHAINED, _lib.ptr(skb), _lib.ptr(pk), klen))
-        keys.append(bytes(pk))
+    keys = [calls.derive_pubkey(ctx, _lib.SCHEME_CHAINED, sk) for sk in sks]
     nodes = [(k, sign(sk, [identity.identity_hash(k)], auth)[0]) for k, sk in zip(keys, sks)]
     nodes[7] = (nodes[7][0], nodes[8][1])
     say(f"\n== identities: Group.UnsignedIdentities over {args.nodes} nodes (one of them unsigned)")

@@ -12,41 +12,34 @@ reported as rounds/s, with the dgpu_stage_times split of one further call
 and the mismatches against synth.group_signatures (must be 0).  The
 G2-signature group runs first and is the yardstick of the box."""
 import argparse
-import ctypes
 import os
 import statistics
 import sys
-
-import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 
 def run(name, code, args):
     import torch
-    from drand_amd import _lib, synth
+    from drand_amd import calls, synth
     from drand_amd.chain import get_context
     dev = torch.device("cuda", 0)
     ctx = get_context(0)
-    lib = ctx.lib
     grp = synth.make_group(args.seed, args.t, args.n, scheme=code)
     msgs, parts, expect_ok = synth.make_recovery_batch(grp, args.rounds, args.seed, args.bad_rate)
     expect = synth.group_signatures(grp, msgs)
     n, m, pb = parts.shape
     sb = expect.shape[1]
-    cbuf = np.frombuffer(b"".join(grp.commits), dtype=np.uint8).copy()
-    _lib.check(lib.dgpu_set_group_scheme(ctx.handle, code, grp.t, grp.n, _lib.ptr(cbuf), len(grp.commits[0])))
+    calls.set_group(ctx, code, grp.t, grp.n, grp.commits)
     d_msgs = torch.from_numpy(msgs).to(dev)
-    d_parts = torch.from_numpy(parts.reshape(n * m, pb)).to(dev)
-    d_plen = torch.full((n * m,), pb, dtype=torch.int32, device=dev)
+    d_parts = torch.from_numpy(parts).to(dev)
+    d_plen = torch.full((n, m), pb, dtype=torch.int32, device=dev)
     d_out = torch.zeros((n, sb), dtype=torch.uint8, device=dev)
     d_ok = torch.zeros(n, dtype=torch.uint8, device=dev)
     stream = torch.cuda.current_stream(dev)
 
     def step():
-        _lib.check(lib.dgpu_recover_batch_device(ctx.handle, n, d_msgs.data_ptr(), m, d_parts.data_ptr(), pb,
-                                                 d_plen.data_ptr(), d_out.data_ptr(), d_ok.data_ptr(), None,
-                                                 ctypes.c_void_p(stream.cuda_stream)))
+        calls.recover_batch_device(ctx, d_msgs, d_parts, d_plen, d_out, d_ok, None, stream)
 
     step()  # warm-up: allocations, code load
     torch.cuda.synchronize()
@@ -58,13 +51,10 @@ def run(name, code, args):
         e1.record(stream)
         e1.synchronize()
         ms.append(e0.elapsed_time(e1))
-    _lib.check(lib.dgpu_set_profiling(ctx.handle, 1))
-    try:
+    with calls.profiled(ctx) as stage_times:
         step()
         torch.cuda.synchronize()
-        stages = _lib.stage_times(ctx)
-    finally:
-        _lib.check(lib.dgpu_set_profiling(ctx.handle, 0))
+        stages = stage_times()
     ok = d_ok.cpu().numpy().astype(bool)
     out = d_out.cpu().numpy()
     both = ok & expect_ok

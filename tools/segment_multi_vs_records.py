@@ -28,11 +28,9 @@ is).  The expectation is parity, not gain: staging is already hidden
 generator-segment starts fail by construction, which costs the per-round path
 nothing (it has no early exit).  One GPU: RCCL with real ranks is unmeasured."""
 import argparse
-import ctypes
 import os
 import sys
 import time
-import types
 
 import numpy as np
 
@@ -49,43 +47,29 @@ def main():
     os.environ["DGPU_MULTI_ALLOW_SAME_DEVICE"] = "1"
     import torch
     torch.cuda.init()
-    from drand_amd import _lib, synth
+    from drand_amd import _lib, calls, synth
     from drand_amd.chain import get_context
     ctx = get_context(0)
-    lib, h = ctx.lib, ctx.handle
     code, n, D = _lib.SCHEME_CHAINED, args.rounds, 2
     c = synth.make_chain(args.seed, n, code, seg_len=64)
-    pk = np.frombuffer(c.pk, dtype=np.uint8).copy()
     link = c.prev[0, :c.prev_len[0]].copy()
     first = int(c.rounds[0])
-    bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-    reason = np.zeros(n, dtype=np.uint8)
-    rand = np.zeros((n, 32), dtype=np.uint8)
     stride = c.sigs.shape[1]
     starts = len(range(64, n, 64))
     shards = [_lib.shard_range(n, D, k) for k in range(D)]
     mctx = _lib.MultiContext([0] * D)
-    sub = []
-    for k in range(D):
-        hk = ctypes.c_void_p()
-        _lib.check(lib.dgpu_multi_context(mctx.handle, k, ctypes.byref(hk)))
-        sub.append(types.SimpleNamespace(lib=lib, handle=hk))
+    sub = [calls.multi_context(mctx, k) for k in range(D)]
 
     def staged():
         return [_lib.staging_stats(s)[2] for s in sub]
 
+    # (the host forms allocate their outputs inside the timed call, as the product's callers do)
     def multi_explicit():
-        _lib.check(lib.dgpu_verify_multi(mctx.handle, code, _lib.ptr(pk), pk.size, n, _lib.ptr(c.rounds),
-                                         _lib.ptr(c.sigs), stride, _lib.ptr(c.sig_len), _lib.ptr(c.prev),
-                                         c.prev.shape[1], _lib.ptr(c.prev_len), _lib.MODE_PER_ROUND, 0, _lib.ptr(bits),
-                                         _lib.ptr(reason)))
+        reason = calls.verify_multi(mctx, code, c.pk, *c.records())
         return int(np.count_nonzero(reason)), [(hi - lo) * (stride + 4 + c.prev.shape[1] + 4 + 8) for lo, hi in shards]
 
     def multi_linked():
-        _lib.check(lib.dgpu_verify_segment_multi(mctx.handle, code, _lib.ptr(pk), pk.size, first, n, _lib.ptr(c.sigs),
-                                                 stride, _lib.ptr(c.sig_len), _lib.ptr(link), link.size,
-                                                 _lib.MODE_PER_ROUND, 0, _lib.ptr(bits), _lib.ptr(reason),
-                                                 _lib.ptr(rand)))
+        reason, _ = calls.verify_segment_multi(mctx, code, c.pk, first, c.sigs, c.sig_len, link)
         return int(np.count_nonzero(reason)), [(hi - lo) * (stride + 4) for lo, hi in shards]
 
     dev = torch.device("cuda", 0)
@@ -94,39 +78,37 @@ def main():
     d_bits = torch.zeros((n + 7) // 8 + 8, dtype=torch.uint8, device=dev)
     d_reason = torch.zeros(n, dtype=torch.uint8, device=dev)
     d_rand = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
-    null = ctypes.c_void_p(None)
     half = (n // 2 + 7) & ~7  # whole bitmap bytes in front of the second half
 
     def invalid_on_device():
         torch.cuda.synchronize()
         return int(torch.count_nonzero(d_reason).item())
 
+    def part(lo, hi):
+        """The records [lo, hi) and their outputs, as views of the device arrays."""
+        return (d_sigs[lo:hi], d_len[lo:hi]), (d_bits[lo // 8:], d_reason[lo:hi], d_rand[lo:hi])
+
+    def seed_call(lo, hi, seed):
+        recs, outs = part(lo, hi)
+        calls.verify_segment_device(ctx, code, c.pk, first + lo, *recs, seed, _lib.MODE_PER_ROUND, 0, *outs)
+
     def whole():
-        _lib.check(lib.dgpu_verify_segment_device(h, code, _lib.ptr(pk), pk.size, first, n, d_sigs.data_ptr(), stride,
-                                                  d_len.data_ptr(), _lib.ptr(link), link.size, _lib.MODE_PER_ROUND, 0,
-                                                  d_bits.data_ptr(), d_reason.data_ptr(), d_rand.data_ptr(), null))
+        seed_call(0, n, link)
         return invalid_on_device(), None
 
     def halves():
-        _lib.check(lib.dgpu_verify_segment_device(h, code, _lib.ptr(pk), pk.size, first, half, d_sigs.data_ptr(), stride,
-                                                  d_len.data_ptr(), _lib.ptr(link), link.size, _lib.MODE_PER_ROUND, 0,
-                                                  d_bits.data_ptr(), d_reason.data_ptr(), d_rand.data_ptr(), null))
-        _lib.check(lib.dgpu_verify_segment_shard_device(
-            h, code, _lib.ptr(pk), pk.size, first + half, n - half, d_sigs.data_ptr() + half * stride, stride,
-            d_len.data_ptr() + 4 * half, d_sigs.data_ptr() + (half - 1) * stride, d_len.data_ptr() + 4 * (half - 1),
-            _lib.MODE_PER_ROUND, 0, d_bits.data_ptr() + half // 8, d_reason.data_ptr() + half,
-            d_rand.data_ptr() + 32 * half, null))
+        seed_call(0, half, link)
+        recs, outs = part(half, n)
+        calls.verify_segment_shard_device(ctx, code, c.pk, first + half, *recs, d_sigs[half - 1], d_len[half - 1:half],
+                                          _lib.MODE_PER_ROUND, 0, *outs)
         return invalid_on_device(), None
 
     seed_half = c.sigs[half - 1].copy()  # (the host's copy of the record the shard call reads as its halo)
 
     def halves_by_seed():
         """The same split with the seed form for both halves: what splitting one call in two costs by itself."""
-        for lo, hi, sd in ((0, half, link), (half, n, seed_half)):
-            _lib.check(lib.dgpu_verify_segment_device(
-                h, code, _lib.ptr(pk), pk.size, first + lo, hi - lo, d_sigs.data_ptr() + lo * stride, stride,
-                d_len.data_ptr() + 4 * lo, _lib.ptr(sd), sd.size, _lib.MODE_PER_ROUND, 0, d_bits.data_ptr() + lo // 8,
-                d_reason.data_ptr() + lo, d_rand.data_ptr() + 32 * lo, null))
+        seed_call(0, half, link)
+        seed_call(half, n, seed_half)
         return invalid_on_device(), None
 
     print(f"linked segments across contexts vs their counterparts, per-round mode; {n} chained rounds, 64-round "

@@ -37,30 +37,22 @@ def main():
     args = ap.parse_args()
     import torch
     torch.cuda.init()
-    from drand_amd import _lib, synth
+    from drand_amd import _lib, calls, synth
     from drand_amd.chain import get_context
     ctx = get_context(0)
-    lib, h = ctx.lib, ctx.handle
     code, n = _lib.SCHEME_CHAINED, args.rounds
     c = synth.make_chain(args.seed, n, code, seg_len=64)
-    pk = np.frombuffer(c.pk, dtype=np.uint8).copy()
     link = c.prev[0, :c.prev_len[0]].copy()
-    bits = np.zeros((n + 7) // 8, dtype=np.uint8)
-    reason = np.zeros(n, dtype=np.uint8)
-    rand = None if args.no_randomness else np.zeros((n, 32), dtype=np.uint8)
     stride = c.sigs.shape[1]
 
+    # (both forms allocate their outputs inside the timed call, as the product's callers do)
     def explicit():
-        _lib.check(lib.dgpu_verify_beacons(h, code, _lib.ptr(pk), pk.size, n, _lib.ptr(c.rounds), _lib.ptr(c.sigs),
-                                           stride, _lib.ptr(c.sig_len), _lib.ptr(c.prev), c.prev.shape[1],
-                                           _lib.ptr(c.prev_len), _lib.MODE_PER_ROUND, 0, _lib.ptr(bits),
-                                           _lib.ptr(reason)))
+        reason = calls.verify_beacons(ctx, code, c.pk, *c.records())
         return int(np.count_nonzero(reason)), n * (stride + 4 + c.prev.shape[1] + 4 + 8)
 
     def linked():
-        _lib.check(lib.dgpu_verify_segment(h, code, _lib.ptr(pk), pk.size, int(c.rounds[0]), n, _lib.ptr(c.sigs),
-                                           stride, _lib.ptr(c.sig_len), _lib.ptr(link), link.size,
-                                           _lib.MODE_PER_ROUND, 0, _lib.ptr(bits), _lib.ptr(reason), _lib.ptr(rand)))
+        reason, _ = calls.verify_segment(ctx, code, c.pk, int(c.rounds[0]), c.sigs, c.sig_len, link,
+                                         randomness=not args.no_randomness)
         return int(np.count_nonzero(reason)), n * (stride + 4)
 
     forms = (("explicit", explicit, 0), ("linked", linked, len(range(64, n, 64))))

@@ -12,7 +12,6 @@ GPU the eight copy streams also share one PCIe link, which 8 GPUs do not).
         DGPU_TEST_STAGE_ONLY=1 python tools/stage_rehearsal.py [--rounds N] [--devices 8]
 """
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -23,12 +22,9 @@ sys.path.insert(0, ROOT)
 
 
 def stats(mctx, k):
-    from drand_amd import _lib
-    h = ctypes.c_void_p()
-    _lib.check(mctx.lib.dgpu_multi_context(mctx.handle, k, ctypes.byref(h)), mctx.lib)
-    ms, hms, nb = ctypes.c_double(), ctypes.c_double(), ctypes.c_uint64()
-    _lib.check(mctx.lib.dgpu_staging_stats(h, ctypes.byref(ms), ctypes.byref(hms), ctypes.byref(nb)), mctx.lib)
-    return {"device_ms": round(ms.value, 2), "host_ms": round(hms.value, 2), "bytes": nb.value}
+    from drand_amd import _lib, calls
+    ms, hms, nb = _lib.staging_stats(calls.multi_context(mctx, k))
+    return {"device_ms": round(ms, 2), "host_ms": round(hms, 2), "bytes": nb}
 
 
 def main():
