@@ -24,6 +24,7 @@
 #include "copy_pool.h"
 #include "kernels.cuh"
 #include "pairing_engine.cuh"
+#include "miller6_kernels.cuh"
 #include "lines_thread.cuh"
 #include "kb_thread.cuh"
 #include "recover.cuh"
@@ -287,6 +288,8 @@ struct dgpu_ctx {
   bool rlc_localize = true;      // DGPU_RLC_LOCALIZE=0: a failing RLC root goes straight to the random-coefficient tree (A/B)
   int rlc_descent_step = 3;      // DGPU_RLC_DESCENT_STEP: tree levels per descent step (children checked: 2^step; r04g: 3 > 2 > 5)
   bool lines_thread = true;      // DGPU_LINES=engine: T-steps on the 12-lane engine (k_eng_lines, A/B)
+  bool miller6 = true;           // DGPU_MILLER=lanes12: the Miller product on the 12-lane engine (k_eng_miller) at every
+                                 // size; default: chunks of thr_min items and more take k_eng_miller6 and the norm tail
   size_t thr_min = 65536;        // DGPU_THR_MIN=<items>: pairing chunks smaller than this take the lane kernels,
                                  // which fill the chip and cut the per-item latency (RLC node checks, r04k: 11.15M
                                  // -> 11.49M rounds/s at 0.1% corrupted; small per-round batches, r04z)
@@ -329,6 +332,8 @@ struct dgpu_ctx {
   double last_stage_host_ms = 0.0;
   bool test_stage_only = false;   // A/B build, DGPU_TEST_STAGE_ONLY=1: host-record calls stage and stop (staging rehearsal)
   size_t last_stage_bytes = 0;
+  bool test_miller_mark = false; // A/B build, DGPU_TEST_MILLER_MARK=1: the six-lane Miller launches get stage marks of their
+                                 // own (eng_miller6, eng_miller_tail), so a test can see which kernels a call ran
   bool kb_pair = false;          // A/B: DGPU_KB_PAIR=1, the Karabina chain on two lanes per round (k_kb_chain_pair)
   bool reduce_norm = false;      // A/B: DGPU_REDUCE_NORM=1, k_kb_chain_thr and k_lines_thr with the carried form of
                                  // fp_reduce_lz (fp.cuh; the form before profiles/r15)
@@ -740,7 +745,18 @@ int eng_pairing_locked(dgpu_ctx* c, const pairing_job& job, hipStream_t s) {
         RC_TRY(launch(k_eng_miller_xw, dim3(grid_for(cnt, ENG_XW_ITEMS)), dim3(ENG_XW_BLOCK), s, cnt, consts, lines, f, n1));
       else
 #endif
+      if (c->miller6 && cnt >= c->thr_min) {  // one Fp2 coefficient per lane, then N1 = Norm(f) from fbuf
+#ifdef DG_AB_KNOBS
+        if (c->test_miller_mark) mark(c, s, "eng_miller6");
+#endif
+        RC_TRY(launch(k_eng_miller6, dim3(grid_for(cnt, M6_ITEMS_PER_WAVE)), eng, s, cnt, lines, f));
+#ifdef DG_AB_KNOBS
+        if (c->test_miller_mark) mark(c, s, "eng_miller_tail");
+#endif
+        RC_TRY(launch(k_eng_miller_tail, blocks, eng, s, cnt, consts, f, n1));
+      } else {
         RC_TRY(launch(k_eng_miller, blocks, eng, s, cnt, consts, lines, f, n1));
+      }
     }
     const size_t inv_threads = std::max<size_t>(1, (cnt + 63) / 64);
     mark(c, s, "eng_inv");
@@ -2100,6 +2116,8 @@ int dgpu_open(int device, dgpu_ctx** out) {
   if (kcv && !strcmp(kcv, "lanes")) c->kb_thread = false;
   const char* lnv = getenv("DGPU_LINES");
   if (lnv && !strcmp(lnv, "engine")) c->lines_thread = false;
+  const char* mlv = getenv("DGPU_MILLER");
+  if (mlv && !strcmp(mlv, "lanes12")) c->miller6 = false;
   const char* tmv = getenv("DGPU_THR_MIN");
   if (tmv && atol(tmv) >= 0) c->thr_min = (size_t)atol(tmv);
   const char* rmv = getenv("DGPU_RLC_MIN");
@@ -2134,6 +2152,8 @@ int dgpu_open(int device, dgpu_ctx** out) {
   if (kic && atol(kic) >= 1) c->kb_inv_chain = (size_t)atol(kic);
   const char* ktf = getenv("DGPU_KB_TEST_FLAG");
   if (ktf && atol(ktf) >= 1) c->kb_test_flag = (size_t)atol(ktf);
+  const char* mmv = getenv("DGPU_TEST_MILLER_MARK");
+  if (mmv) c->test_miller_mark = !strcmp(mmv, "1");
   const char* kpv = getenv("DGPU_KB_PAIR");
   if (kpv) c->kb_pair = !strcmp(kpv, "1");
   const char* rnv = getenv("DGPU_REDUCE_NORM");

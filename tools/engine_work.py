@@ -43,12 +43,36 @@ def program_work(ops, prog):
 
 INV_MADS = 32 * 140 + 392  # one field inversion by divsteps (round 4; a^(p-2) was 82 mul + 380 sqr)
 
+MILLER_TAIL_OPS = 7  # miller6_kernels.cuh ENG_MILLER_TAIL_OPS: N1 = Norm(f), the program's last ops
+
+
+def miller6_work(ops):
+    """k_eng_miller6 (miller6.cuh) with its norm tail: six lanes per item, an
+    Fp2 product as 3 product terms.  A line product is 3 Fp2 products and 2
+    reductions on each lane.  The squaring in the direct form is 3 Fp2
+    products on every lane, 2 more terms (the plain square f_i^2) on the even
+    lanes, 2 reductions each.  The tail is the 12-lane program's."""
+    prog = G.prog_miller()
+    n_line = 2 * sum(1 for ins in prog if ins[0] == "ldline")
+    n_sqr = sum(1 for ins in prog if ins == ("run", "M_SQR"))
+    tail = program_work(ops, prog[-MILLER_TAIL_OPS:])
+    assert [ins[1] for ins in prog[-MILLER_TAIL_OPS:]] == ["M_XIF", "M_NRM", "M_XIN2", "M_T012", "M_XIT", "M_D", "M_N1"]
+    line_terms, sqr_terms, redc = 6 * 9, 3 * 11 + 3 * 9, 6 * 2
+    terms = n_line * line_terms + n_sqr * sqr_terms + tail["product_terms"]
+    reductions = (n_line + n_sqr) * redc + tail["reductions"]
+    simt = 6 * (n_line * (9 + 2) + n_sqr * (11 + 2)) * MADS_PER_PRODUCT + tail["simt_lane_mads"]
+    return {"product_terms": terms, "reductions": reductions, "line_products": n_line, "squarings": n_sqr,
+            "tail": tail, "mads": (terms + reductions) * MADS_PER_PRODUCT, "simt_lane_mads": simt}
+
 
 def main():
     ops = G.build_ops()
     kern = {
         "k_eng_lines": program_work(ops, G.prog_lines()),
-        "k_eng_miller": program_work(ops, G.prog_miller()),
+        # the shipped Miller kernels (k_eng_miller6 + k_eng_miller_tail); the 12-lane
+        # program, which small calls and DGPU_MILLER=lanes12 run, beside it
+        "k_eng_miller": miller6_work(ops),
+        "k_eng_miller_lanes12": program_work(ops, G.prog_miller()),
         "k_eng_fe": program_work(ops, G.prog_fe()),
         # Montgomery's trick: 3 Fp multiplications per item (392 mads each), one
         # inversion per 64 items amortized (fp.cuh fp_inv: 32 divstep batches of
@@ -87,9 +111,9 @@ def main():
     # from the key's fixed table, 8 of the 12 exports scaled by one Fp
     # multiplication (a P coordinate): 68 line steps x 8 x 392 mads more
     n_ld = sum(1 for ins in G.prog_miller() if ins[0] == "ldline")
-    fixed = dict(kern["k_eng_miller"])
+    fixed = dict(kern["k_eng_miller_lanes12"])  # k_eng_miller_fixed stays on the 12-lane program
     fixed["line_scalings"] = n_ld * 8
-    fixed["mads"] = kern["k_eng_miller"]["mads"] + n_ld * 8 * 392
+    fixed["mads"] = kern["k_eng_miller_lanes12"]["mads"] + n_ld * 8 * 392
     kern["k_eng_miller_fixed"] = fixed
     out = {
         "unit": "per item (one two-pair pairing check); mads = 32x32->64 v_mad_u64_u32 products the algorithm performs",

@@ -41,10 +41,12 @@ run_step() {
     python3 tools/rocpd_stats.py $(find $O/prof -name "*results.db" | head -1) > $O/kernel_stats.csv || true ;;
   traffic)
     # the third pass runs the engine lines kernel, whose 45,696 B/round of
-    # stores calibrate WRITE_SIZE (tools/traffic_summary.py)
-    for pass in fetch:FETCH_SIZE write:WRITE_SIZE write_cal:WRITE_SIZE; do
+    # stores calibrate WRITE_SIZE, the fourth the 12-lane Miller kernel, whose
+    # loads of the same bytes calibrate FETCH_SIZE (tools/traffic_summary.py)
+    for pass in fetch:FETCH_SIZE write:WRITE_SIZE write_cal:WRITE_SIZE fetch_cal:FETCH_SIZE; do
       name=${pass%%:*}
       ( [ $name = write_cal ] && export DGPU_LINES=engine
+        [ $name = fetch_cal ] && export DGPU_MILLER=lanes12
         timeout -s KILL 180 rocprofv3 --kernel-trace --output-format csv --pmc ${pass#*:} -d $O/traffic/$name -o p \
           -- python3 tools/prof_verify.py ${TRAFFIC_ARGS:---rounds 131072 --iters 1} > $O/traffic_$name.log 2>&1 ) \
         || return $?

@@ -15,7 +15,10 @@ line buffer gives an exact calibration for its 4-B-per-lane SoA accesses:
 k_eng_lines stores exactly 68 x 12 x 14 x 4 = 45,696 B per round and
 k_eng_miller loads exactly those bytes (inputs/constants of either kernel are
 < 1% of that), so write_cal = 45,696 / WRITE_SIZE(k_eng_lines) and
-fetch_cal = 45,696 / FETCH_SIZE(k_eng_miller); the corrected per-round bytes
+fetch_cal = 45,696 / FETCH_SIZE(k_eng_miller) (the 12-lane kernel; the bulk
+default k_eng_miller6 loads 8 B per lane, so the 12-lane kernel runs in a
+pass of its own under DGPU_MILLER=lanes12, fetch_cal/, as tools/gpu/session.sh
+makes it); the corrected per-round bytes
 (raw x cal) are what bench.py reports.  The line buffer (6 GB per chunk) far
 exceeds the 256 MiB Infinity Cache, so these bytes do reach HBM."""
 import csv
@@ -41,7 +44,7 @@ def main(d, rounds, out):
     cal_dir = os.path.join(d, "write_cal")
     tot = defaultdict(lambda: defaultdict(float))
     for sub in os.listdir(d):
-        if sub == "write_cal" or not os.path.isdir(os.path.join(d, sub)):
+        if sub in ("write_cal", "fetch_cal") or not os.path.isdir(os.path.join(d, sub)):
             continue
         for k, v in _totals(os.path.join(d, sub)).items():
             for c, x in v.items():
@@ -52,8 +55,13 @@ def main(d, rounds, out):
     if not wl and os.path.isdir(cal_dir):
         wl = _totals(cal_dir).get("dgpu::k_eng_lines", {}).get("WRITE_SIZE", 0) / rounds or None
     fm = raw.get("dgpu::k_eng_miller", {}).get("fetch")
+    fcal_dir = os.path.join(d, "fetch_cal")
+    if not fm and os.path.isdir(fcal_dir):
+        fm = _totals(fcal_dir).get("dgpu::k_eng_miller", {}).get("FETCH_SIZE", 0) / rounds or None
+    if not fm:
+        raise SystemExit("no fetch calibrator (k_eng_miller) in any pass: run the fetch_cal pass (DGPU_MILLER=lanes12)")
     write_cal = LINE_BYTES_PER_ROUND / wl if wl else 1.0
-    fetch_cal = LINE_BYTES_PER_ROUND / fm if fm else 1.0
+    fetch_cal = LINE_BYTES_PER_ROUND / fm
     res = {k: {"fetch_bytes_per_round": v["fetch"] * fetch_cal, "write_bytes_per_round": v["write"] * write_cal,
                "raw_fetch_size_per_round": v["fetch"], "raw_write_size_per_round": v["write"]}
            for k, v in raw.items()}
