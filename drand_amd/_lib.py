@@ -19,7 +19,8 @@ AB_KNOBS = frozenset({"DGPU_DEC_OVERLAP", "DGPU_MSM_SEG", "DGPU_LANE_SLICES", "D
                       "DGPU_RLC_LOCALIZE", "DGPU_G1_LINES", "DGPU_SUBGROUP", "DGPU_RECOVER", "DGPU_RECOVER_ROWS",
                       "DGPU_KB_INV_CHAIN", "DGPU_KB_TEST_FLAG", "DGPU_TEST_ALLOC_CAP", "DGPU_STAGE",
                       "DGPU_ENG_XW", "DGPU_TEST_STAGE_ONLY", "DGPU_LINES_WAVE", "DGPU_KB_PAIR", "DGPU_TEST_FORCE_EXC",
-                      "DGPU_REDUCE_NORM", "DGPU_KEYED_RANGE", "DGPU_TEST_MILLER_MARK"})
+                      "DGPU_REDUCE_NORM", "DGPU_KEYED_RANGE", "DGPU_TEST_MILLER_MARK",
+                      "DGPU_TEST_FE_MARK"})
 
 DGPU_OK = 0
 DGPU_EINVAL = -1

@@ -25,6 +25,7 @@
 #include "kernels.cuh"
 #include "pairing_engine.cuh"
 #include "miller6_kernels.cuh"
+#include "feseg6_kernels.cuh"
 #include "lines_thread.cuh"
 #include "kb_thread.cuh"
 #include "recover.cuh"
@@ -290,6 +291,8 @@ struct dgpu_ctx {
   bool lines_thread = true;      // DGPU_LINES=engine: T-steps on the 12-lane engine (k_eng_lines, A/B)
   bool miller6 = true;           // DGPU_MILLER=lanes12: the Miller product on the 12-lane engine (k_eng_miller) at every
                                  // size; default: chunks of thr_min items and more take k_eng_miller6 and the norm tail
+  bool feseg6 = true;            // DGPU_FESEG=lanes12: the Karabina FE's segments 1..5 on the 12-lane engine (k_eng_fe_seg) at
+                                 // every size; default: chunks of thr_min items and more take k_eng_fe_seg6
   size_t thr_min = 65536;        // DGPU_THR_MIN=<items>: pairing chunks smaller than this take the lane kernels,
                                  // which fill the chip and cut the per-item latency (RLC node checks, r04k: 11.15M
                                  // -> 11.49M rounds/s at 0.1% corrupted; small per-round batches, r04z)
@@ -334,6 +337,8 @@ struct dgpu_ctx {
   size_t last_stage_bytes = 0;
   bool test_miller_mark = false; // A/B build, DGPU_TEST_MILLER_MARK=1: the six-lane Miller launches get stage marks of their
                                  // own (eng_miller6, eng_miller_tail), so a test can see which kernels a call ran
+  bool test_fe_mark = false;     // A/B build, DGPU_TEST_FE_MARK=1: the six-lane FE segment launches get a stage mark of their
+                                 // own (eng_fe_seg6)
   bool kb_pair = false;          // A/B: DGPU_KB_PAIR=1, the Karabina chain on two lanes per round (k_kb_chain_pair)
   bool reduce_norm = false;      // A/B: DGPU_REDUCE_NORM=1, k_kb_chain_thr and k_lines_thr with the carried form of
                                  // fp_reduce_lz (fp.cuh; the form before profiles/r15)
@@ -618,14 +623,23 @@ int eng_fe_kb_locked(dgpu_ctx* c, const uint32_t* consts, size_t cnt, size_t cap
     const int so = ENG_PROG_FEK_OFF[seg], sl = ENG_PROG_FEK_OFF[seg + 1] - ENG_PROG_FEK_OFF[seg];
     const bool first = seg == 0, last = seg == nseg - 1;
 #ifdef DG_AB_KNOBS
-    if (c->eng_xw & 2)  // measured slower too (r06d)
+    if (c->eng_xw & 2) {  // measured slower too (r06d)
       RC_TRY(launch(first || last ? k_eng_fe_seg_xw<ENG_SLOTS_FE> : k_eng_fe_seg_xw<ENG_FEK_MID_SLOTS>,
                     dim3(grid_for(cnt, ENG_XW_ITEMS)), dim3(ENG_XW_BLOCK), s, so, sl, first, last, cnt, r0, consts, f, n1inv,
                     xbuf, flags, fb, st));
-    else
+      continue;
+    }
 #endif
+    if (!first && c->feseg6 && cnt >= c->thr_min) {  // segments 1..5 with one Fp2 coefficient per lane
+#ifdef DG_AB_KNOBS
+      if (c->test_fe_mark) mark(c, s, "eng_fe_seg6");
+#endif
+      RC_TRY(launch(k_eng_fe_seg6, dim3(grid_for(cnt, M6_ITEMS_PER_WAVE)), dim3(ENG_BLOCK), s, seg, cnt, r0, consts, xbuf,
+                    flags, fb, st));
+    } else {
       RC_TRY(launch(k_eng_fe_seg, dim3(blocks), dim3(ENG_BLOCK), s, so, sl, first, last, cnt, r0, consts, f, n1inv, xbuf,
                     flags, fb, st));
+    }
   }
   return launch(k_eng_fe_fb, dim3(ENG_FB_GRID), dim3(ENG_BLOCK), s, cnt, r0, consts, f, n1inv, st, flags, fb);
 }
@@ -2118,6 +2132,8 @@ int dgpu_open(int device, dgpu_ctx** out) {
   if (lnv && !strcmp(lnv, "engine")) c->lines_thread = false;
   const char* mlv = getenv("DGPU_MILLER");
   if (mlv && !strcmp(mlv, "lanes12")) c->miller6 = false;
+  const char* fsv = getenv("DGPU_FESEG");
+  if (fsv && !strcmp(fsv, "lanes12")) c->feseg6 = false;
   const char* tmv = getenv("DGPU_THR_MIN");
   if (tmv && atol(tmv) >= 0) c->thr_min = (size_t)atol(tmv);
   const char* rmv = getenv("DGPU_RLC_MIN");
@@ -2154,6 +2170,8 @@ int dgpu_open(int device, dgpu_ctx** out) {
   if (ktf && atol(ktf) >= 1) c->kb_test_flag = (size_t)atol(ktf);
   const char* mmv = getenv("DGPU_TEST_MILLER_MARK");
   if (mmv) c->test_miller_mark = !strcmp(mmv, "1");
+  const char* fmv = getenv("DGPU_TEST_FE_MARK");
+  if (fmv) c->test_fe_mark = !strcmp(fmv, "1");
   const char* kpv = getenv("DGPU_KB_PAIR");
   if (kpv) c->kb_pair = !strcmp(kpv, "1");
   const char* rnv = getenv("DGPU_REDUCE_NORM");

@@ -65,6 +65,29 @@ def miller6_work(ops):
             "tail": tail, "mads": (terms + reductions) * MADS_PER_PRODUCT, "simt_lane_mads": simt}
 
 
+def feseg6_work(ops, segs):
+    """The Karabina FE's segments as shipped: segment 0 on the 12-lane program,
+    segments 1..5 in k_eng_fe_seg6 (feseg6.cuh), six lanes per item.  An Fp12
+    product (E_MUL, E_MULCJ) is 6 Fp2 products of 3 terms and 2 reductions on
+    each lane; a Frobenius map is one Fp2 product by a constant in 4 terms and
+    2 reductions on each lane; A <- A^2 is miller6.cuh's general squaring (11
+    terms on even lanes, 9 on odd ones, 2 reductions each); conj has no
+    products."""
+    seg0 = program_work(ops, segs[0])
+    runs = [ins[1] for sg in segs[1:] for ins in sg if ins[0] == "run"]
+    assert set(runs) <= {"E_XIA", "E_MUL", "E_MULCJ", "E_CONJ", "E_FROB1", "E_FROB2", "E_CYCA"}
+    n_mul = sum(1 for r in runs if r in ("E_MUL", "E_MULCJ"))
+    n_frob = sum(1 for r in runs if r in ("E_FROB1", "E_FROB2"))
+    n_sqr = sum(1 for r in runs if r == "E_CYCA")
+    terms = n_mul * 6 * 18 + n_frob * 6 * 4 + n_sqr * (3 * 11 + 3 * 9)
+    redc = (n_mul + n_frob + n_sqr) * 6 * 2
+    simt = 6 * (n_mul * (18 + 2) + n_frob * (4 + 2) + n_sqr * (11 + 2)) * MADS_PER_PRODUCT
+    return {"product_terms": seg0["product_terms"] + terms, "reductions": seg0["reductions"] + redc,
+            "fp12_products": n_mul, "frobenius_maps": n_frob, "squarings": n_sqr, "segment0": seg0,
+            "mads": seg0["mads"] + (terms + redc) * MADS_PER_PRODUCT,
+            "simt_lane_mads": seg0["simt_lane_mads"] + simt}
+
+
 def main():
     ops = G.build_ops()
     kern = {
@@ -88,7 +111,6 @@ def main():
     # (k_eng_kb_dec: 12 sqr + 5 mul forward, 2 mul + 2 sqr per value after the
     # first backward, 17 mul per decompression)
     segs = G.prog_fe_kb()
-    seg_work = program_work(ops, [ins for sg in segs for ins in sg])
     cyc = {o.name: o for o in ops}["E_CYC"].subs[1]
     comp = {G.E_R + c for c in G.KB_COMP}
     sq_terms = sum(len(r.terms) for r in cyc if r.dst in comp)
@@ -102,7 +124,11 @@ def main():
     norm = 2 * ns * SQR + (ns - 1) * MUL
     inv = 3 * MUL + INV_MADS // KB_INV_CHAIN
     dec = 2 * ns * SQR + (ns - 1) * MUL + (ns - 1) * (2 * MUL + 2 * SQR) + ns * 17 * MUL
+    # the shipped segment kernels (k_eng_fe_seg(0), then k_eng_fe_seg6); the 12-lane
+    # program, which small calls and DGPU_FESEG=lanes12 run, beside it
+    seg_work = feseg6_work(ops, segs)
     kern["k_eng_fe_seg"] = seg_work
+    kern["k_eng_fe_seg_lanes12"] = program_work(ops, [ins for sg in segs for ins in sg])
     kern["k_eng_kb_chain"] = chain
     kern["k_eng_kb_inv"] = {"mads": n_exp * (norm + inv + dec), "per_exponentiation": {
         "k_eng_kb_norm": norm, "k_eng_inv": inv, "k_eng_kb_dec": dec}}
