@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("DRAND_GPU_LIB") or os.path.join(_HERE, "libdrand_gpu.
 AB_LIB_PATH = os.path.join(_HERE, "libdrand_gpu_ab.so")
 AB_KNOBS = frozenset({"DGPU_DEC_OVERLAP", "DGPU_MSM_SEG", "DGPU_LANE_SLICES", "DGPU_KB_NORM", "DGPU_RLC_DESCENT_STEP",
                       "DGPU_RLC_LOCALIZE", "DGPU_G1_LINES", "DGPU_SUBGROUP", "DGPU_RECOVER", "DGPU_RECOVER_ROWS",
+                      "DGPU_RECOVER_WIDE_BUDGET",
                       "DGPU_KB_INV_CHAIN", "DGPU_KB_TEST_FLAG", "DGPU_TEST_ALLOC_CAP", "DGPU_STAGE",
                       "DGPU_ENG_XW", "DGPU_TEST_STAGE_ONLY", "DGPU_LINES_WAVE", "DGPU_KB_PAIR", "DGPU_TEST_FORCE_EXC",
                       "DGPU_REDUCE_NORM", "DGPU_KEYED_RANGE", "DGPU_TEST_MILLER_MARK",
@@ -69,6 +70,7 @@ SYMBOLS = [
     ("dgpu_make_chain", _c.c_int, [_P, _c.c_int, _P, _c.c_size_t, _c.c_size_t, _P, _P, _P, _P]),
     ("dgpu_set_group", _c.c_int, [_P, _c.c_int, _c.c_int, _P]),
     ("dgpu_set_group_scheme", _c.c_int, [_P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_size_t]),
+    ("dgpu_set_group_wide", _c.c_int, [_P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_size_t]),
     ("dgpu_recover_batch_device", _c.c_int, [_P, _c.c_size_t, _P, _c.c_size_t, _P, _c.c_size_t, _P, _P, _P, _P, _P]),
     ("dgpu_make_partials", _c.c_int, [_P, _c.c_size_t, _P, _c.c_size_t, _P, _P, _P, _c.c_size_t, _P]),
     ("dgpu_make_partials_scheme", _c.c_int, [_P, _c.c_int, _c.c_size_t, _P, _c.c_size_t, _P, _P, _P, _c.c_size_t,
@@ -120,6 +122,7 @@ SYMBOLS = [
                                          _c.c_size_t, _P, _P, _c.c_size_t, _P, _P]),
     ("dgpu_multi_set_group", _c.c_int, [_P, _c.c_int, _c.c_int, _P]),
     ("dgpu_multi_set_group_scheme", _c.c_int, [_P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_size_t]),
+    ("dgpu_multi_set_group_wide", _c.c_int, [_P, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_size_t]),
     ("dgpu_recover_multi", _c.c_int, [_P, _c.c_size_t, _P, _c.c_size_t, _P, _c.c_size_t, _P, _P, _P, _P]),
     ("dgpu_verify_keyed", _c.c_int, [_P, _c.c_int, _c.c_size_t, _P, _c.c_size_t, _c.c_size_t, _P, _P, _c.c_size_t, _P,
                                      _P, _c.c_size_t, _P, _c.c_int, _c.c_uint64, _P, _P]),
@@ -174,6 +177,12 @@ def check(rc, lib=None):
 
 
 MAX_STAGES = 32  # DGPU_MAX_STAGES
+NARROW_MAX_T = 32  # dgpu_set_group[_scheme]'s largest threshold; above it dgpu_set_group_wide
+MAX_THRESHOLD = 1024  # DGPU_MAX_THRESHOLD
+# recover_wide.cuh: window-table bytes per term by "signatures on G1", and one chunk's budget
+# (tests/test_recover_wide_host.py compares all five with the headers' values)
+RECW_TERM_BYTES = {False: 3136, True: 1792}
+RECW_TABLE_BUDGET = 1 << 30
 
 
 def stage_times(ctx):

@@ -141,12 +141,15 @@ def derive_pubkey(ctx, code, sk):
 
 def set_group(ctx, code, t, n, commits, entry="dgpu_set_group"):
     """Install a group's t commitments (a list of bytes): dgpu_set_group for
-    48-byte G1 commitments, dgpu_set_group_scheme under a G1-signature scheme.
+    48-byte G1 commitments, dgpu_set_group_scheme under a G1-signature scheme,
+    and dgpu_set_group_wide for a threshold above 32 (up to DGPU_MAX_THRESHOLD).
     The context holds one group at a time: its key (returned) is recorded on
     the context object as `installed_group`, None while no group is known."""
     buf = _u8(b"".join(commits))
     ctx.installed_group = None
-    if code in G1_SIG_CODES:
+    if t > _lib.NARROW_MAX_T:
+        rc = getattr(ctx.lib, entry + "_wide")(ctx.handle, code, t, n, ptr(buf), len(commits[0]))
+    elif code in G1_SIG_CODES:
         rc = getattr(ctx.lib, entry + "_scheme")(ctx.handle, code, t, n, ptr(buf), len(commits[0]))
     else:
         rc = getattr(ctx.lib, entry)(ctx.handle, t, n, ptr(buf))

@@ -32,6 +32,7 @@
 #include "g1sig.cuh"
 #include "rlc_msm.cuh"
 #include "recover_g1.cuh"
+#include "recover_wide.cuh"
 #include "ingest_row.cuh"
 #include "check_rows.cuh"
 #include "keyed.cuh"
@@ -317,6 +318,8 @@ struct dgpu_ctx {
   DevBuf grp_wtab, rec_cls, rec_x_list, rec_x_msgs, rec_x_parts, rec_x_plen, rec_x_out, rec_x_ok, rec_x_st;
   DevBuf rec_tab, rec_tabz, rec_tabpre;  // the batched check's shared affine window tables
   DevBuf rec_tab_rows;                   // ... as 224-byte rows (the gather layout; r05l)
+  DevBuf rec_wide_tab;                   // a wide group's window tables, one chunk of rounds (rec_tab_wide_layout)
+  size_t recw_budget = RECW_TABLE_BUDGET;  // ... and that chunk's byte budget (DGPU_RECOVER_WIDE_BUDGET=<bytes>, A/B)
   bool recover_exact = false;    // DGPU_RECOVER=exact: every round on the per-partial path (A/B)
   size_t cof_engine_max = 16384;  // DGPU_COF_ENGINE_MAX=<rounds>: calls up to this size clear the hash cofactor on
                                  // the engine ladder (k_cof_*; 0 = always k_h2c_finish)
@@ -2164,6 +2167,8 @@ int dgpu_open(int device, dgpu_ctx** out) {
   if (rcv && !strcmp(rcv, "exact")) c->recover_exact = true;
   const char* rrv = getenv("DGPU_RECOVER_ROWS");
   if (rrv && !strcmp(rrv, "0")) c->recover_rows = false;
+  const char* rwb = getenv("DGPU_RECOVER_WIDE_BUDGET");
+  if (rwb && atol(rwb) >= 1) c->recw_budget = (size_t)atol(rwb);
   const char* kic = getenv("DGPU_KB_INV_CHAIN");
   if (kic && atol(kic) >= 1) c->kb_inv_chain = (size_t)atol(kic);
   const char* ktf = getenv("DGPU_KB_TEST_FLAG");

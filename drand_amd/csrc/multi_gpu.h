@@ -486,6 +486,16 @@ int dgpu_multi_set_group_scheme(dgpu_multi* m, int scheme, int t, int n, const u
   return DGPU_OK;
 }
 
+int dgpu_multi_set_group_wide(dgpu_multi* m, int scheme, int t, int n, const uint8_t* commits, size_t commit_len) {
+  if (!m) return set_err(DGPU_EINVAL, "null handle");
+  std::lock_guard<std::mutex> mlk(m->mu);
+  for (int k = 0; k < m->ndev; ++k) {
+    int rc = dgpu_set_group_wide(m->ctx[k], scheme, t, n, commits, commit_len);
+    if (rc) return set_err(rc, "device %d: %s", m->devs[k], std::string(g_last_error).c_str());
+  }
+  return DGPU_OK;
+}
+
 int dgpu_multi_set_group(dgpu_multi* m, int t, int n, const uint8_t* commits48) {
   if (!m) return set_err(DGPU_EINVAL, "null handle");
   std::lock_guard<std::mutex> mlk(m->mu);

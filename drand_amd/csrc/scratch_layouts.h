@@ -340,6 +340,29 @@ struct rec_sel_layout {
     xs = c.take<uint32_t>(n_rounds * RECOVER_MAX_T);
   }
 };
+// rec_sel of a wide group (recover_wide.cuh, t > RECOVER_MAX_T): the same two
+// regions at stride t
+struct rec_sel_wide_layout {
+  uint32_t *sel, *xs;  // [round][t]
+  void fill(carver& c, size_t n_rounds, size_t t) {
+    sel = c.take<uint32_t>(n_rounds * t);
+    xs = c.take<uint32_t>(n_rounds * t);
+  }
+};
+// rec_wide_tab: the window tables of one chunk of `rounds` rounds of a wide
+// group -- 8 entries per term, X and Y (aw words), Z until the batch inversion
+// (jw - aw words), the inversion's prefix products (one Fp) -- each an SoA over
+// the chunk's rounds * t * 8 entries (a shorter last chunk uses a prefix of
+// every region).  recw_chunk_rounds sizes `rounds` under RECW_TABLE_BUDGET.
+struct rec_tab_wide_layout {
+  uint32_t *tab, *tabz, *pre;
+  void fill(carver& c, size_t rounds, size_t t, int aw, int jw) {
+    const size_t ne = rounds * t * 8;
+    tab = c.take<uint32_t>(ne * aw);
+    tabz = c.take<uint32_t>(ne * (jw - aw));
+    pre = c.take<uint32_t>(ne * FP_WORDS);
+  }
+};
 // rec_part: the MSM's per-slice sums, slice i a Jacobian SoA of jw words per
 // round with stride n_rounds (the kernels take the base: part + i * jw *
 // n_rounds).  Sized for G2 points whatever the group.

@@ -92,11 +92,8 @@ int set_group_g1_locked(dgpu_ctx* c, int scheme, int t, int n, const uint8_t* co
   return DGPU_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int dgpu_set_group_scheme(dgpu_ctx* c, int scheme, int t, int n, const uint8_t* commits, size_t commit_len) {
+// dgpu_set_group_scheme and dgpu_set_group_wide: one body, the threshold limit given.
+int set_group_checked(dgpu_ctx* c, int scheme, int t, int n, const uint8_t* commits, size_t commit_len, int max_t) {
   if (!c || !commits) return set_err(DGPU_EINVAL, "null argument");
   if (!scheme_known(scheme)) return set_err(DGPU_EINVAL, "bad scheme %d", scheme);
   const bool g1 = sig_on_g1(scheme);
@@ -104,7 +101,7 @@ int dgpu_set_group_scheme(dgpu_ctx* c, int scheme, int t, int n, const uint8_t* 
   if (commit_len != want)
     return set_err(DGPU_EINVAL, "commitments of scheme %d are %zu bytes (compressed %s), got %zu", scheme, want,
                    g1 ? "G2" : "G1", commit_len);
-  if (t < 1 || t > RECOVER_MAX_T) return set_err(DGPU_EINVAL, "threshold t=%d outside [1, %d]", t, RECOVER_MAX_T);
+  if (t < 1 || t > max_t) return set_err(DGPU_EINVAL, "threshold t=%d outside [1, %d]", t, max_t);
   if (n < t || n > 65536) return set_err(DGPU_EINVAL, "group size n=%d invalid for t=%d", n, t);
   std::lock_guard<std::mutex> lk(c->mu);
   HIP_TRY(hipSetDevice(c->device));
@@ -112,6 +109,20 @@ int dgpu_set_group_scheme(dgpu_ctx* c, int scheme, int t, int n, const uint8_t* 
   // the group's tables may still be read by an earlier asynchronous recovery
   HIP_TRY(hipEventSynchronize(c->done));
   return g1 ? set_group_g1_locked(c, scheme, t, n, commits) : set_group_g2_locked(c, t, n, commits);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dgpu_set_group_scheme(dgpu_ctx* c, int scheme, int t, int n, const uint8_t* commits, size_t commit_len) {
+  return set_group_checked(c, scheme, t, n, commits, commit_len, RECOVER_MAX_T);
+}
+
+// (the installed group's t selects the recovery path: above RECOVER_MAX_T the wide one)
+int dgpu_set_group_wide(dgpu_ctx* c, int scheme, int t, int n, const uint8_t* commits, size_t commit_len) {
+  static_assert(RECOVER_WIDE_MAX_T == DGPU_MAX_THRESHOLD, "one limit");
+  return set_group_checked(c, scheme, t, n, commits, commit_len, DGPU_MAX_THRESHOLD);
 }
 
 int dgpu_set_group(dgpu_ctx* c, int t, int n, const uint8_t* commits48) {
@@ -169,15 +180,19 @@ int recover_begin_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_msgs, si
   const size_t key_words = g1 ? (size_t)G2A_WORDS : 2 * FP_LIMBS;
   int rc;
   lane_scratch& L = c->lane[0];
+  const bool wide = c->grp_t > RECOVER_MAX_T;  // (recover_wide.cuh: sel, xs and the digits at stride t)
+  const size_t t_stride = wide ? (size_t)c->grp_t : (size_t)RECOVER_MAX_T;
   rec_sel_layout sel;
+  rec_sel_wide_layout wsel;
   rec_part_layout part;
   static_assert(REC_G1J_WORDS == G1J_WORDS, "one G1 Jacobian SoA");
   if ((rc = c->rec_hidx.ensure(items * 4)) || (rc = c->rec_pk.ensure(items * key_words * 4)) ||
-      (rc = c->rec_idx.ensure(items * 4)) || (rc = c->rec_lam.ensure(n_rounds * RECOVER_MAX_T * RECOVER_SLOTS * 8)) ||
+      (rc = c->rec_idx.ensure(items * 4)) || (rc = c->rec_lam.ensure(n_rounds * t_stride * RECOVER_SLOTS * 8)) ||
       (rc = c->rec_pts.ensure(n_rounds * G2A_WORDS * 4)) || (rc = c->rec_vpk.ensure(n_rounds * key_words * 4)) ||
       (rc = c->rec_st.ensure(n_rounds)) || (rc = c->rec_cls.ensure(n_rounds)) ||
       (rc = L.h_pts.ensure(n_rounds * G2A_WORDS * 4)) || (rc = L.sig_pts.ensure(items * G2A_WORDS * 4)) ||
-      (rc = c->status.ensure(items)) || (rc = carve(c->rec_sel, &sel, n_rounds)) ||
+      (rc = c->status.ensure(items)) ||
+      (rc = wide ? carve(c->rec_sel, &wsel, n_rounds, t_stride) : carve(c->rec_sel, &sel, n_rounds)) ||
       (rc = carve(c->rec_part, &part, n_rounds, g1 ? G1J_WORDS : G2J_WORDS)))
     return rc;
   recover_walk& w = *out;
@@ -190,8 +205,8 @@ int recover_begin_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_msgs, si
   w.hidx = c->rec_hidx.u32();
   w.keys = c->rec_pk.u32();
   w.idx = c->rec_idx.u32();
-  w.sel = sel.sel;
-  w.xs = sel.xs;
+  w.sel = wide ? wsel.sel : sel.sel;
+  w.xs = wide ? wsel.xs : sel.xs;
   w.dig = c->rec_lam.u64();
   w.part = part.slice[0];  // (the kernels take the slices' base)
   w.rpts = c->rec_pts.u32();
@@ -249,6 +264,56 @@ int recover_msm_w4_launch(const recover_walk& w, const uint8_t* d_ok, hipStream_
   return launch_n(msm, 4 * w.n_rounds, 256, s, w.n_rounds, w.t, d_ok, w.sel, w.dig, w.sg, w.items, w.part, 4);
 }
 
+// ---- a wide group's launches (recover_wide.cuh; t > RECOVER_MAX_T)
+bool walk_wide(const recover_walk& w) { return w.t > RECOVER_MAX_T; }
+
+// Candidates / classes before the batched check (exact = false) or the
+// selection after the VerifyPartial pairings (exact = true): a block per round.
+int recover_walk_wide_launch(dgpu_ctx* c, const recover_walk& w, bool exact, int want_status, uint8_t* d_out,
+                             uint8_t* d_ok, hipStream_t s) {
+  return launch(exact ? k_recover_walk_wide<true> : k_recover_walk_wide<false>, dim3((unsigned)w.n_rounds), dim3(256), s,
+                w.n_rounds, w.m, w.t, want_status, w.idx, w.st, w.sel, w.xs, w.cls, d_ok, d_out, c->grp_commits.u32(),
+                w.rpts, w.rpk, w.rst);
+}
+
+int recover_lagrange_wide_launch(const recover_walk& w, const uint8_t* d_ok, uint64_t seed, hipStream_t s) {
+  return launch(k_recover_lagrange_wide, dim3((unsigned)w.n_rounds), dim3(RECW_LAG_THREADS), s, w.n_rounds, w.t, d_ok,
+                w.xs, w.dig, seed);
+}
+
+// The MSM of both paths (slices = 5: the batched check's sum too): the batch
+// in chunks of rounds whose window tables stay under the budget, enqueued in
+// order -- tables, batch inversion, L lanes per (round, slice).
+template <class G>
+int recover_msm_wide_chunks(dgpu_ctx* c, const recover_walk& w, const uint8_t* d_ok, int slices, int aw, hipStream_t s) {
+  const size_t per = recw_chunk_rounds(w.t, w.g1 ? RECW_TERM_BYTES_G1 : RECW_TERM_BYTES_G2, c->recw_budget);
+  rec_tab_wide_layout T;
+  int rc;
+  if ((rc = carve(c->rec_wide_tab, &T, per < w.n_rounds ? per : w.n_rounds, (size_t)w.t, aw, G::JW))) return rc;
+  const int L = recw_lanes(w.t);
+  for (size_t r0 = 0; r0 < w.n_rounds; r0 += per) {
+    const size_t nc = w.n_rounds - r0 < per ? w.n_rounds - r0 : per;
+    const size_t ne = nc * (size_t)w.t * 8;
+#ifdef DG_AB_KNOBS
+    // test hook: under a lowered budget (DGPU_RECOVER_WIDE_BUDGET) a profiled call marks its chunks, so a test
+    // can see that the budget took effect (the first four by name; the shipped library marks recover_msm alone)
+    static const char* const chunk_mark[4] = {"recover_msm_chunk0", "recover_msm_chunk1", "recover_msm_chunk2",
+                                              "recover_msm_chunk3"};
+    if (c->recw_budget != RECW_TABLE_BUDGET && r0 / per < 4) mark(c, s, chunk_mark[r0 / per]);
+#endif
+    RC_TRY(launch_n(k_recover_tables_wide<G>, nc * (size_t)w.t, 256, s, r0, nc, w.t, d_ok, w.sel, w.sg, w.items, T.tab,
+                    T.tabz));
+    RC_TRY(launch_n(w.g1 ? k_g1_batch_affine : k_g2_batch_affine, (ne + 15) / 16, 256, s, ne, T.tab, T.tabz, T.pre));
+    RC_TRY(launch_n(k_recover_msm_wide<G>, nc * (size_t)slices * L, 64, s, w.n_rounds, r0, nc, w.t, L, slices, d_ok, w.dig,
+                    T.tab, w.part));
+  }
+  return DGPU_OK;
+}
+int recover_msm_wide_locked(dgpu_ctx* c, const recover_walk& w, const uint8_t* d_ok, int slices, hipStream_t s) {
+  return w.g1 ? recover_msm_wide_chunks<recw_g1>(c, w, d_ok, slices, 2 * FP_WORDS, s)
+              : recover_msm_wide_chunks<recw_g2>(c, w, d_ok, slices, G2A_WORDS, s);
+}
+
 // The slices' sums to the round's signature: compressed into d_out's 96-byte
 // slot and affine in rpts; slices = 5 (batched check): rpts gets B.
 int recover_finish_launch(const recover_walk& w, const uint8_t* d_ok, uint8_t* d_out, int slices, hipStream_t s) {
@@ -261,6 +326,12 @@ int recover_finish_launch(const recover_walk& w, const uint8_t* d_ok, uint8_t* d
 // G1 signatures).
 int recover_combine_launch(dgpu_ctx* c, const recover_walk& w, uint8_t* d_ok, hipStream_t s) {
   mark(c, s, w.g1 ? "recover_rlc_g2" : "recover_rlc_g1");
+  if (walk_wide(w)) {  // L lanes per round over the key group's window table
+    const int L = recw_lanes(w.t);
+    return launch_n(w.g1 ? k_recover_rlc_wide<recw_g2> : k_recover_rlc_wide<recw_g1>, w.n_rounds * L, 64, s, w.n_rounds,
+                    w.t, L, c->grp_n, w.sel, w.idx, w.dig, c->grp_wtab.u32(), c->grp_commits.u32(), w.cls, d_ok, w.rpk,
+                    w.rst);
+  }
   return launch_n(w.g1 ? k_recover_rlc_g2 : k_recover_rlc_g1, w.n_rounds, 64, s, w.n_rounds, w.t, c->grp_n, w.sel, w.idx,
                   w.dig, c->grp_wtab.u32(), c->grp_commits.u32(), w.cls, d_ok, w.rpk, w.rst);
 }
@@ -307,13 +378,22 @@ int recover_exact_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_msgs, si
   if ((rc = recover_begin_locked(c, n_rounds, d_msgs, m, d_parts, stride, d_plen, true, s, &w))) return rc;
   // VerifyPartial of every partial on the engine
   if ((rc = eng_pairing_locked(c, item_key_job(c, w, w.items, w.hidx, w.sg, w.keys, w.st), s))) return rc;
+  const bool wide = walk_wide(w);
   mark(c, s, "recover_select");
-  RC_TRY(launch_n(k_recover_select, n_rounds, 64, s, n_rounds, m, w.t, w.idx, w.st, w.sel, w.xs, d_out, d_ok,
-                  c->grp_commits.u32(), w.rpts, w.rpk, w.rst));
+  if (wide)
+    RC_TRY(recover_walk_wide_launch(c, w, true, 0, d_out, d_ok, s));
+  else
+    RC_TRY(launch_n(k_recover_select, n_rounds, 64, s, n_rounds, m, w.t, w.idx, w.st, w.sel, w.xs, d_out, d_ok,
+                    c->grp_commits.u32(), w.rpts, w.rpk, w.rst));
   mark(c, s, "recover_lagrange");
-  RC_TRY(launch_n(k_recover_lagrange, n_rounds * RECOVER_MAX_T, 256, s, n_rounds, w.t, d_ok, w.xs, w.dig, 0));
+  if (wide)
+    RC_TRY(recover_lagrange_wide_launch(w, d_ok, 0, s));
+  else
+    RC_TRY(launch_n(k_recover_lagrange, n_rounds * RECOVER_MAX_T, 256, s, n_rounds, w.t, d_ok, w.xs, w.dig, 0));
   mark(c, s, "recover_msm");
-  if ((rc = w.g1 ? recover_msm_g1_locked(c, w, d_ok, 4, s) : recover_msm_w4_launch(w, d_ok, s)) ||
+  if ((rc = wide   ? recover_msm_wide_locked(c, w, d_ok, 4, s)
+            : w.g1 ? recover_msm_g1_locked(c, w, d_ok, 4, s)
+                   : recover_msm_w4_launch(w, d_ok, s)) ||
       (rc = recover_finish_launch(w, d_ok, d_out, 4, s)) || (rc = eng_pairing_locked(c, verify_recovered_job(c, w), s)))
     return rc;
   mark(c, s, "recover_verdict");
@@ -340,13 +420,22 @@ int recover_slots_locked(dgpu_ctx* c, size_t n_rounds, const uint8_t* d_msgs, si
   recover_walk w;
   int rc;
   if ((rc = recover_begin_locked(c, n_rounds, d_msgs, m, d_parts, stride, d_plen, false, s, &w))) return rc;
+  const bool wide = walk_wide(w);
   mark(c, s, "recover_select");
-  RC_TRY(launch_n(k_recover_cand, n_rounds, 64, s, n_rounds, m, w.t, d_status ? 1 : 0, w.idx, w.st, w.sel, w.xs, w.cls,
-                  d_ok, d_out));
+  if (wide)
+    RC_TRY(recover_walk_wide_launch(c, w, false, d_status ? 1 : 0, d_out, d_ok, s));
+  else
+    RC_TRY(launch_n(k_recover_cand, n_rounds, 64, s, n_rounds, m, w.t, d_status ? 1 : 0, w.idx, w.st, w.sel, w.xs, w.cls,
+                    d_ok, d_out));
   mark(c, s, "recover_lagrange");
-  RC_TRY(launch_n(k_recover_lagrange, n_rounds * RECOVER_MAX_T, 256, s, n_rounds, w.t, d_ok, w.xs, w.dig, seed));
+  if (wide)
+    RC_TRY(recover_lagrange_wide_launch(w, d_ok, seed, s));
+  else
+    RC_TRY(launch_n(k_recover_lagrange, n_rounds * RECOVER_MAX_T, 256, s, n_rounds, w.t, d_ok, w.xs, w.dig, seed));
   mark(c, s, "recover_msm");
-  if ((rc = w.g1 ? recover_msm_g1_locked(c, w, d_ok, 5, s) : recover_msm_g2_locked(c, w, d_ok, s)) ||
+  if ((rc = wide   ? recover_msm_wide_locked(c, w, d_ok, 5, s)
+            : w.g1 ? recover_msm_g1_locked(c, w, d_ok, 5, s)
+                   : recover_msm_g2_locked(c, w, d_ok, s)) ||
       (rc = recover_finish_launch(w, d_ok, d_out, 5, s)) || (rc = recover_combine_launch(c, w, d_ok, s)))
     return rc;
   // one pairing per round: e(A, H) e(-g1, B) == 1; G1 signatures: e(H, A) e(-B, g2) == 1

@@ -12,6 +12,9 @@ DistPublic.Coefficients): 48-byte G1 points for the G2-signature schemes,
 bls-unchained-g1-rfc9380), whose partials are BE16(index) || 48-byte G1
 signature and whose recovered signatures are 48 bytes.  No CPU fallback: the
 work runs in libdrand_gpu.so (dgpu_set_group_scheme / dgpu_recover_batch).
+Any threshold 1 <= t <= 1024 (DGPU_MAX_THRESHOLD) is accepted: above 32 the
+group is installed with dgpu_set_group_wide (calls.set_group) and the library
+takes its wide recovery path; above 1024 the library's error is raised.
 """
 import struct
 import threading

@@ -72,7 +72,8 @@ extern "C" {
  * dgpu_check_rows_multi).  Also additive: verification under a key per record
  * (dgpu_verify_keyed, dgpu_verify_keyed_device, reason DGPU_REASON_KEY) and
  * VerifyPartial of every slot without a recovery (dgpu_verify_partials,
- * dgpu_verify_partials_device). */
+ * dgpu_verify_partials_device).  Also additive: threshold groups above t = 32
+ * (dgpu_set_group_wide, dgpu_multi_set_group_wide, DGPU_MAX_THRESHOLD). */
 #define DGPU_ABI_VERSION 3
 
 /* scheme IDs (common/scheme/scheme.go:9,12; bls-unchained-on-g1 added by this build) */
@@ -619,7 +620,9 @@ int dgpu_derive_pubkey(dgpu_ctx *ctx, int scheme, const uint8_t *sk_be32, uint8_
  * (48 bytes each), group size n (share indices 0..n-1 get a precomputed
  * PubPoly.Eval table; larger indices are evaluated on the fly).
  * 1 <= t <= 32, t <= n <= 65536.  Rejects undecodable commitments.
- * Installs a G2-signature group (the two pedersen-bls schemes). */
+ * Installs a G2-signature group (the two pedersen-bls schemes).  drand's
+ * key.MinimumT is n/2 + 1, so t <= 32 serves groups of up to 63 nodes: larger
+ * groups are installed with dgpu_set_group_wide. */
 int dgpu_set_group(dgpu_ctx *ctx, int t, int n, const uint8_t *commits48);
 
 /* dgpu_set_group for any scheme.  DGPU_SCHEME_CHAINED / _UNCHAINED:
@@ -636,6 +639,24 @@ int dgpu_set_group(dgpu_ctx *ctx, int t, int n, const uint8_t *commits48);
  * commitment; a rejected G1-signature call leaves the installed group as it
  * was. */
 int dgpu_set_group_scheme(dgpu_ctx *ctx, int scheme, int t, int n, const uint8_t *commits, size_t commit_len);
+
+/* The largest threshold of dgpu_set_group_wide (groups of up to 2047 nodes
+ * under key.MinimumT). */
+#define DGPU_MAX_THRESHOLD 1024
+
+/* dgpu_set_group_scheme without its limit on t: 1 <= t <= DGPU_MAX_THRESHOLD,
+ * t <= n <= 65536.  For t <= 32 the call is exactly dgpu_set_group_scheme.
+ * Above, the same group state is built under the same rules (commitment
+ * decoding, subgroup checks, which rejected calls keep the installed group),
+ * and the recover and partial entry points (dgpu_recover_batch[_device],
+ * dgpu_recover_multi, dgpu_verify_partials[_device]) take their wide path:
+ * the same results by kernels that share a round's t terms among lanes
+ * (one Fr inversion per round for the Lagrange coefficients, L lanes per
+ * multi-scalar slice) and build the window tables of a batch in chunks of
+ * rounds of at most 1 GiB (RECW_TABLE_BUDGET; 3,136 t bytes per round for G2
+ * signatures, 1,792 t for G1), enqueued in order on the call's stream.
+ * Installing is O(n t) point operations per table. */
+int dgpu_set_group_wide(dgpu_ctx *ctx, int scheme, int t, int n, const uint8_t *commits, size_t commit_len);
 
 /* Batch form of key.Scheme.Recover (kyber tbls.Recover + share.RecoverCommit
  * (R)) as the aggregator calls it (chain/beacon/chain.go:158-168), n_rounds
@@ -801,6 +822,8 @@ int dgpu_check_rows_multi(dgpu_multi *m, int scheme, const uint8_t *pk, size_t p
 int dgpu_multi_set_group(dgpu_multi *m, int t, int n, const uint8_t *commits48);
 /* dgpu_set_group_scheme on every device of the handle. */
 int dgpu_multi_set_group_scheme(dgpu_multi *m, int scheme, int t, int n, const uint8_t *commits, size_t commit_len);
+/* dgpu_set_group_wide on every device of the handle. */
+int dgpu_multi_set_group_wide(dgpu_multi *m, int scheme, int t, int n, const uint8_t *commits, size_t commit_len);
 
 /* dgpu_recover_batch over the node: rounds shard contiguously across the
  * devices (dgpu_shard_range over n_rounds), each device recovers its shard,
